@@ -21,9 +21,13 @@ carries the RCCL unique id, the barriers and the max-over-ranks time.  If the C
 ABI's communicator cannot be used the torch.distributed twin runs instead, the
 line says so and the exit code is 3.
 
-Prints ONE JSON line on rank 0.  At N=1 the line also carries `host_path`: the
-reference's own calling pattern (a producer thread calls EnqueueSteps, the
-consumer GetConversionResult, double buffering on; benchmark.py:300-360) over 8
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times `--steps`
+passes and prints the line (its `roofline` quotes stored profiles and the live
+kernel time, no extra run).  `--dump-outputs DIR` writes what the last timed
+pass computed (see dump_outputs).  With `--full`, at N=1 the line also
+carries `host_path`: the reference's own calling pattern (a producer thread
+calls EnqueueSteps, the consumer GetConversionResult, double buffering on;
+benchmark.py:300-360) over 8
 bunches, PCIe transfers and index->ID conversion included -- measured after
 and outside the timed region of `value`; `host_path_copy`: the same with the
 caller's own copy of every result, which is what the reference's
@@ -33,7 +37,7 @@ maker half, 262 144 steps x 200 photons) with its roofline -- memory-side
 atomic requests against the rate the memory side delivers -- and an oracle
 baseline.  `roofline` prices the propagation kernel's
 algorithmic HBM bytes against the 8 TB/s peak (the kernel is VALU-bound, so the
-fraction is tiny by construction -- see DESIGN.md); `cpu_baseline` times the CPU
+fraction is tiny by construction -- see DESIGN.md); `cpu_baseline` (`--full`) times the CPU
 restatement of the reference kernel (oracle/, all host cores) on a bounded
 sample of the same workload.
 """
@@ -98,7 +102,30 @@ def parse():
                          "buffer (record counts and a 64-bit sum); config.gather_verified.  DEFAULT at N>1; at N=1 only with "
                          "CLSIMHIP_BENCH_GATHER=1 and this flag")
     ap.add_argument("--no-verify-gather", dest="verify_gather", action="store_false", help="N>1: skip the gather verification launch")
+    ap.add_argument("--full", action="store_true",
+                    help="N=1, c2/c3/c5: after the timed region also measure host_path, host_path_copy, cpu_baseline and (c2) table_maker; "
+                         "--no-host-path / --no-cpu-baseline / --no-table-maker leave one of them out.  Off: the line holds the timed "
+                         "region's figures only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="c2/c3/c5: write the detected photons of the last timed launch (rank 0) as DIR/hits.npy and DIR/hit_count.npy")
     return ap.parse_args()
+
+
+def dump_outputs(directory, photons, counted):
+    """`--dump-outputs`: what the caller of PropagateDevice receives from the last timed launch, in a form two builds can
+    compare.  hits.npy: float64, one row per detected photon record (min(counter, capacity) of them), one column per field
+    of PHOTON_DTYPE in its order (string / DOM fields hold indices), rows sorted (the kernel appends them in no fixed
+    order); above 64 MB a fixed seeded sample of the sorted rows.  hit_count.npy: float64 [the kernel's hit counter]."""
+    from clsim_amd.synthetic import PHOTON_DTYPE
+    os.makedirs(directory, exist_ok=True)
+    rows = np.stack([photons[name].astype(np.float64) for name in PHOTON_DTYPE.names], axis=1) if len(photons) else \
+        np.zeros((0, len(PHOTON_DTYPE.names)), dtype=np.float64)
+    rows = rows[np.lexsort(rows.T[::-1])]
+    limit = ((64 << 20) - 4096) // (rows.itemsize * len(PHOTON_DTYPE.names))        # (4 KB for the two files' headers and the count)
+    if len(rows) > limit:
+        rows = rows[np.sort(np.random.default_rng(20261016).choice(len(rows), limit, replace=False))]
+    np.save(os.path.join(directory, "hits.npy"), rows)
+    np.save(os.path.join(directory, "hit_count.npy"), np.array([counted], dtype=np.float64))
 
 
 def cpu_baseline(args, steps_np, seconds):
@@ -669,7 +696,9 @@ def main():
     sys.stdout.flush()
     JSON_FD = os.dup(1)
     os.dup2(2, 1)
-    if not args.no_cpu_baseline and int(os.environ.get("WORLD_SIZE", "1")) == 1:
+    if args.dump_outputs and (args.workload not in ("c2", "c3", "c5") or args.host_path):
+        raise SystemExit("bench.py: --dump-outputs covers the device path of --workload c2 | c3 | c5 (not --host-path)")
+    if args.full and not args.no_cpu_baseline and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         # the checker's library is built (a `make` child process) BEFORE anything initialises the GPU: a GPU-initialised
         # process must not spawn build tools under a profiler's preload
         from oracle import capi
@@ -901,6 +930,11 @@ def main():
     gather_stats = gatherer.statistics() if gatherer is not None else None
     counted_last = int(d_count[(state["pass"] - 1) % n_buffers].cpu().item())
     hits_last = min(counted_last, capacity)             # the counter keeps counting past the buffer; `capacity` records are stored
+    if args.dump_outputs and rank == 0:
+        from clsim_amd.synthetic import PHOTON_DTYPE
+        last = d_photons[(state["pass"] - 1) % n_buffers][:hits_last].cpu().numpy()
+        dump_outputs(args.dump_outputs, last.reshape(-1).view(PHOTON_DTYPE), counted_last)
+        del last
 
     t = torch.tensor([elapsed], dtype=torch.float64, device=ctl)
     if world > 1:
@@ -1098,7 +1132,7 @@ def main():
             out["rehearsal"] = ("FUNCTIONAL REHEARSAL, NOT A MEASUREMENT: %d ranks time-share one GPU, torch.distributed over gloo, "
                                 "RCCL library = %s" % (world, os.environ.get("CLSIMHIP_RCCL_LIBRARY", "(default)")))
             out["value"] = None
-        if world == 1 and not args.no_host_path:
+        if args.full and world == 1 and not args.no_host_path:
             # the reference's "actual" metric, outside the timed region of `value`: a second converter with two buffer sets
             del d_photons, d_count
             torch.cuda.empty_cache()
@@ -1109,9 +1143,9 @@ def main():
             # series of its own -- every record is copied out of the library's buffer (what the C++ adapter's GetConversionResult() does)
             out["host_path_copy"] = host_path_run(CV, args, steps_np, conv2, 8, in_place=False)
             del conv2
-        if not args.no_cpu_baseline and world == 1:      # reported on rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:      # reported on rank 0 at N=1 only
             out["cpu_baseline"] = cpu_baseline(args, steps_np, args.cpu_seconds)
-        if world == 1 and args.workload == "c2" and not args.no_table_maker and not args.keep_detected and args.shard_steps == 0:
+        if args.full and world == 1 and args.workload == "c2" and not args.no_table_maker and not args.keep_detected and args.shard_steps == 0:
             # BASELINE configs[4]'s other half, bounded: one warm-up and two timed passes of the table maker's own
             # bench bunch (262 144 steps x 200 photons, ~2 s a pass) after and outside the timed region of `value`, with its roofline
             # and an oracle baseline of a few seconds -- the same record `--workload tab` prints, so that a driver-run line holds it

@@ -1,4 +1,4 @@
-"""Build container only (skipped where /root/reference is absent; nothing of the reference travels).
+"""The C++ adapters' stand-in headers against the reference's own headers.  Nothing of the reference travels.
 
 1. The IceTray build of the C++ adapters (clsim_amd/cxx/, -DCLSIMHIP_WITH_ICETRAY) is compiled with
    -I/root/reference/public FIRST on the include path: every <clsim/...> header the adapter and its glue include is the
@@ -9,7 +9,12 @@
    The binary then runs the same checks as tests/test_icetray_adapter.py.
 2. Every stand-in under tests/stubs/clsim/ (used by the tests that do travel to the GPU box) is compared with the header it
    stands for: same virtual member functions in the same order (the vtable layout), with the same parameter lists, and
-   the same set of constructors."""
+   the same set of constructors.  What these checks need of the reference headers is stored as SHA-256 hashes in
+   tests/golden/reference_header_surfaces.json, so they run everywhere; where the reference tree is present they also check
+   that file against it (regenerate: python -c "from tests.test_reference_headers import write_surfaces; write_surfaces()").
+Part 1 needs the reference tree and is skipped where it is absent."""
+import hashlib
+import json
 import os
 import re
 import subprocess
@@ -23,7 +28,8 @@ CXX = os.path.join(ROOT, "clsim_amd", "cxx")
 REF_PUBLIC = "/root/reference/public"
 STUBS = os.path.join(ROOT, "tests", "stubs")
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF_PUBLIC, "clsim")), reason="the reference tree is not on this machine")
+SURFACES = os.path.join(ROOT, "tests", "golden", "reference_header_surfaces.json")
+HAVE_REFERENCE = os.path.isdir(os.path.join(REF_PUBLIC, "clsim"))
 
 
 def build_against_reference_headers(tmp_path):
@@ -38,6 +44,7 @@ def build_against_reference_headers(tmp_path):
     return exe, included
 
 
+@pytest.mark.skipif(not HAVE_REFERENCE, reason="the reference tree is not on this machine")
 def test_adapters_compile_and_run_against_the_reference_headers(tmp_path):
     exe, included = build_against_reference_headers(tmp_path)
     clsim = sorted(h for h in included if "/clsim/" in h)
@@ -173,31 +180,62 @@ def reference_header_of(cls, rel):
     raise AssertionError("no reference header defines " + cls)
 
 
-@pytest.mark.parametrize("rel", stub_headers())
-def test_stand_in_declares_what_the_reference_header_declares(rel):
+def _h(value):
+    """what the fixture stores of a declaration: the SHA-256 of its canonical form"""
+    return hashlib.sha256(repr(value).encode()).hexdigest()[:16]
+
+
+def stub_classes(rel):
     stub = _strip(_macro_expand(open(os.path.join(STUBS, "clsim", rel)).read(), os.path.join(STUBS, "clsim")))
     classes = re.findall(r"\b(?:struct|class)\s+(I3CLSim\w+)\b[^;{]*\{", stub)
     assert classes, rel
+    return stub, classes
+
+
+def reference_surface(rel):
+    """per class of stand-in `rel`, hashed: the reference class's base, its virtual members (in order and as a set), the names
+    of its base's virtual members, the virtual members it adds to its base (in order) and its constructors"""
+    out = {}
+    for cls in stub_classes(rel)[1]:
+        rv, rc, rbase = class_surface(_strip(open(reference_header_of(cls, rel)).read()), cls)
+        base_names = {v[0] for v in class_surface(_strip(open(reference_header_of(rbase, rel)).read()), rbase)[0]} if rbase else set()
+        out[cls] = {"base": _h(rbase), "virtuals": _h(rv), "virtual_set": sorted({_h(v) for v in rv}),
+                    "base_virtual_names": sorted({_h(n) for n in base_names}),
+                    "new_virtuals": _h([v for v in rv if v[0] not in base_names and v[0] != "~"]),
+                    "ctors": sorted({_h(c) for c in rc})}
+    return out
+
+
+def write_surfaces():
+    """needs the reference tree: writes tests/golden/reference_header_surfaces.json"""
+    with open(SURFACES, "w") as f:
+        json.dump({rel: reference_surface(rel) for rel in stub_headers()}, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
+@pytest.mark.parametrize("rel", stub_headers())
+def test_stand_in_declares_what_the_reference_header_declares(rel):
+    stub, classes = stub_classes(rel)
+    with open(SURFACES) as f:
+        stored = json.load(f)[rel]
+    if HAVE_REFERENCE:
+        assert reference_surface(rel) == stored, "the reference headers differ from %s: run write_surfaces()" % SURFACES
     for cls in classes:
-        real = _strip(open(reference_header_of(cls, rel)).read())
+        ref = stored[cls]
         sv, sc, sbase = class_surface(stub, cls)
-        rv, rc, rbase = class_surface(real, cls)
-        assert sbase == rbase, (cls, sbase, rbase)
-        if rbase is None:
+        assert _h(sbase) == ref["base"], (cls, sbase)
+        if sbase is None:
             # an interface root: same virtual functions in the same order (= the same vtable), same parameter types, same
             # constness; a virtual destructor only where the reference has one
-            assert sv == rv, "%s: virtual members differ\n stand-in: %s\n reference: %s" % (cls, sv, rv)
+            assert _h(sv) == ref["virtuals"], "%s: virtual members differ from the reference's\n stand-in: %s" % (cls, sv)
         else:
             # a derived class: overriders take their vtable slot from the base, so order is free; what the stand-in declares
             # virtual must exist in the reference class with the same signature, and virtuals the reference ADDS (new slots)
             # must all be there in the reference's order
-            rset = set(rv)
-            extra = [v for v in sv if v not in rset and v[0] != "~"]
+            extra = [v for v in sv if _h(v) not in ref["virtual_set"] and v[0] != "~"]
             assert not extra, "%s: the stand-in declares virtuals the reference lacks: %s" % (cls, extra)
-            base_names = {v[0] for v in class_surface(_strip(open(reference_header_of(rbase, rel)).read()), rbase)[0]}
-            new_real = [v for v in rv if v[0] not in base_names and v[0] != "~"]
-            new_stub = [v for v in sv if v[0] not in base_names and v[0] != "~"]
-            assert new_stub == new_real, "%s: new virtual members differ\n stand-in: %s\n reference: %s" % (cls, new_stub, new_real)
+            new_stub = [v for v in sv if _h(v[0]) not in ref["base_virtual_names"] and v[0] != "~"]
+            assert _h(new_stub) == ref["new_virtuals"], "%s: new virtual members differ from the reference's\n stand-in: %s" % (cls, new_stub)
         # every constructor the stand-in offers exists in the reference with the same parameter types
-        missing = {c for c in sc if c not in rc and c != ()}
-        assert not missing, "%s: the stand-in has constructors the reference lacks: %s (reference: %s)" % (cls, missing, rc)
+        missing = {c for c in sc if _h(c) not in ref["ctors"] and c != ()}
+        assert not missing, "%s: the stand-in has constructors the reference lacks: %s" % (cls, missing)

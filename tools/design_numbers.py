@@ -5,7 +5,7 @@ DESIGN.md; tests/test_design_numbers.py fails when DESIGN.md and the files disag
 import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 R = os.path.join(ROOT, "profiles", "r06")
-ROWS = [("C2 = configs[1] (the headline; `python bench.py`)", "final_bench_default_line.json", "final_c2_pmc_summary.json"),
+ROWS = [("C2 = configs[1] (the headline; `python bench.py --full`)", "final_bench_default_line.json", "final_c2_pmc_summary.json"),
         ("C3 = configs[2], 10 M steps in two bunches (`--workload c3`)", "final_bench_c3.json", "final_c3_pmc_summary.json"),
         ("C5 = configs[4], flasher half (`--workload c5`)", "final_bench_c5.json", "final_c5_pmc_summary.json"),
         ("the reference's benchmark.py, steps born in HBM (`--workload benchmark`)", "final_bench_benchmark.json", None),

@@ -10,7 +10,7 @@ PART=${2:-all}
 mkdir -p $OUT
 B="timeout -k 10 400 python3 bench.py"
 if [ "$PART" != "prof" ]; then
-$B > $OUT/final_bench_default_line.json 2> $OUT/default.err; echo default rc=$?
+$B --full > $OUT/final_bench_default_line.json 2> $OUT/default.err; echo default rc=$?
 $B --workload c3 --no-cpu-baseline --no-host-path --steps 5 --warmup 1 > $OUT/final_bench_c3.json 2> $OUT/c3.err; echo c3 rc=$?
 $B --workload c5 --no-cpu-baseline --no-host-path --steps 5 --warmup 1 > $OUT/final_bench_c5.json 2> $OUT/c5.err; echo c5 rc=$?
 $B --workload benchmark --steps 5 --warmup 1 > $OUT/final_bench_benchmark.json 2> $OUT/benchmark.err; echo benchmark rc=$?
