@@ -123,6 +123,8 @@ SYMBOLS = [
     "clsimhip_tabulator_get_bin_content", "clsimhip_tabulator_get_bin_sums", "clsimhip_tabulator_get_bin_edges",
     "clsimhip_tabulator_get_statistics", "clsimhip_tabulator_get_rng_state", "clsimhip_tabulator_get_table",
     "clsimhip_tabulator_write_fits_file",
+    "clsimhip_mcpe_generator_create", "clsimhip_mcpe_generator_destroy", "clsimhip_mcpe_generator_last_error",
+    "clsimhip_mcpe_convert_host", "clsimhip_mcpe_convert_device", "clsimhip_set_mcpe_generator", "clsimhip_get_result_mcpes",
 ]
 
 _lib = None
@@ -265,6 +267,13 @@ def load():
         "clsimhip_tabulator_get_statistics": (i32, [vp, DP]),
         "clsimhip_tabulator_get_rng_state": (i32, [vp, vp, sz]),
         "clsimhip_tabulator_get_table": (C.c_long, [vp, C.c_char_p, DP, sz]),
+        "clsimhip_mcpe_generator_create": (i32, [C.POINTER(Function), sz, sz, vp, vp, vp, C.POINTER(Polynomial), dbl, dbl, dbl, u64, C.POINTER(vp)]),
+        "clsimhip_mcpe_generator_destroy": (None, [vp]),
+        "clsimhip_mcpe_generator_last_error": (C.c_char_p, [vp]),
+        "clsimhip_mcpe_convert_host": (i32, [vp, vp, sz, vp, sz, C.POINTER(sz), vp]),
+        "clsimhip_mcpe_convert_device": (i32, [vp, i32, vp, vp, sz, vp, sz, vp, vp]),
+        "clsimhip_set_mcpe_generator": (i32, [vp, vp, i32]),
+        "clsimhip_get_result_mcpes": (i32, [vp, vp, C.POINTER(vp), C.POINTER(sz)]),
         "clsimhip_tabulator_write_fits_file": (i32, [vp, C.c_char_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double), sz]),
     }
     for name in SYMBOLS:

@@ -323,6 +323,71 @@ class I3CLSimSimpleGeometry:
         return cls(g["string_ids"], g["dom_ids"], g["x"], g["y"], g["z"], g["subdetectors"], g["om_radius"])
 
 
+# clsimhip_mcpe: I3MCPE(particle, npe = 1, time) with the DOM it belongs to; `id` is the step's / photon's identifier
+MCPE_DTYPE = np.dtype([("id", "<u4"), ("stringID", "<i2"), ("omID", "<u2"), ("time", "<f8")])
+MCPE_CONDITIONS = ("negative_weight", "off_surface", "unknown_dom", "probability_above_one")
+
+
+class MCPEGenerator:
+    """Detected photons -> MCPEs (clsimhip_mcpe_generator): I3CLSimPhotonToMCPEConverterForDOMs::Convert
+    (private/clsim/dom/I3PhotonToMCPEConverter.cxx:602-669) as a function of the record and a seed.
+
+    wavelengthAcceptances: up to 8 I3CLSimFunctionFromTable (equal spacing) / I3CLSimFunctionConstant; stringIDs, omIDs,
+    classIndex: the class of every DOM; angularAcceptance: an I3CLSimFunctionPolynomial.  Give it to initializeHIP(...,
+    mcpeGenerator=...) to run on the GPU behind the propagator, or call ConvertHost / ConvertDevice on records."""
+
+    def __init__(self, wavelengthAcceptances, stringIDs, omIDs, classIndex, angularAcceptance, domRadius=0.16510,
+                 oversizeFactor=1.0, pancakeFactor=1.0, seed=0):
+        self._lib = _lib.load()
+        self._h = C.c_void_p()
+        self._keep = list(wavelengthAcceptances)
+        descs = (_lib.Function * len(self._keep))(*[f._desc() for f in self._keep])
+        sid = np.ascontiguousarray(stringIDs, dtype=np.int32)
+        did = np.ascontiguousarray(omIDs, dtype=np.uint32)
+        cls = np.ascontiguousarray(classIndex, dtype=np.int32)
+        if not (len(sid) == len(did) == len(cls)):
+            raise ValueError("stringIDs, omIDs and classIndex must have the same length")
+        poly = _lib.Polynomial()
+        coeff = np.ascontiguousarray(angularAcceptance.coefficients, dtype=np.float64)
+        poly.n = len(coeff)
+        poly.coefficients = _dp(coeff)
+        poly.range_min, poly.range_max = angularAcceptance.rangemin, angularAcceptance.rangemax
+        poly.underflow, poly.overflow = angularAcceptance.underflow, angularAcceptance.overflow
+        _check(self._lib.clsimhip_mcpe_generator_create(descs, len(self._keep), len(sid), sid.ctypes.data_as(C.c_void_p),
+                                                        did.ctypes.data_as(C.c_void_p), cls.ctypes.data_as(C.c_void_p), C.byref(poly),
+                                                        float(domRadius), float(oversizeFactor), float(pancakeFactor), int(seed),
+                                                        C.byref(self._h)))
+
+    def __del__(self):
+        try:
+            if self._h:
+                self._lib.clsimhip_mcpe_generator_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def ConvertHost(self, photons):
+        """(mcpes, counters): the host twin, in input order; counters = {condition: count} (MCPE_CONDITIONS)"""
+        photons = np.ascontiguousarray(photons, dtype=PHOTON_DTYPE)
+        out = np.zeros(len(photons), dtype=MCPE_DTYPE)
+        n, counters = C.c_size_t(), np.zeros(4, dtype=np.uint64)
+        _check(self._lib.clsimhip_mcpe_convert_host(self._h, photons.ctypes.data_as(C.c_void_p), len(photons), out.ctypes.data_as(C.c_void_p),
+                                                    len(out), C.byref(n), counters.ctypes.data_as(C.c_void_p)))
+        return out[:n.value], dict(zip(MCPE_CONDITIONS, (int(c) for c in counters)))
+
+    def ConvertDevice(self, d_photons, d_hit_count, capacity, d_mcpes, mcpe_capacity, d_counters, device=0, stream=0):
+        """the kernel on device-resident records (addresses); d_counters: five uint32, [0] MCPEs made, [1..4] MCPE_CONDITIONS"""
+        _check(self._lib.clsimhip_mcpe_convert_device(self._h, int(device), C.c_void_p(d_photons), C.c_void_p(d_hit_count), int(capacity),
+                                                      C.c_void_p(d_mcpes), int(mcpe_capacity), C.c_void_p(d_counters), C.c_void_p(stream)))
+
+
+class ConversionResult(tuple):
+    """What GetConversionResult / GetConversionResultInPlace return: the tuple (identifier, photons[, histories]) / (identifier,
+    photons, release), with the bunch's MCPEs (MCPE_DTYPE) as attribute `mcpes` when the converter has an MCPE generator (None
+    otherwise)"""
+    mcpes = None
+
+
 class I3CLSimStepToPhotonConverterHIP:
     """MI355X implementation of I3CLSimStepToPhotonConverter."""
 
@@ -331,6 +396,7 @@ class I3CLSimStepToPhotonConverterHIP:
         self._h = C.c_void_p()
         _check(self._lib.clsimhip_create(int(device), C.byref(self._h)))
         self._history_entries = 0
+        self._mcpe = None
 
     def __del__(self):
         try:
@@ -376,6 +442,11 @@ class I3CLSimStepToPhotonConverterHIP:
     def SetPhotonHistoryEntries(self, v):
         self._call("clsimhip_set_photon_history_entries", int(v))
         self._history_entries = int(v)
+    def SetMCPEGenerator(self, generator, keepPhotons=True):
+        """generator: an MCPEGenerator or None (off).  keepPhotons=False: results carry MCPEs only, the photon records stay on
+        the device (the client module's two switches, frame->photons / frame->hits)"""
+        self._call("clsimhip_set_mcpe_generator", generator._h if generator is not None else None, int(bool(keepPhotons)))
+        self._mcpe = generator
     def SetWorkgroupSize(self, v): self._call("clsimhip_set_workgroup_size", int(v))
     def SetMaxNumWorkitems(self, v): self._call("clsimhip_set_max_num_workitems", int(v))
 
@@ -403,12 +474,24 @@ class I3CLSimStepToPhotonConverterHIP:
         steps = np.ascontiguousarray(steps, dtype=STEP_DTYPE)
         self._call("clsimhip_enqueue_steps", steps.ctypes.data_as(C.c_void_p), len(steps), int(identifier))
 
+    def _result_mcpes(self, ptr):
+        """copy of the MCPEs of the result `ptr` belongs to (None without a generator)"""
+        if self._mcpe is None:
+            return None
+        mp, mn = C.c_void_p(), C.c_size_t()
+        self._call("clsimhip_get_result_mcpes", ptr, C.byref(mp), C.byref(mn))
+        mcpes = np.zeros(mn.value, dtype=MCPE_DTYPE)
+        if mn.value:
+            C.memmove(mcpes.ctypes.data, mp.value, mn.value * 16)
+        return mcpes
+
     def GetConversionResult(self, with_histories=False, out=None):
         """ConversionResult_t (I3CLSimStepToPhotonConverter.h:70-90): (identifier, photons), plus with
         with_histories=True the photonHistories as a list of [k_i, 4] arrays (k_i = min(numScatters_i,
         PhotonHistoryEntries); None when no histories are recorded).  The photons are copied out of the library's buffer
         (like the C++ adapter copies them into the I3CLSimPhotonSeries it hands to the caller): into `out`, a PHOTON_DTYPE
-        array the caller recycles, when it is given and large enough -- a view of it is returned."""
+        array the caller recycles, when it is given and large enough -- a view of it is returned.  With an MCPE generator the
+        result's attribute `mcpes` holds the bunch's MCPEs."""
         # a recycled buffer is written through its raw address: it must be exactly what the records are -- checked before a
         # result is taken, whatever that result holds (the contract does not depend on the data)
         if out is not None and not (isinstance(out, np.ndarray) and out.dtype == PHOTON_DTYPE and out.ndim == 1 and out.flags.c_contiguous
@@ -417,38 +500,56 @@ class I3CLSimStepToPhotonConverterHIP:
         ident, ptr, n = C.c_uint32(), C.c_void_p(), C.c_size_t()
         self._call("clsimhip_get_conversion_result", C.byref(ident), C.byref(ptr), C.byref(n))
         histories = None
-        if n.value:
-            buf = (C.c_char * (n.value * 80)).from_address(ptr.value)
-            if out is not None and len(out) >= n.value:
-                C.memmove(out.ctypes.data, ptr.value, n.value * 80)
-                photons = out[:n.value]
+        try:            # whatever fails below, the result goes back to the library
+            if n.value:
+                buf = (C.c_char * (n.value * 80)).from_address(ptr.value)
+                if out is not None and len(out) >= n.value:
+                    C.memmove(out.ctypes.data, ptr.value, n.value * 80)
+                    photons = out[:n.value]
+                else:
+                    photons = np.frombuffer(buf, dtype=PHOTON_DTYPE).copy()
+                if with_histories:
+                    hp, entries = C.POINTER(C.c_float)(), C.c_uint32()
+                    self._call("clsimhip_get_result_histories", ptr, C.byref(hp), C.byref(entries))
+                    if hp and entries.value:
+                        flat = np.ctypeslib.as_array(hp, shape=(n.value, entries.value, 4)).copy()
+                        histories = [flat[i, :min(int(photons["numScatters"][i]), entries.value)] for i in range(n.value)]
             else:
-                photons = np.frombuffer(buf, dtype=PHOTON_DTYPE).copy()
-            if with_histories:
-                hp, entries = C.POINTER(C.c_float)(), C.c_uint32()
-                self._call("clsimhip_get_result_histories", ptr, C.byref(hp), C.byref(entries))
-                if hp and entries.value:
-                    flat = np.ctypeslib.as_array(hp, shape=(n.value, entries.value, 4)).copy()
-                    histories = [flat[i, :min(int(photons["numScatters"][i]), entries.value)] for i in range(n.value)]
-            self._call("clsimhip_release_result", ptr)
-        else:
-            photons = np.zeros(0, dtype=PHOTON_DTYPE)
-            if with_histories and self._history_entries:
-                histories = []
-        return (ident.value, photons, histories) if with_histories else (ident.value, photons)
+                photons = np.zeros(0, dtype=PHOTON_DTYPE)
+                if with_histories and self._history_entries:
+                    histories = []
+            mcpes = self._result_mcpes(ptr)
+        finally:
+            if n.value or self._mcpe is not None:
+                self._call("clsimhip_release_result", ptr)
+        result = ConversionResult((ident.value, photons, histories) if with_histories else (ident.value, photons))
+        result.mcpes = mcpes
+        return result
 
     def GetConversionResultInPlace(self):
         """(identifier, photons, release): `photons` is a read-only view of the library's page-locked result buffer -- what
         a C or C++ consumer that works on the records where they are gets from clsimhip_get_conversion_result -- valid until
-        `release()` is called (clsimhip_release_result), which the caller must do"""
+        `release()` is called (clsimhip_release_result), which the caller must do.  With an MCPE generator the returned tuple's
+        attribute `mcpes` holds a copy of the bunch's MCPEs (also when the result carries no photon records)."""
         ident, ptr, n = C.c_uint32(), C.c_void_p(), C.c_size_t()
         self._call("clsimhip_get_conversion_result", C.byref(ident), C.byref(ptr), C.byref(n))
+        try:
+            mcpes = self._result_mcpes(ptr)
+        except Exception:
+            if n.value or self._mcpe is not None:
+                self._call("clsimhip_release_result", ptr)
+            raise
         if not n.value:
-            return ident.value, np.zeros(0, dtype=PHOTON_DTYPE), (lambda: None)
-        buf = (C.c_char * (n.value * 80)).from_address(ptr.value)
-        view = np.frombuffer(buf, dtype=PHOTON_DTYPE)
-        view.flags.writeable = False
-        return ident.value, view, (lambda: self._call("clsimhip_release_result", ptr))
+            if self._mcpe is not None:          # (the handle of a result without photon records)
+                self._call("clsimhip_release_result", ptr)
+            result = ConversionResult((ident.value, np.zeros(0, dtype=PHOTON_DTYPE), (lambda: None)))
+        else:
+            buf = (C.c_char * (n.value * 80)).from_address(ptr.value)
+            view = np.frombuffer(buf, dtype=PHOTON_DTYPE)
+            view.flags.writeable = False
+            result = ConversionResult((ident.value, view, (lambda: self._call("clsimhip_release_result", ptr))))
+        result.mcpes = mcpes
+        return result
 
     def _size(self, name):
         v = C.c_size_t()
@@ -584,9 +685,11 @@ def initializeHIP(device, geometry, medium, wavelengthGenerationBias, wavelength
                   enableDoubleBuffering=False, doublePrecision=False, stopDetectedPhotons=True, saveAllPhotons=False,
                   saveAllPhotonsPrescale=0.01, fixedNumberOfAbsorptionLengths=float("nan"), pancakeFactor=1.0,
                   photonHistoryEntries=0, limitWorkgroupSize=0, approximateNumberOfWorkItems=262144,
-                  seed=12345, streams=None, tuning=None):
+                  seed=12345, streams=None, tuning=None, mcpeGenerator=None, keepPhotons=True):
     """Canonical configuration sequence, I3CLSimModuleHelper::initializeOpenCL
-    (ModuleHelper.cxx:303-372).  tuning: {key: value} for clsimhip_set_tuning, applied before Compile()."""
+    (ModuleHelper.cxx:303-372).  tuning: {key: value} for clsimhip_set_tuning, applied before Compile().
+    mcpeGenerator: an MCPEGenerator that turns every bunch's photons into MCPEs on the GPU (result attribute `mcpes`);
+    keepPhotons=False then leaves the photon records on the device."""
     conv = I3CLSimStepToPhotonConverterHIP(device)
     for key, value in (tuning or {}).items():
         conv.SetTuning(key, value)
@@ -602,6 +705,8 @@ def initializeHIP(device, geometry, medium, wavelengthGenerationBias, wavelength
     conv.SetFixedNumberOfAbsorptionLengths(fixedNumberOfAbsorptionLengths)
     conv.SetDOMPancakeFactor(pancakeFactor)
     conv.SetPhotonHistoryEntries(photonHistoryEntries)
+    if mcpeGenerator is not None:
+        conv.SetMCPEGenerator(mcpeGenerator, keepPhotons)
     conv.Compile()
     max_wg = conv.GetMaxWorkgroupSize()
     if limitWorkgroupSize:

@@ -12,11 +12,13 @@
 #include "tabulator.h"
 #include "step_store.h"
 #include "flasher.h"
+#include "mcpe.h"
 
 using namespace clsimhip;
 
 struct clsimhip_converter { Converter impl; explicit clsimhip_converter(int dev) : impl(dev) {} };
 struct clsimhip_medium { MediumData data; };
+struct clsimhip_mcpe_generator { std::shared_ptr<McpeGenerator> impl; };
 struct clsimhip_tabulator {
     std::unique_ptr<Tabulator> impl;
 };
@@ -948,6 +950,47 @@ long clsimhip_tabulator_get_table(const clsimhip_tabulator *t, const char *name,
     long n = -1;
     const int rc = guarded_tab(const_cast<clsimhip_tabulator *>(t), [&] { need(t, "tabulator"); need(name, "name"); n = t->impl->get_table(name, out, cap); });
     return rc == CLSIMHIP_OK ? n : rc;
+}
+
+// ---- MCPE generator (mcpe.h) ----
+int clsimhip_mcpe_generator_create(const clsimhip_function *classes, size_t n_classes, size_t n_doms, const int32_t *string_ids,
+                                   const uint32_t *om_ids, const int32_t *class_index, const clsimhip_polynomial *angular_acceptance,
+                                   double dom_radius, double oversize, double pancake, uint64_t seed, clsimhip_mcpe_generator **out)
+{
+    return guarded(nullptr, [&] {
+        need(classes, "classes"); need(angular_acceptance, "angular_acceptance"); need(out, "out");
+        std::vector<FunctionData> fs;
+        for (size_t k = 0; k < n_classes; ++k) fs.push_back(function_from(classes + k));
+        *out = new clsimhip_mcpe_generator{std::make_shared<McpeGenerator>(fs, n_doms, string_ids, om_ids, class_index, *angular_acceptance,
+                                                                          dom_radius, oversize, pancake, seed)};
+    });
+}
+void clsimhip_mcpe_generator_destroy(clsimhip_mcpe_generator *g) { delete g; }
+const char *clsimhip_mcpe_generator_last_error(const clsimhip_mcpe_generator *g) { (void)g; return g_last_error.c_str(); }
+int clsimhip_mcpe_convert_host(const clsimhip_mcpe_generator *g, const clsimhip_photon *photons, size_t n, clsimhip_mcpe *out,
+                               size_t capacity, size_t *n_out, uint64_t counters[4])
+{
+    return guarded(nullptr, [&] {
+        need(g, "generator");
+        if (counters) std::memset(counters, 0, 4 * sizeof(uint64_t));
+        g->impl->convert_host(photons, n, out, capacity, n_out, counters);
+    });
+}
+int clsimhip_mcpe_convert_device(clsimhip_mcpe_generator *g, int device, const void *d_photons, const void *d_hit_count, size_t capacity,
+                                 void *d_mcpes, size_t mcpe_capacity, void *d_counters, void *hip_stream)
+{
+    return guarded(nullptr, [&] {
+        need(g, "generator");
+        g->impl->convert_device(device, d_photons, d_hit_count, capacity, d_mcpes, mcpe_capacity, d_counters, static_cast<hipStream_t>(hip_stream));
+    });
+}
+int clsimhip_set_mcpe_generator(clsimhip_converter *c, clsimhip_mcpe_generator *g, int keep_photons)
+{
+    return guarded(c, [&] { need(c, "converter"); c->impl.set_mcpe_generator(g ? g->impl : std::shared_ptr<McpeGenerator>(), keep_photons != 0); });
+}
+int clsimhip_get_result_mcpes(clsimhip_converter *c, const clsimhip_photon *photons, const clsimhip_mcpe **mcpes, size_t *n)
+{
+    return guarded(c, [&] { need(c, "converter"); c->impl.result_mcpes(photons, mcpes, n); });
 }
 
 } // extern "C"

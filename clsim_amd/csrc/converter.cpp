@@ -4,6 +4,7 @@
 // reference's queueToOpenCL_/queueFromOpenCL_.  With double buffering one bunch
 // is on the GPU while the previous one is downloaded and converted.
 #include "converter.h"
+#include "mcpe.h"
 
 #include <chrono>
 #include <cmath>
@@ -164,6 +165,8 @@ void Converter::release_device()
         if (sl.h_steps) (void)hipHostFree(sl.h_steps);
         if (sl.step_buffer.p) (void)hipHostFree(sl.step_buffer.p);
         if (sl.h_hit_count) (void)hipHostFree(sl.h_hit_count);
+        (void)hipFree(sl.d_mcpes); (void)hipFree(sl.d_mcpe_counters);
+        if (sl.h_mcpe_counters) (void)hipHostFree(sl.h_mcpe_counters);
         sl = Slot();
     }
     for (const StepBuffer &b : free_step_buffers_) (void)hipHostFree(b.p);
@@ -171,6 +174,8 @@ void Converter::release_device()
     (void)hipFree(d_tables_); (void)hipFree(d_dom_tx_); (void)hipFree(d_dom_ty_); (void)hipFree(d_dom_tz_); (void)hipFree(d_len_table_); (void)hipFree(d_prox_map_); (void)hipFree(d_dom_prox_); (void)hipFree(d_dom_centres_); (void)hipFree(d_dom_named_); (void)hipFree(d_id_strings_); (void)hipFree(d_id_doms_); (void)hipFree(d_id_dom_start_);
     for (const PinnedBuffer &b : free_result_buffers_) (void)hipHostFree(b.p);
     free_result_buffers_.clear(); result_buffers_made_ = 0; pinning_refused_ = false;
+    for (const McpeBuffer &b : free_mcpe_buffers_) (void)hipHostFree(b.p);
+    free_mcpe_buffers_.clear(); mcpe_buffers_made_ = 0; mcpe_pinning_refused_ = false;
     // results nobody released, and results nobody fetched: their page-locked buffers go with the converter
     handed_out_.clear();
     if (out_queue_) {
@@ -243,6 +248,14 @@ void Converter::set_wlen_bias(FunctionData b)
 void Converter::set_medium(MediumData m) { guard(); m.validate(); compiled_ = false; medium_ = std::move(m); have_medium_ = true; }
 void Converter::set_geometry(GeometryInput g) { guard(); compiled_ = false; geometry_ = std::move(g); have_geometry_ = true; }
 
+void Converter::set_mcpe_generator(std::shared_ptr<McpeGenerator> g, bool keep_photons)
+{
+    guard();
+    compiled_ = false;
+    mcpe_ = std::move(g);
+    keep_photons_ = keep_photons;
+}
+
 void Converter::set_workgroup_size(size_t v)
 {
     guard();
@@ -282,6 +295,22 @@ void Converter::compile()
     if (const char *e = std::getenv("CLSIMHIP_DOM_PROX_N")) set_tuning("dom_map_cells", std::max(4, std::min(512, std::atoi(e))));
     if (const char *e = std::getenv("CLSIMHIP_NO_NAMED_SEARCH")) set_tuning("named_search", e[0] == '1' ? 0 : 1);
 #endif
+    if (mcpe_) {
+        // the generator reads IDs from the records: every DOM's pair must fit them (the host conversion reports such IDs only when a
+        // photon carries them, OpenCL.cxx:1577-1586) and must have a class (log_fatal per photon in the reference, :628-630)
+        for (size_t i = 0; i < geometry_.string_ids.size(); ++i) {
+            const int32_t sid = geometry_.string_ids[i];
+            const uint32_t did = geometry_.dom_ids[i];
+            if (sid < -32768 || sid > 32767 || did > 65535u)
+                throw Error(CLSIMHIP_ERR_CONFIG, "MCPE generator: string ID " + std::to_string(sid) + " / OM ID " + std::to_string(did) + " does not fit the photon record");
+            if (!mcpe_->has_class(sid, did))
+                throw Error(CLSIMHIP_ERR_CONFIG, "No wavelength acceptance configured for OMKey(" + std::to_string(sid) + "," + std::to_string(did) + ")");
+        }
+        if (history_entries_ && !keep_photons_) throw Error(CLSIMHIP_ERR_CONFIG, "photon histories need keep_photons");
+        // records of a converter with another pancake factor sit at another radius: every one of them would be OFF_SURFACE
+        if (mcpe_->pancake() != pancake_)
+            throw Error(CLSIMHIP_ERR_CONFIG, "MCPE generator: made for DOM pancake factor " + std::to_string(mcpe_->pancake()) + ", the converter's is " + std::to_string(pancake_));
+    }
     tables_ = compile_tables(medium_, geometry_, generators_, bias_, pancake_, table_tuning_);
     if (!std::isnan(fixed_abs_lengths_)) {                      // OpenCL.cxx:425-431
         tables_.params.has_fixed_abs = 1;
@@ -457,6 +486,12 @@ void Converter::setup_device_buffers()
             const size_t bytes = static_cast<size_t>(max_output_photons_) * history_entries_ * 16;
             hip_check(hipMalloc(reinterpret_cast<void **>(&sl.d_hist_out), bytes), "photon histories");
             hip_check(hipHostMalloc(reinterpret_cast<void **>(&sl.h_hist), bytes, hipHostMallocDefault), "pinned photon histories");
+        }
+        if (mcpe_) {
+            if (!d_id_strings_) throw Error(CLSIMHIP_ERR_CONFIG, "MCPE generator: the geometry has no DOM");
+            hip_check(hipMalloc(reinterpret_cast<void **>(&sl.d_mcpes), static_cast<size_t>(max_output_photons_) * sizeof(clsimhip_mcpe)), "MCPEs");
+            hip_check(hipMalloc(reinterpret_cast<void **>(&sl.d_mcpe_counters), 32), "MCPE counters");
+            hip_check(hipHostMalloc(reinterpret_cast<void **>(&sl.h_mcpe_counters), 32, hipHostMallocDefault), "pinned MCPE counters");
         }
         hip_check(hipEventCreate(&sl.start), "hipEventCreate");
         hip_check(hipEventCreate(&sl.stop), "hipEventCreate");
@@ -651,6 +686,12 @@ void Converter::submit(Slot &s, Job &job)
     hip_check(hipEventRecord(s.stop, stream_), "event");
     hip_check(hipMemcpyAsync(s.h_hit_count, s.d_hit_count, 4, hipMemcpyDeviceToHost, stream_), "download hit counter");
     hip_check(hipMemcpyAsync(s.h_hit_count + 1, P.queue + 2, 12, hipMemcpyDeviceToHost, stream_), "download skipped-step and bad-record counters");
+    if (mcpe_) {
+        // behind assemble_hits_kernel on the bunch's stream, over the records the bunch stored (min(hit counter, capacity)); outside
+        // the start / stop pair: the propagation kernel's time stays what it was
+        mcpe_->convert_device(device_, s.d_photons, s.d_hit_count, max_output_photons_, s.d_mcpes, max_output_photons_, s.d_mcpe_counters, stream_);
+        hip_check(hipMemcpyAsync(s.h_mcpe_counters, s.d_mcpe_counters, 20, hipMemcpyDeviceToHost, stream_), "download MCPE counters");
+    }
     hip_check(hipEventRecord(s.counted, stream_), "event");
 }
 
@@ -674,6 +715,17 @@ void Converter::finish(Slot &s, std::chrono::steady_clock::time_point &last_done
     // thread: round 2 zero-filled a vector per result, copied the download into it and converted indices one by one -- 0.4 s
     // per bunch of 8.4 M photons in the reference's benchmark, the device idle 80 % of the time).  With every pool buffer in
     // the caller's hands the records go into a plain vector.
+    uint32_t n_mcpes = 0;
+    if (mcpe_) {
+        const uint32_t *mc = s.h_mcpe_counters;
+        if ((mc[1] | mc[2] | mc[3] | mc[4]) != 0u)      // log_fatal in the reference, all four (I3PhotonToMCPEConverter.cxx:606, 612, 630, 660)
+            throw Error(CLSIMHIP_ERR_DEVICE, "MCPE generator, bunch " + std::to_string(s.id) + ": " + std::to_string(mc[1]) + " photons with negative weight, " +
+                                                 std::to_string(mc[2]) + " not on the DOM surface, " + std::to_string(mc[3]) + " at a DOM without wavelength acceptance, " +
+                                                 std::to_string(mc[4]) + " with hit probability above 1");
+        n_mcpes = std::min(mc[0], max_output_photons_);
+    }
+    const uint32_t detected = hits;
+    if (mcpe_ && !keep_photons_) hits = 0;              // the records stay on the device
     Result r;
     r.count = hits;
     std::unique_ptr<std::vector<clsimhip_photon>> photons;
@@ -708,6 +760,26 @@ void Converter::finish(Slot &s, std::chrono::steady_clock::time_point &last_done
         }
         if (!d_id_strings_) replace_indices(where, hits);      // OpenCL.cxx:1604-1619 does this on the caller thread
     }
+    if (mcpe_) {
+        r.mcpe_count = n_mcpes;
+        if (n_mcpes) {
+            const McpeBuffer buf = take_mcpe_buffer(n_mcpes);
+            clsimhip_mcpe *to = buf.p;
+            if (buf.p) { r.mcpe_pinned.reset(buf.p); r.mcpe_pinned_capacity = buf.capacity; }
+            else { r.mcpes.reset(new std::vector<clsimhip_mcpe>(n_mcpes)); to = r.mcpes->data(); }
+            try {
+                hip_check(hipMemcpyAsync(to, s.d_mcpes, static_cast<size_t>(n_mcpes) * sizeof(clsimhip_mcpe), hipMemcpyDeviceToHost, copy_stream_), "download MCPEs");
+                hip_check(hipStreamSynchronize(copy_stream_), "download MCPEs");
+            } catch (...) {
+                // both pool buffers go back to their pools, as above
+                std::lock_guard<std::mutex> lk(result_pool_mutex_);
+                if (r.pinned) free_result_buffers_.push_back(PinnedBuffer{r.pinned.release(), r.pinned_capacity});
+                if (r.mcpe_pinned) free_mcpe_buffers_.push_back(McpeBuffer{r.mcpe_pinned.release(), r.mcpe_pinned_capacity});
+                throw;
+            }
+        }
+        if (!hits) r.handle.reset(new clsimhip_photon());
+    }
     std::unique_ptr<std::vector<float>> histories;
     if (hits && history_entries_) {
         // ConvertPhotonHistories (OpenCL.cxx:940-989): unroll each ring into forward order
@@ -736,7 +808,7 @@ void Converter::finish(Slot &s, std::chrono::steady_clock::time_point &last_done
         else total_host_ns_ += static_cast<uint64_t>(static_cast<double>(ms) * 1e6);
         ++num_kernel_calls_;
         photons_generated_ += s.generated;
-        photons_at_doms_ += hits;
+        photons_at_doms_ += detected;
     }
     first = false;
     last_done = now;
@@ -812,7 +884,7 @@ void Converter::get_result(uint32_t *identifier, const clsimhip_photon **photons
     *identifier = r.id;
     *n = r.count;
     static const clsimhip_photon empty_sentinel{};
-    const clsimhip_photon *key = r.count ? r.data() : nullptr;
+    const clsimhip_photon *key = r.count ? r.data() : r.handle.get();
     *photons = key ? key : &empty_sentinel;
     if (key) {
         std::lock_guard<std::mutex> lk(results_mutex_);
@@ -835,64 +907,90 @@ void Converter::result_histories(const clsimhip_photon *photons, const float **h
     if (it->second.histories) *histories = it->second.histories->data();
 }
 
+void Converter::result_mcpes(const clsimhip_photon *photons, const clsimhip_mcpe **mcpes, size_t *n)
+{
+    need_init();
+    if (!mcpes || !n) throw Error(CLSIMHIP_ERR_ARGUMENT, "output pointers are (null)");
+    *mcpes = nullptr;
+    *n = 0;
+    if (!mcpe_) return;
+    std::lock_guard<std::mutex> lk(results_mutex_);
+    auto it = handed_out_.find(photons);
+    if (it == handed_out_.end()) throw Error(CLSIMHIP_ERR_ARGUMENT, "not a result handed out by GetConversionResult (or already released)");
+    *n = it->second.mcpe_count;
+    if (it->second.mcpe_count) *mcpes = it->second.mcpe_data();
+}
+
 void Converter::release_result(const clsimhip_photon *photons)
 {
     PinnedBuffer back;
+    McpeBuffer mcpe_back;
     {
         std::lock_guard<std::mutex> lk(results_mutex_);
         auto it = handed_out_.find(photons);
         if (it == handed_out_.end()) return;
         back.capacity = it->second.pinned_capacity;
         back.p = it->second.pinned.release();
+        mcpe_back.capacity = it->second.mcpe_pinned_capacity;
+        mcpe_back.p = it->second.mcpe_pinned.release();
         handed_out_.erase(it);
     }
-    if (back.p) {
+    if (back.p || mcpe_back.p) {
         std::lock_guard<std::mutex> lk(result_pool_mutex_);
-        free_result_buffers_.push_back(back);
+        if (back.p) free_result_buffers_.push_back(back);
+        if (mcpe_back.p) free_mcpe_buffers_.push_back(mcpe_back);
     }
 }
 
 void Converter::Result::HostFree::operator()(clsimhip_photon *p) const { if (p) (void)hipHostFree(p); }
+void Converter::Result::McpeHostFree::operator()(clsimhip_mcpe *p) const { if (p) (void)hipHostFree(p); }
 
-Converter::PinnedBuffer Converter::take_result_buffer(size_t records)
+// A page-locked buffer for `records` records of a result pool (photons: free_result_buffers_, MCPEs: free_mcpe_buffers_): the
+// smallest free buffer that holds them; else a new one (a quarter more, at least min_result_records_, never more than
+// max_output_photons_), for which -- kResultBuffers made -- the smallest free one makes room; {nullptr, 0} when every buffer is
+// with the caller or the host refuses to page-lock more.
+template <class Buffer>
+Buffer Converter::take_pinned_buffer(std::vector<Buffer> &free_buffers, int &made, bool &refused, size_t records)
 {
-    clsimhip_photon *too_small = nullptr;
+    decltype(Buffer().p) too_small = nullptr;
     {
         std::lock_guard<std::mutex> lk(result_pool_mutex_);
-        // the smallest free buffer that holds the records
-        size_t best = free_result_buffers_.size(), smallest = free_result_buffers_.size();
-        for (size_t i = 0; i < free_result_buffers_.size(); ++i) {
-            const size_t c = free_result_buffers_[i].capacity;
-            if (c >= records && (best == free_result_buffers_.size() || c < free_result_buffers_[best].capacity)) best = i;
-            if (smallest == free_result_buffers_.size() || c < free_result_buffers_[smallest].capacity) smallest = i;
+        size_t best = free_buffers.size(), smallest = free_buffers.size();
+        for (size_t i = 0; i < free_buffers.size(); ++i) {
+            const size_t c = free_buffers[i].capacity;
+            if (c >= records && (best == free_buffers.size() || c < free_buffers[best].capacity)) best = i;
+            if (smallest == free_buffers.size() || c < free_buffers[smallest].capacity) smallest = i;
         }
-        if (best != free_result_buffers_.size()) {
-            const PinnedBuffer b = free_result_buffers_[best];
-            free_result_buffers_.erase(free_result_buffers_.begin() + static_cast<std::ptrdiff_t>(best));
+        if (best != free_buffers.size()) {
+            const Buffer b = free_buffers[best];
+            free_buffers.erase(free_buffers.begin() + static_cast<std::ptrdiff_t>(best));
             return b;
         }
-        if (pinning_refused_) return PinnedBuffer();
-        if (result_buffers_made_ >= kResultBuffers) {
-            if (free_result_buffers_.empty()) return PinnedBuffer();            // all of them are with the caller
-            too_small = free_result_buffers_[smallest].p;                       // a free one makes room for a larger one
-            free_result_buffers_.erase(free_result_buffers_.begin() + static_cast<std::ptrdiff_t>(smallest));
-            --result_buffers_made_;
+        if (refused) return Buffer();
+        if (made >= kResultBuffers) {
+            if (free_buffers.empty()) return Buffer();                          // all of them are with the caller
+            too_small = free_buffers[smallest].p;                               // a free one makes room for a larger one
+            free_buffers.erase(free_buffers.begin() + static_cast<std::ptrdiff_t>(smallest));
+            --made;
         }
-        ++result_buffers_made_;
+        ++made;
     }
     if (too_small) (void)hipHostFree(too_small);
-    PinnedBuffer b;
+    Buffer b;
     b.capacity = std::max(min_result_records_, (records + records / 4 + 4095) / 4096 * 4096);
     b.capacity = std::max(records, std::min(b.capacity, static_cast<size_t>(max_output_photons_)));
-    if (hipHostMalloc(reinterpret_cast<void **>(&b.p), b.capacity * sizeof(clsimhip_photon), hipHostMallocDefault) != hipSuccess) {
+    if (hipHostMalloc(reinterpret_cast<void **>(&b.p), b.capacity * sizeof(*b.p), hipHostMallocDefault) != hipSuccess) {
         (void)hipGetLastError();
         std::lock_guard<std::mutex> lk(result_pool_mutex_);
-        --result_buffers_made_;
-        pinning_refused_ = true;
-        return PinnedBuffer();
+        --made;
+        refused = true;
+        return Buffer();
     }
     return b;
 }
+
+Converter::McpeBuffer Converter::take_mcpe_buffer(size_t records) { return take_pinned_buffer(free_mcpe_buffers_, mcpe_buffers_made_, mcpe_pinning_refused_, records); }
+Converter::PinnedBuffer Converter::take_result_buffer(size_t records) { return take_pinned_buffer(free_result_buffers_, result_buffers_made_, pinning_refused_, records); }
 
 size_t Converter::queue_size() const { need_init(); return in_queue_->size(); }
 bool Converter::more_photons_available() const { need_init(); return !out_queue_->empty(); }

@@ -41,6 +41,8 @@ hipError_t launch_keep_kernel(const KParams &P, const KVariant &v, hipStream_t s
 size_t prop_kernel_max_lanes();
 size_t prop_kernel_lds_budget();
 
+class McpeGenerator;            // mcpe.h
+
 // RCCL gather of detected photons (comm.cpp)
 struct Comm;
 void comm_unique_id(uint8_t id[CLSIMHIP_UNIQUE_ID_BYTES]);
@@ -166,6 +168,8 @@ public:
     void set_history_entries(uint32_t v) { guard(); history_entries_ = v; }
     void set_workgroup_size(size_t v);
     void set_max_num_workitems(size_t v);
+    // clsimhip_set_mcpe_generator: the hit maker runs behind every bunch's propagation (null: off)
+    void set_mcpe_generator(std::shared_ptr<McpeGenerator> g, bool keep_photons);
 
     void compile();
     void initialize(uint64_t seed);
@@ -178,6 +182,7 @@ public:
     void enqueue_steps(const clsimhip_step *steps, size_t n, uint32_t identifier);
     void get_result(uint32_t *identifier, const clsimhip_photon **photons, size_t *n);
     void result_histories(const clsimhip_photon *photons, const float **histories, uint32_t *entries);
+    void result_mcpes(const clsimhip_photon *photons, const clsimhip_mcpe **mcpes, size_t *n);
     void release_result(const clsimhip_photon *photons);
     size_t queue_size() const;
     bool more_photons_available() const;
@@ -245,6 +250,15 @@ private:
         std::unique_ptr<std::vector<clsimhip_photon>> photons;
         std::unique_ptr<std::vector<float>> histories;     // [photons][history_entries_][4], forward order
         const clsimhip_photon *data() const { return pinned ? pinned.get() : (photons ? photons->data() : nullptr); }
+        // with an MCPE generator: the bunch's MCPEs, in a page-locked buffer of the MCPE pool or (pool exhausted) a vector, and --
+        // when the result carries no photon record -- a record of its own whose address is the result's handle
+        struct McpeHostFree { void operator()(clsimhip_mcpe *p) const; };
+        std::unique_ptr<clsimhip_mcpe, McpeHostFree> mcpe_pinned;
+        size_t mcpe_pinned_capacity = 0;
+        size_t mcpe_count = 0;
+        std::unique_ptr<std::vector<clsimhip_mcpe>> mcpes;
+        std::unique_ptr<clsimhip_photon> handle;
+        const clsimhip_mcpe *mcpe_data() const { return mcpe_pinned ? mcpe_pinned.get() : (mcpes ? mcpes->data() : nullptr); }
     };
 
     void guard() const { if (initialized_) throw Error(CLSIMHIP_ERR_STATE, "I3CLSimStepToPhotonConverterHIP already initialized!"); }
@@ -268,6 +282,9 @@ private:
     uint32_t history_entries_ = 0;
     size_t workgroup_size_ = 0, max_workitems_ = 0;
     uint32_t max_output_photons_ = 0;
+
+    std::shared_ptr<McpeGenerator> mcpe_;       // null: no MCPEs are made (the default)
+    bool keep_photons_ = true;
 
     bool compiled_ = false, initialized_ = false;
     CompiledTables tables_;
@@ -295,6 +312,8 @@ private:
         clsimhip_step *h_steps = nullptr;       // pinned staging (for a job that came without a pool buffer)
         StepBuffer step_buffer;                 // the pool buffer the slot's upload reads; goes back to the pool when the slot is used again
         uint32_t *h_hit_count = nullptr;
+        clsimhip_mcpe *d_mcpes = nullptr;       // with an MCPE generator: max_output_photons_ records, five counters (mcpe.h)
+        uint32_t *d_mcpe_counters = nullptr, *h_mcpe_counters = nullptr;
         hipEvent_t start = nullptr, stop = nullptr, counted = nullptr, uploaded = nullptr;
         uint32_t id = 0;
         uint64_t generated = 0;
@@ -313,6 +332,13 @@ private:
     bool pinning_refused_ = false;                      // the host would not page-lock more: results are copied out from then on
     std::mutex result_pool_mutex_;
     PinnedBuffer take_result_buffer(size_t records);    // {nullptr, 0} when every buffer is with the caller (or the host refuses)
+    // the same for MCPEs (16-byte records), at most kResultBuffers as well
+    struct McpeBuffer { clsimhip_mcpe *p = nullptr; size_t capacity = 0; };
+    std::vector<McpeBuffer> free_mcpe_buffers_;
+    int mcpe_buffers_made_ = 0;
+    bool mcpe_pinning_refused_ = false;
+    McpeBuffer take_mcpe_buffer(size_t records);
+    template <class Buffer> Buffer take_pinned_buffer(std::vector<Buffer> &free_buffers, int &made, bool &refused, size_t records);    // the one routine behind both
     // Page-locked step buffers (see Job): input queue depth + one per slot + the one being filled, each sized by the bunch it first
     // carried (a quarter more) and replaced by a larger one when a later bunch needs it, at most kStepPoolBytes in all
     static constexpr int kStepBuffers = 8;

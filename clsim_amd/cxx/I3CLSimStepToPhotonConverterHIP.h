@@ -211,6 +211,14 @@ public:
         size_t n = 0;
         check(clsimhip_get_conversion_result(handle_, &r.identifier, &p, &n));
         r.photons = I3CLSimPhotonSeriesPtr(new I3CLSimPhotonSeries(n));
+        lastMCPEs_.clear();
+        if (mcpeGenerator_) {       // (ConversionResult_t has no place for them: GetLastMCPEs())
+            const clsimhip_mcpe *m = nullptr;
+            size_t nm = 0;
+            check(clsimhip_get_result_mcpes(handle_, p, &m, &nm));
+            lastMCPEs_.assign(m, m + nm);
+            if (!n) check(clsimhip_release_result(handle_, p));     // the handle of a result without photon records
+        }
         if (n) {
             std::memcpy(static_cast<void *>(r.photons->data()), p, n * sizeof(clsimhip_photon));
             // I3CLSimPhotonHistory (public/clsim/I3CLSimPhotonHistory.h): per photon the recorded scatter points
@@ -243,6 +251,8 @@ public:
         const I3CLSimPhoton *photons = nullptr;
         std::size_t size = 0;
         std::shared_ptr<const void> hold;
+        const clsimhip_mcpe *mcpes = nullptr;       // with an MCPE generator: the bunch's MCPEs, valid as long as `photons`
+        std::size_t numMCPEs = 0;
         const I3CLSimPhoton *begin() const { return photons; }
         const I3CLSimPhoton *end() const { return photons + size; }
     };
@@ -252,6 +262,7 @@ public:
         const clsimhip_photon *p = nullptr;
         check(clsimhip_get_conversion_result(handle_, &v.identifier, &p, &v.size));
         v.photons = reinterpret_cast<const I3CLSimPhoton *>(p);
+        if (mcpeGenerator_) check(clsimhip_get_result_mcpes(handle_, p, &v.mcpes, &v.numMCPEs));
         if (p) {
             std::shared_ptr<clsimhip_converter> keep = owner_;
             v.hold = std::shared_ptr<const void>(static_cast<const void *>(p), [keep](const void *q) { (void)clsimhip_release_result(keep.get(), static_cast<const clsimhip_photon *>(q)); });
@@ -311,6 +322,17 @@ public:
     std::size_t GetMaxWorkgroupSize() const { size_t v = 0; check(clsimhip_get_max_workgroup_size(handle_, &v)); return v; }
     clsimhip_converter *Handle() { return handle_; }
 
+    // ---- MCPE generator (no reference counterpart: the reference makes MCPEs from the returned photons on a host thread,
+    // I3CLSimClientModule.cxx:359-439; include/clsimhip.h, "MCPE generator").  Before Initialize(); nullptr switches it off.  With
+    // keepPhotons = false results carry no photon records.  The generator object stays the caller's (the converter shares it). ----
+    void SetMCPEGenerator(clsimhip_mcpe_generator *generator, bool keepPhotons = true)
+    {
+        check(clsimhip_set_mcpe_generator(handle_, generator, keepPhotons ? 1 : 0));
+        mcpeGenerator_ = generator != nullptr;
+    }
+    // the MCPEs of the bunch the last GetConversionResult() returned (its identifier: that result's), in no particular order
+    const std::vector<clsimhip_mcpe> &GetLastMCPEs() const { return lastMCPEs_; }
+
 private:
     void check(int rc) const
     {
@@ -326,6 +348,8 @@ private:
     clsimhip_converter *handle_;
     std::shared_ptr<clsimhip_converter> owner_;      // owns handle_ (deleter: clsimhip_destroy); shared with the in-place result views
     uint64_t seed_;
+    bool mcpeGenerator_ = false;
+    std::vector<clsimhip_mcpe> lastMCPEs_;
 #ifdef CLSIMHIP_WITH_ICETRAY
     I3RandomServicePtr randomService_;
 #endif

@@ -655,7 +655,11 @@ typedef struct {
 #define CLSIMHIP_AXES_CYLINDRICAL 1     /* CylindricalAxes: rho, azimuth [rad], z, delay time (cylindrical_coordinates.c.cl) */
 typedef struct {                        /* I3CLSimFunctionPolynomial (function/I3CLSimFunctionPolynomial.cxx:35-153) */
     int32_t n;
-    const double *coefficients;         /* c0 + x*(c1 + x*(...)) */
+    const double *coefficients;         /* c0 + c1 x + c2 x^2 + ...  Two users, two evaluation orders: the table maker's kernel
+                                           evaluates it in single precision in Horner form, c0 + x*(c1 + x*(...)), as the OpenCL
+                                           text the reference generates does (Polynomial.cxx:104-153); the MCPE generator below
+                                           follows the host GetValue (:85-101) in double precision: sum += c_i * multiplier,
+                                           multiplier *= x */
     double range_min, range_max;        /* -inf / +inf: unbounded */
     double underflow, overflow;
 } clsimhip_polynomial;
@@ -703,6 +707,66 @@ int clsimhip_tabulator_write_fits_file(clsimhip_tabulator *t, const char *path, 
                                        const int64_t *int_values, const double *double_values, size_t n_keys);
 int clsimhip_tabulator_get_rng_state(clsimhip_tabulator *t, uint64_t *x, size_t count);
 long clsimhip_tabulator_get_table(const clsimhip_tabulator *t, const char *name, double *out, size_t cap);
+
+/* ---- MCPE generator: detected photons -> photo-electrons (no device counterpart in the reference) --------------------
+ * The stage behind the propagator: I3CLSimPhotonToMCPEConverterForDOMs::Convert (private/clsim/dom/
+ * I3PhotonToMCPEConverter.cxx:602-669), which the reference's client module calls for every returned photon on a host thread
+ * (I3CLSimClientModule.cxx:359-439), with the arrival time correction of the older module in the same file (:512-518; zero when
+ * pancake = oversize).  A pure function of one delivered photon record (string and OM IDs in it, not indices), a fixed
+ * configuration and a 64-bit seed:
+ *     weight < 0 -> NEGATIVE_WEIGHT; weight == 0 -> no MCPE; the photon is not within 3 cm of the radius dom_radius * oversize /
+ *     pancake -> OFF_SURFACE; P = weight x wavelength acceptance of the DOM's class x angular acceptance(-direction z, clamped
+ *     to [-1, 1]); no class for the DOM -> UNKNOWN_DOM; P > 1 -> PROBABILITY_ABOVE_ONE; an MCPE when P > u,
+ *     u = (h >> 11) 2^-53, h = seed folded with splitmix64 over the record's ten 64-bit words;
+ *     time = photon time + (-position . direction) (1 - pancake / oversize) / group velocity.
+ * All of it is binary64 + - x / in one fixed order (the two sin / cos pairs of the direction: the library's deterministic single
+ * precision ones), so the HIP kernel and the host twin give the same bits.  The reference draws u from an I3RandomService in
+ * arrival order, which no two runs repeat; keying the draw on the record makes the result independent of the schedule and
+ * takes nothing from the propagator's RNG streams.  The four named conditions are log_fatal in the reference. */
+typedef struct {                        /* I3MCPE(particle, npe = 1, time); the particle's major / minor ID and time shift are */
+    uint32_t identifier;                /* the caller's, keyed by `identifier` (AddPhotonsToFrames, ClientModule.cxx:359-439)   */
+    int16_t string_id;
+    uint16_t om_id;
+    double time;
+} clsimhip_mcpe;                        /* 16 bytes */
+#define CLSIMHIP_MCPE_NEGATIVE_WEIGHT 0         /* index into the condition counters */
+#define CLSIMHIP_MCPE_OFF_SURFACE 1
+#define CLSIMHIP_MCPE_UNKNOWN_DOM 2
+#define CLSIMHIP_MCPE_PROBABILITY_ABOVE_ONE 3
+typedef struct clsimhip_mcpe_generator clsimhip_mcpe_generator;
+/* n_classes (1 ... 8) wavelength acceptances, kinds TABLE and CONSTANT (others: CLSIMHIP_ERR_CONFIG; at most 4096 table values
+ * together), the class of every DOM as parallel arrays (the reference's I3CLSimFunctionMap: IceCube / DeepCore,
+ * python/traysegments/common.py:185-210; at most 2^24 DOMs), the angular acceptance (at most 32 coefficients).  Host only: no
+ * GPU is touched. */
+int clsimhip_mcpe_generator_create(const clsimhip_function *classes, size_t n_classes, size_t n_doms, const int32_t *string_ids,
+                                   const uint32_t *om_ids, const int32_t *class_index, const clsimhip_polynomial *angular_acceptance,
+                                   double dom_radius, double oversize, double pancake, uint64_t seed, clsimhip_mcpe_generator **out);
+/* a converter the generator was given to keeps it alive until the converter is destroyed */
+void clsimhip_mcpe_generator_destroy(clsimhip_mcpe_generator *g);
+const char *clsimhip_mcpe_generator_last_error(const clsimhip_mcpe_generator *g);
+/* The host twin: the definition, for callers without a GPU and for the tests.  Keeps the input order.  *n_out = MCPEs made (may
+ * exceed `capacity`: only the first `capacity` are stored); counters[4] (may be NULL) receives the four condition counts. */
+int clsimhip_mcpe_convert_host(const clsimhip_mcpe_generator *g, const clsimhip_photon *photons, size_t n, clsimhip_mcpe *out,
+                               size_t capacity, size_t *n_out, uint64_t counters[4]);
+/* The kernel, on records that live in HBM (pairs with clsimhip_propagate_device + index -> ID conversion, or any buffer of records
+ * with IDs): min(*d_hit_count, capacity) records of d_photons (16-byte aligned).  d_counters: five uint32, zeroed by this call;
+ * [0] counts the MCPEs and keeps counting past mcpe_capacity (only the first mcpe_capacity are stored in d_mcpes, the photon
+ * counter's rule), [1..4] the four conditions.  Output order is unspecified.  Asynchronous on hip_stream (NULL = default stream). */
+int clsimhip_mcpe_convert_device(clsimhip_mcpe_generator *g, int device, const void *d_photons, const void *d_hit_count, size_t capacity,
+                                 void *d_mcpes, size_t mcpe_capacity, void *d_counters, void *hip_stream);
+/* Attach the generator to a converter: the kernel then runs on every bunch's stream behind the propagation kernels, over the
+ * records the bunch stored.  Before Initialize() only (CLSIMHIP_ERR_STATE after); g = NULL switches it off (the default).
+ * Compile() then refuses (CLSIMHIP_ERR_CONFIG) a geometry with a DOM that has no class or whose IDs do not fit the record, a
+ * generator made for another pancake factor than the converter's (its records would all be OFF_SURFACE), and photon histories
+ * together with keep_photons = 0 (a history belongs to a photon record).
+ * keep_photons != 0: results carry the photons as without a generator, plus MCPEs.
+ * keep_photons = 0: the photon records never cross to the host; a result's photon count is 0 and its `photons` pointer is a
+ * non-NULL handle for clsimhip_get_result_mcpes / clsimhip_release_result (the client module's two switches). */
+int clsimhip_set_mcpe_generator(clsimhip_converter *c, clsimhip_mcpe_generator *g, int keep_photons);
+/* MCPEs of the result `photons` belongs to; valid until clsimhip_release_result(c, photons).  *mcpes is NULL when there are none.
+ * A bunch that met one of the four conditions fails as a bunch with a corrupted record does (the worker stops,
+ * CLSIMHIP_ERR_DEVICE with the four counts in the text). */
+int clsimhip_get_result_mcpes(clsimhip_converter *c, const clsimhip_photon *photons, const clsimhip_mcpe **mcpes, size_t *n);
 
 #ifdef __cplusplus
 }
