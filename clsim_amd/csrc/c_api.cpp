@@ -28,21 +28,6 @@ namespace {
 // several threads per converter (I3CLSimServer.cxx:126-135, 324-331), so a per-object string would be a data race.
 thread_local std::string g_last_error;
 
-// device scratch memory of one call, freed on every path out of it
-struct DeviceBuffer {
-    void *p = nullptr;
-    DeviceBuffer() = default;
-    DeviceBuffer(const DeviceBuffer &) = delete;
-    DeviceBuffer &operator=(const DeviceBuffer &) = delete;
-    ~DeviceBuffer() { if (p) (void)hipFree(p); }
-    void alloc(size_t bytes, const char *what)
-    {
-        const hipError_t e = hipMalloc(&p, bytes ? bytes : 1);
-        if (e != hipSuccess) { p = nullptr; throw Error(CLSIMHIP_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); }
-    }
-    template <class T> T *as() const { return static_cast<T *>(p); }
-};
-
 template <class F>
 int guarded(clsimhip_converter *c, F &&f)
 {
@@ -607,22 +592,20 @@ int clsimhip_eval_math(int device_ordinal, int what, const float *x, const float
 {
     return guarded(nullptr, [&] {
         need(x, "x"); need(out, "out");
-        auto chk = [](hipError_t e, const char *w) { if (e != hipSuccess) throw Error(CLSIMHIP_ERR_DEVICE, std::string(w) + ": " + hipGetErrorString(e)); };
         int count = 0;
         if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) throw Error(CLSIMHIP_ERR_DEVICE, "no HIP device available");
         DeviceGuard on_device(device_ordinal);
-        DeviceBuffer bx, by, bout;
-        bx.alloc(n * 4 + 16, "hipMalloc"); bout.alloc(n * 4 + 16, "hipMalloc");
-        float *dx = bx.as<float>(), *dy = nullptr, *dout = bout.as<float>();
-        chk(hipMemcpy(dx, x, n * 4, hipMemcpyHostToDevice), "hipMemcpy");
+        DeviceBuffer<float> bx(n + 4, "hipMalloc"), by, bout(n + 4, "hipMalloc");
+        float *dx = bx.get(), *dy = nullptr, *dout = bout.get();
+        hip_check(hipMemcpy(dx, x, n * 4, hipMemcpyHostToDevice), "hipMemcpy");
         if (y) {
-            by.alloc(n * 4 + 16, "hipMalloc");
-            dy = by.as<float>();
-            chk(hipMemcpy(dy, y, n * 4, hipMemcpyHostToDevice), "hipMemcpy");
+            by.alloc(n + 4, "hipMalloc");
+            dy = by.get();
+            hip_check(hipMemcpy(dy, y, n * 4, hipMemcpyHostToDevice), "hipMemcpy");
         }
-        chk(launch_eval_math(what, dx, dy, static_cast<uint32_t>(n), dout, nullptr), "eval_math launch");
-        chk(hipDeviceSynchronize(), "eval_math");
-        chk(hipMemcpy(out, dout, n * 4, hipMemcpyDeviceToHost), "hipMemcpy");
+        hip_check(launch_eval_math(what, dx, dy, static_cast<uint32_t>(n), dout, nullptr), "eval_math launch");
+        hip_check(hipDeviceSynchronize(), "eval_math");
+        hip_check(hipMemcpy(out, dout, n * 4, hipMemcpyDeviceToHost), "hipMemcpy");
     });
 }
 int clsimhip_check_math_exhaustive(int device_ordinal, int what, int exp_lo, int exp_hi, uint32_t *result, size_t result_cap)
@@ -631,16 +614,14 @@ int clsimhip_check_math_exhaustive(int device_ordinal, int what, int exp_lo, int
         need(result, "result");
         if (!((what >= 11 && what <= 13) || (what >= 16 && what <= 19)) || exp_lo < -126 || exp_hi > 127 || exp_lo > exp_hi || result_cap < 1 || result_cap > 4096)
             throw Error(CLSIMHIP_ERR_CONFIG, "clsimhip_check_math_exhaustive: what in 11..13 or 16..19, -126 <= exp_lo <= exp_hi <= 127, 1 <= result_cap <= 4096");
-        auto chk = [](hipError_t e, const char *w) { if (e != hipSuccess) throw Error(CLSIMHIP_ERR_DEVICE, std::string(w) + ": " + hipGetErrorString(e)); };
         int count = 0;
         if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) throw Error(CLSIMHIP_ERR_DEVICE, "no HIP device available");
         DeviceGuard on_device(device_ordinal);
-        DeviceBuffer buf;
-        buf.alloc(result_cap * 4, "hipMalloc");
-        chk(hipMemset(buf.as<uint32_t>(), 0, result_cap * 4), "hipMemset");
-        chk(launch_check_math(what, exp_lo, exp_hi, buf.as<uint32_t>(), static_cast<uint32_t>(result_cap), nullptr), "check_math launch");
-        chk(hipDeviceSynchronize(), "check_math");
-        chk(hipMemcpy(result, buf.as<uint32_t>(), result_cap * 4, hipMemcpyDeviceToHost), "hipMemcpy");
+        DeviceBuffer<uint32_t> buf(result_cap, "hipMalloc");
+        hip_check(hipMemset(buf.get(), 0, result_cap * 4), "hipMemset");
+        hip_check(launch_check_math(what, exp_lo, exp_hi, buf.get(), static_cast<uint32_t>(result_cap), nullptr), "check_math launch");
+        hip_check(hipDeviceSynchronize(), "check_math");
+        hip_check(hipMemcpy(result, buf.get(), result_cap * 4, hipMemcpyDeviceToHost), "hipMemcpy");
     });
 }
 
@@ -684,22 +665,20 @@ int clsimhip_generate_steps_device(int device, const clsimhip_step_request *requ
         if (padded > capacity) throw Error(CLSIMHIP_ERR_ARGUMENT, "the requests produce more steps than the buffer holds");
         if (padded_out) *padded_out = static_cast<size_t>(padded);
         if (padded == 0) return;
-        auto chk = [](hipError_t e, const char *w) { if (e != hipSuccess) throw Error(CLSIMHIP_ERR_DEVICE, std::string(w) + ": " + hipGetErrorString(e)); };
         int count = 0;
         if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) throw Error(CLSIMHIP_ERR_DEVICE, "no HIP device available (the step producer has no CPU fallback)");
         DeviceGuard on_device(device);
         hipStream_t stream = static_cast<hipStream_t>(hip_stream);
         const size_t nreq = n ? n : 1;
-        DeviceBuffer b_req, b_first;
-        b_req.alloc(nreq * sizeof(clsimhip_step_request), "hipMalloc");
-        b_first.alloc((n + 1) * sizeof(uint64_t), "hipMalloc");
-        clsimhip_step_request *d_req = b_req.as<clsimhip_step_request>();
-        uint64_t *d_first = b_first.as<uint64_t>();
-        if (n) chk(hipMemcpyAsync(d_req, requests, n * sizeof(clsimhip_step_request), hipMemcpyHostToDevice, stream), "upload requests");
-        chk(hipMemcpyAsync(d_first, first.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream), "upload offsets");
-        chk(launch_generate_steps(d_req, d_first, static_cast<uint32_t>(n ? n : 1), real, padded, seed, d_steps, stream), "step generation kernel launch");
+        DeviceBuffer<clsimhip_step_request> b_req(nreq, "hipMalloc");
+        DeviceBuffer<uint64_t> b_first(n + 1, "hipMalloc");
+        clsimhip_step_request *d_req = b_req.get();
+        uint64_t *d_first = b_first.get();
+        if (n) hip_check(hipMemcpyAsync(d_req, requests, n * sizeof(clsimhip_step_request), hipMemcpyHostToDevice, stream), "upload requests");
+        hip_check(hipMemcpyAsync(d_first, first.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream), "upload offsets");
+        hip_check(launch_generate_steps(d_req, d_first, static_cast<uint32_t>(n ? n : 1), real, padded, seed, d_steps, stream), "step generation kernel launch");
         // the request copies were made from pageable memory (synchronous w.r.t. the host); free after the kernel
-        chk(hipStreamSynchronize(stream), "step generation kernel");
+        hip_check(hipStreamSynchronize(stream), "step generation kernel");
     });
 }
 int clsimhip_generate_steps(int device, const clsimhip_step_request *requests, size_t n, uint64_t seed, size_t granularity,
@@ -710,17 +689,15 @@ int clsimhip_generate_steps(int device, const clsimhip_step_request *requests, s
         std::vector<uint64_t> first; uint64_t real = 0, padded = 0;
         plan_steps(requests, n, granularity, first, real, padded);
         if (padded > capacity) throw Error(CLSIMHIP_ERR_ARGUMENT, "the requests produce more steps than the buffer holds");
-        auto chk = [](hipError_t e, const char *w) { if (e != hipSuccess) throw Error(CLSIMHIP_ERR_DEVICE, std::string(w) + ": " + hipGetErrorString(e)); };
         int count = 0;
         if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) throw Error(CLSIMHIP_ERR_DEVICE, "no HIP device available (the step producer has no CPU fallback)");
         DeviceGuard on_device(device);
-        DeviceBuffer b_steps;
-        b_steps.alloc(padded * sizeof(clsimhip_step), "hipMalloc");
-        void *d_steps = b_steps.p;
+        DeviceBuffer<clsimhip_step> b_steps(padded, "hipMalloc");
+        void *d_steps = b_steps.get();
         size_t got = 0;
         const int rc = clsimhip_generate_steps_device(device, requests, n, seed, granularity, d_steps, padded, nullptr, &got);
         if (rc != CLSIMHIP_OK) throw Error(rc, g_last_error);
-        chk(hipMemcpy(steps_out, d_steps, padded * sizeof(clsimhip_step), hipMemcpyDeviceToHost), "download steps");
+        hip_check(hipMemcpy(steps_out, d_steps, padded * sizeof(clsimhip_step), hipMemcpyDeviceToHost), "download steps");
         if (padded_out) *padded_out = static_cast<size_t>(padded);
     });
 }
@@ -768,22 +745,20 @@ int clsimhip_generate_flasher_steps_device(int device, const clsimhip_flasher_co
             std::copy(d.begin(), d.end(), profiles.begin() + w * 2 * kFlasherProfilePoints);
             std::copy(c.begin(), c.end(), profiles.begin() + (w * 2 + 1) * kFlasherProfilePoints);
         }
-        auto chk = [](hipError_t e, const char *w) { if (e != hipSuccess) throw Error(CLSIMHIP_ERR_DEVICE, std::string(w) + ": " + hipGetErrorString(e)); };
         int count = 0;
         if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) throw Error(CLSIMHIP_ERR_DEVICE, "no HIP device available (the step producer has no CPU fallback)");
         DeviceGuard on_device(device);
         hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-        DeviceBuffer b_req, b_plan, b_prof;
-        b_req.alloc(n * sizeof(clsimhip_flasher_request), "hipMalloc");
-        b_plan.alloc(n * sizeof(FlasherPlanEntry), "hipMalloc");
-        b_prof.alloc(profiles.size() * sizeof(float), "hipMalloc");
-        void *d_req = b_req.p, *d_plan = b_plan.p, *d_prof = b_prof.p;
-        chk(hipMemcpyAsync(d_req, requests, n * sizeof(clsimhip_flasher_request), hipMemcpyHostToDevice, stream), "upload pulses");
-        chk(hipMemcpyAsync(d_plan, plan.data(), n * sizeof(FlasherPlanEntry), hipMemcpyHostToDevice, stream), "upload plan");
-        chk(hipMemcpyAsync(d_prof, profiles.data(), profiles.size() * sizeof(float), hipMemcpyHostToDevice, stream), "upload time profiles");
-        chk(launch_generate_flasher_steps(*config, static_cast<const clsimhip_flasher_request *>(d_req), d_plan, static_cast<uint32_t>(n), total, seed,
+        DeviceBuffer<clsimhip_flasher_request> b_req(n, "hipMalloc");
+        DeviceBuffer<FlasherPlanEntry> b_plan(n, "hipMalloc");
+        DeviceBuffer<float> b_prof(profiles.size(), "hipMalloc");
+        void *d_req = b_req.get(), *d_plan = b_plan.get(), *d_prof = b_prof.get();
+        hip_check(hipMemcpyAsync(d_req, requests, n * sizeof(clsimhip_flasher_request), hipMemcpyHostToDevice, stream), "upload pulses");
+        hip_check(hipMemcpyAsync(d_plan, plan.data(), n * sizeof(FlasherPlanEntry), hipMemcpyHostToDevice, stream), "upload plan");
+        hip_check(hipMemcpyAsync(d_prof, profiles.data(), profiles.size() * sizeof(float), hipMemcpyHostToDevice, stream), "upload time profiles");
+        hip_check(launch_generate_flasher_steps(*config, static_cast<const clsimhip_flasher_request *>(d_req), d_plan, static_cast<uint32_t>(n), total, seed,
                                           static_cast<const float *>(d_prof), d_steps, stream), "flasher step kernel launch");
-        chk(hipStreamSynchronize(stream), "flasher step kernel");
+        hip_check(hipStreamSynchronize(stream), "flasher step kernel");
     });
 }
 int clsimhip_generate_flasher_steps(int device, const clsimhip_flasher_config *config, const clsimhip_flasher_request *requests,
@@ -795,16 +770,14 @@ int clsimhip_generate_flasher_steps(int device, const clsimhip_flasher_config *c
         int rc = clsimhip_count_flasher_steps(config, requests, n, &total, nullptr);
         if (rc != CLSIMHIP_OK) throw Error(rc, g_last_error);
         if (total > capacity) throw Error(CLSIMHIP_ERR_ARGUMENT, "the pulses produce more steps than the buffer holds");
-        auto chk = [](hipError_t e, const char *w) { if (e != hipSuccess) throw Error(CLSIMHIP_ERR_DEVICE, std::string(w) + ": " + hipGetErrorString(e)); };
         int count = 0;
         if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) throw Error(CLSIMHIP_ERR_DEVICE, "no HIP device available (the step producer has no CPU fallback)");
         DeviceGuard on_device(device);
-        DeviceBuffer b_steps;
-        b_steps.alloc(total * sizeof(clsimhip_step), "hipMalloc");
-        void *d_steps = b_steps.p;
+        DeviceBuffer<clsimhip_step> b_steps(total, "hipMalloc");
+        void *d_steps = b_steps.get();
         rc = clsimhip_generate_flasher_steps_device(device, config, requests, n, seed, d_steps, total, nullptr, nullptr);
         if (rc != CLSIMHIP_OK) throw Error(rc, g_last_error);
-        chk(hipMemcpy(steps_out, d_steps, total * sizeof(clsimhip_step), hipMemcpyDeviceToHost), "download steps");
+        hip_check(hipMemcpy(steps_out, d_steps, total * sizeof(clsimhip_step), hipMemcpyDeviceToHost), "download steps");
         if (count_out) *count_out = total;
     });
 }

@@ -79,10 +79,6 @@ void nccl_check(ncclResult_t e, const char *what)
 {
     if (e != ncclSuccess) throw Error(CLSIMHIP_ERR_DEVICE, std::string(what) + ": " + rccl().GetErrorString(e));
 }
-void hip_ok(hipError_t e, const char *what)
-{
-    if (e != hipSuccess) throw Error(CLSIMHIP_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
-}
 } // namespace
 
 struct Comm {
@@ -91,17 +87,17 @@ struct Comm {
     // what a rank announces: {hit counter, 0, room in its gather buffer (low, high word)}; the root's room decides, on
     // every rank alike, how much travels
     static constexpr size_t kWords = 4;
-    uint32_t *d_mine = nullptr;         // kWords, device
-    uint32_t *d_all = nullptr;          // world x kWords, device
-    uint32_t *h_mine = nullptr;         // kWords, pinned
-    uint32_t *h_all = nullptr;          // world x kWords, pinned
-    hipEvent_t counted = nullptr;
+    DeviceBuffer<uint32_t> d_mine;      // kWords
+    DeviceBuffer<uint32_t> d_all;       // world x kWords
+    PinnedBuffer<uint32_t> h_mine;      // kWords
+    PinnedBuffer<uint32_t> h_all;       // world x kWords
+    Event counted;
     // what the COMMUNICATOR says about itself (ncclCommCount / ncclCommUserRank after ncclCommInitRank), not what the
     // caller passed in: a multi-GPU record quotes these
     int rccl_ranks = 0, rccl_rank = -1;
     char pci_bus_id[32] = {0};
     // per-gather timing on the caller's stream (events resolved lazily, in comm_statistics)
-    struct Timed { hipEvent_t begin, end; };
+    struct Timed { Event begin, end; };
     std::vector<Timed> in_flight, spare;
     uint64_t gathers = 0, records_sent = 0, records_received = 0;
     double gather_ms = 0.0;
@@ -111,18 +107,18 @@ struct Comm {
     {
         for (Timed &t : in_flight) {
             float ms = 0.f;
-            if (hipEventSynchronize(t.end) == hipSuccess && hipEventElapsedTime(&ms, t.begin, t.end) == hipSuccess) gather_ms += ms;
-            spare.push_back(t);
+            if (hipEventSynchronize(t.end.get()) == hipSuccess && hipEventElapsedTime(&ms, t.begin.get(), t.end.get()) == hipSuccess) gather_ms += ms;
+            spare.push_back(std::move(t));
         }
         in_flight.clear();
     }
     Timed take_timer()
     {
         if (in_flight.size() >= 256) resolve_timers();
-        if (!spare.empty()) { Timed t = spare.back(); spare.pop_back(); return t; }
-        Timed t{nullptr, nullptr};
-        hip_ok(hipEventCreate(&t.begin), "hipEventCreate");
-        hip_ok(hipEventCreate(&t.end), "hipEventCreate");
+        if (!spare.empty()) { Timed t = std::move(spare.back()); spare.pop_back(); return t; }
+        Timed t;
+        t.begin.create("hipEventCreate");
+        t.end.create("hipEventCreate");
         return t;
     }
 };
@@ -159,11 +155,11 @@ Comm *comm_create(int device, int rank, int world, const uint8_t id[CLSIMHIP_UNI
     }
     if (hipDeviceGetPCIBusId(c->pci_bus_id, static_cast<int>(sizeof c->pci_bus_id), device) != hipSuccess) c->pci_bus_id[0] = 0;
     const size_t words = Comm::kWords * static_cast<size_t>(world);
-    hip_ok(hipMalloc(reinterpret_cast<void **>(&c->d_mine), sizeof(uint32_t) * Comm::kWords), "hipMalloc");
-    hip_ok(hipMalloc(reinterpret_cast<void **>(&c->d_all), sizeof(uint32_t) * words), "hipMalloc");
-    hip_ok(hipHostMalloc(reinterpret_cast<void **>(&c->h_mine), sizeof(uint32_t) * Comm::kWords, hipHostMallocDefault), "hipHostMalloc");
-    hip_ok(hipHostMalloc(reinterpret_cast<void **>(&c->h_all), sizeof(uint32_t) * words, hipHostMallocDefault), "hipHostMalloc");
-    hip_ok(hipEventCreateWithFlags(&c->counted, hipEventDisableTiming), "hipEventCreate");
+    c->d_mine.alloc(Comm::kWords, "hipMalloc");
+    c->d_all.alloc(words, "hipMalloc");
+    c->h_mine.alloc(Comm::kWords, "hipHostMalloc");
+    c->h_all.alloc(words, "hipHostMalloc");
+    c->counted.create_untimed("hipEventCreate");
     return c.release();
 }
 
@@ -196,19 +192,10 @@ void comm_statistics(Comm *c, uint64_t *gathers, double *gather_ms, uint64_t *re
 void comm_destroy(Comm *c)
 {
     if (!c) return;
-    int previous = -1;
-    if (hipGetDevice(&previous) != hipSuccess) previous = -1;
-    (void)hipSetDevice(c->device);
+    DeviceGuard on_device(c->device, std::nothrow);
     if (c->comm) (void)rccl().CommDestroy(c->comm);
-    (void)hipFree(c->d_mine);
-    (void)hipFree(c->d_all);
-    if (c->h_mine) (void)hipHostFree(c->h_mine);
-    if (c->h_all) (void)hipHostFree(c->h_all);
-    if (c->counted) (void)hipEventDestroy(c->counted);
     c->resolve_timers();
-    for (Comm::Timed &t : c->spare) { (void)hipEventDestroy(t.begin); (void)hipEventDestroy(t.end); }
-    if (previous >= 0) (void)hipSetDevice(previous);
-    delete c;
+    delete c;           // (its buffers and events, with its device current)
 }
 
 // Blocks the calling thread only until the hit counts are known (the kernel that produced them must have finished
@@ -232,31 +219,31 @@ void comm_gather_hits(Comm *c, const void *d_photons, const void *d_hit_count, s
     const Rccl &R = rccl();
     const size_t W = Comm::kWords;
     std::lock_guard<std::mutex> lock(c->mutex);
-    const Comm::Timed timer = c->take_timer();
-    hip_ok(hipEventRecord(timer.begin, stream), "event");
+    uint32_t *const d_mine = c->d_mine.get(), *const d_all = c->d_all.get(), *const h_mine = c->h_mine.get(), *const h_all = c->h_all.get();
     // (whatever happens below, the pair is closed and accounted for)
     struct CloseTimer {
         Comm *c; Comm::Timed t; hipStream_t s;
-        ~CloseTimer() { (void)hipEventRecord(t.end, s); c->in_flight.push_back(t); ++c->gathers; }
-    } close_timer{c, timer, stream};
-    c->h_mine[0] = 0;
-    c->h_mine[1] = static_cast<uint32_t>(std::min<size_t>(capacity, 0xffffffffu));
-    c->h_mine[2] = static_cast<uint32_t>(static_cast<uint64_t>(gathered_capacity) & 0xffffffffu);
-    c->h_mine[3] = static_cast<uint32_t>(static_cast<uint64_t>(gathered_capacity) >> 32);
-    hip_ok(hipMemcpyAsync(c->d_mine, c->h_mine, sizeof(uint32_t) * W, hipMemcpyHostToDevice, stream), "upload gather header");
-    hip_ok(hipMemcpyAsync(c->d_mine, d_hit_count, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream), "copy hit counter");
-    nccl_check(R.AllGather(c->d_mine, c->d_all, W, ncclUint32, c->comm, stream), "ncclAllGather (hit counts)");
-    hip_ok(hipMemcpyAsync(c->h_all, c->d_all, sizeof(uint32_t) * W * static_cast<size_t>(c->world), hipMemcpyDeviceToHost, stream), "download hit counts");
-    hip_ok(hipEventRecord(c->counted, stream), "event");
-    hip_ok(hipEventSynchronize(c->counted), "hit counts");
+        ~CloseTimer() { (void)hipEventRecord(t.end.get(), s); c->in_flight.push_back(std::move(t)); ++c->gathers; }
+    } close_timer{c, c->take_timer(), stream};
+    hip_check(hipEventRecord(close_timer.t.begin.get(), stream), "event");
+    h_mine[0] = 0;
+    h_mine[1] = static_cast<uint32_t>(std::min<size_t>(capacity, 0xffffffffu));
+    h_mine[2] = static_cast<uint32_t>(static_cast<uint64_t>(gathered_capacity) & 0xffffffffu);
+    h_mine[3] = static_cast<uint32_t>(static_cast<uint64_t>(gathered_capacity) >> 32);
+    hip_check(hipMemcpyAsync(d_mine, h_mine, sizeof(uint32_t) * W, hipMemcpyHostToDevice, stream), "upload gather header");
+    hip_check(hipMemcpyAsync(d_mine, d_hit_count, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream), "copy hit counter");
+    nccl_check(R.AllGather(d_mine, d_all, W, ncclUint32, c->comm, stream), "ncclAllGather (hit counts)");
+    hip_check(hipMemcpyAsync(h_all, d_all, sizeof(uint32_t) * W * static_cast<size_t>(c->world), hipMemcpyDeviceToHost, stream), "download hit counts");
+    hip_check(hipEventRecord(c->counted.get(), stream), "event");
+    hip_check(hipEventSynchronize(c->counted.get()), "hit counts");
     // The kernel's counter keeps counting past the capacity of the photon buffer (propagation_kernel.c.cl:329-334);
     // a rank sends what it stored, and no more than still fits on the root.
-    const uint64_t room = static_cast<uint64_t>(c->h_all[W * root + 2]) | (static_cast<uint64_t>(c->h_all[W * root + 3]) << 32);
+    const uint64_t room = static_cast<uint64_t>(h_all[W * root + 2]) | (static_cast<uint64_t>(h_all[W * root + 3]) << 32);
     std::vector<size_t> travels(static_cast<size_t>(c->world));
     uint64_t total = 0, accepted = 0;
     for (int r = 0; r < c->world; ++r) {
-        const uint64_t stored = std::min<uint64_t>(c->h_all[W * r], c->h_all[W * r + 1]);
-        if (counts_out) counts_out[r] = c->h_all[W * r];
+        const uint64_t stored = std::min<uint64_t>(h_all[W * r], h_all[W * r + 1]);
+        if (counts_out) counts_out[r] = h_all[W * r];
         travels[r] = static_cast<size_t>(std::min<uint64_t>(stored, room - accepted));
         accepted += travels[r];
         total += stored;
@@ -288,7 +275,7 @@ void comm_gather_hits(Comm *c, const void *d_photons, const void *d_hit_count, s
     if (c->rank == root && travels[root] != 0) {
         size_t offset = 0;
         for (int r = 0; r < root; ++r) offset += travels[r];
-        hip_ok(hipMemcpyAsync(static_cast<uint8_t *>(d_gathered) + offset * kRecord, d_photons, travels[root] * kRecord, hipMemcpyDeviceToDevice, stream),
+        hip_check(hipMemcpyAsync(static_cast<uint8_t *>(d_gathered) + offset * kRecord, d_photons, travels[root] * kRecord, hipMemcpyDeviceToDevice, stream),
                "copy the root's own photons");
     }
     if (total > room)

@@ -27,15 +27,12 @@ constexpr uint32_t kQueueSlots = 256;
 // 0.63M 2.00 / 2.23.  Round 2's threshold was 614 400.)
 constexpr size_t kPooledKernelMinSteps = 524288;
 
-hipError_t Converter::launch(const KParams &P, hipStream_t stream) const
+hipError_t Converter::launch(const KParams &P, const LaunchTuning &tuning, hipStream_t stream) const
 {
     KVariant v = tables_.variant;
-    const bool pooled = pooled_for(P.n_steps);
-    {
-        std::lock_guard<std::mutex> lk(tuning_mutex_);
-        v.grid = grid_;
-        v.generic_only = generic_only_;
-    }
+    const bool pooled = tuning.pooled_for(P.n_steps, concurrent_launches_);
+    v.grid = tuning.grid;
+    v.generic_only = tuning.generic_only;
     if (v.keep_detected) return pooled ? launch_pool_keep_kernel(P, v, stream) : launch_keep_kernel(P, v, stream);
     return pooled ? launch_pool_kernel(P, v, stream) : launch_prop_kernel(P, v, stream);
 }
@@ -43,85 +40,83 @@ hipError_t Converter::launch(const KParams &P, hipStream_t stream) const
 // ---- tuning (include/clsimhip.h: clsimhip_set_tuning) -----------------------------------------------------------------
 void Converter::apply_kernel_choice()
 {
-    use_pool_ = pool_possible_ && kernel_choice_ != 2;
-    pool_min_steps_ = (kernel_choice_ != 0) ? 0 : kPooledKernelMinSteps;
-    if (tuned_pool_min_steps_ >= 0) pool_min_steps_ = static_cast<size_t>(tuned_pool_min_steps_);
-    pool_max_steps_ = pool_kernel_max_steps();
-    if (tuned_pool_max_steps_ >= 0) pool_max_steps_ = std::min(pool_max_steps_, static_cast<size_t>(tuned_pool_max_steps_));
+    LaunchTuning &t = tuning_;
+    t.derived = true;
+    t.use_pool = pool_possible_ && t.kernel != 2;
+    t.pool_min_steps = (t.kernel != 0) ? 0 : kPooledKernelMinSteps;
+    if (t.tuned_pool_min_steps >= 0) t.pool_min_steps = static_cast<size_t>(t.tuned_pool_min_steps);
+    t.pool_max_steps = pool_kernel_max_steps();
+    if (t.tuned_pool_max_steps >= 0) t.pool_max_steps = std::min(t.pool_max_steps, static_cast<size_t>(t.tuned_pool_max_steps));
 }
 
 namespace {
-struct TuningKey { const char *name; long long lo, hi; };
+struct TuningKey {
+    const char *name;
+    long long lo, hi;
+    bool shapes_tables;             // one of the three keys of Compile()
+    long long (*get)(const LaunchTuning &, const TableTuning &);
+    void (*set)(LaunchTuning &, TableTuning &, long long);
+};
+#define LAUNCH_FIELD(f) false, [](const LaunchTuning &l, const TableTuning &) { return static_cast<long long>(l.f); }, \
+                        [](LaunchTuning &l, TableTuning &, long long v) { l.f = static_cast<decltype(l.f)>(v); }
+#define TABLE_FIELD(f) true, [](const LaunchTuning &, const TableTuning &t) { return static_cast<long long>(t.f); }, \
+                       [](LaunchTuning &, TableTuning &t, long long v) { t.f = static_cast<decltype(t.f)>(v); }
 // (the table of include/clsimhip.h, in its order)
 const TuningKey kTuningKeys[] = {
-    {"kernel", 0, 2}, {"pool_min_steps", -1, 1ll << 40}, {"pool_max_steps", -1, 1ll << 40}, {"pool_ring", 0, 4096},
-    {"k_new", 0, 4096}, {"k_search", 0, 64}, {"slices", 0, 65535}, {"k_pop", 0, 64}, {"k_wait", -1, 255}, {"k_aim", -1, 64},
-    {"grid", 0, 1 << 20}, {"generic_kernels", 0, 1}, {"result_min_records", 1, 1ll << 32},
-    {"string_map_cells", 8, 4096}, {"dom_map_cells", 4, 512}, {"named_search", 0, 1},
+    {"kernel", 0, 2, LAUNCH_FIELD(kernel)},
+    // (once initialized the two report what the launches use)
+    {"pool_min_steps", -1, 1ll << 40, false,
+     [](const LaunchTuning &l, const TableTuning &) { return l.derived ? static_cast<long long>(l.pool_min_steps) : l.tuned_pool_min_steps; },
+     [](LaunchTuning &l, TableTuning &, long long v) { l.tuned_pool_min_steps = v; }},
+    {"pool_max_steps", -1, 1ll << 40, false,
+     [](const LaunchTuning &l, const TableTuning &) { return l.derived ? static_cast<long long>(l.pool_max_steps) : l.tuned_pool_max_steps; },
+     [](LaunchTuning &l, TableTuning &, long long v) { l.tuned_pool_max_steps = v; }},
+    {"pool_ring", 0, 4096, LAUNCH_FIELD(pool_ring)},
+    {"k_new", 0, 4096, LAUNCH_FIELD(k_new)},
+    {"k_search", 0, 64, LAUNCH_FIELD(k_search)},
+    {"slices", 0, 65535, LAUNCH_FIELD(slices)},
+    {"k_pop", 0, 64, LAUNCH_FIELD(k_pop)},
+    {"k_wait", -1, 255, LAUNCH_FIELD(k_wait)},
+    {"k_aim", -1, 64, LAUNCH_FIELD(k_aim)},
+    {"grid", 0, 1 << 20, LAUNCH_FIELD(grid)},
+    {"generic_kernels", 0, 1, LAUNCH_FIELD(generic_only)},
+    {"result_min_records", 1, 1ll << 32, LAUNCH_FIELD(result_min_records)},
+    {"string_map_cells", 8, 4096, TABLE_FIELD(string_map_cells)},
+    {"dom_map_cells", 4, 512, TABLE_FIELD(dom_map_cells)},
+    {"named_search", 0, 1, TABLE_FIELD(named_search)},
 };
+#undef LAUNCH_FIELD
+#undef TABLE_FIELD
+
+const TuningKey &tuning_key(const std::string &key)
+{
+    for (const TuningKey &t : kTuningKeys) if (key == t.name) return t;
+    throw Error(CLSIMHIP_ERR_ARGUMENT, "no tuning key named " + key);
 }
+} // namespace
 
 void Converter::set_tuning(const std::string &key, long long value)
 {
-    const TuningKey *k = nullptr;
-    for (const TuningKey &t : kTuningKeys) if (key == t.name) k = &t;
-    if (!k) throw Error(CLSIMHIP_ERR_ARGUMENT, "no tuning key named " + key);
-    if (value < k->lo || value > k->hi)
-        throw Error(CLSIMHIP_ERR_ARGUMENT, "tuning " + key + ": " + std::to_string(value) + " is outside " + std::to_string(k->lo) + " ... " + std::to_string(k->hi));
-    const bool table_key = (key == "string_map_cells" || key == "dom_map_cells" || key == "named_search");
-    if (table_key && compiled_) throw Error(CLSIMHIP_ERR_STATE, "tuning " + key + " shapes a table of Compile(): set it before Compile()");
-    std::lock_guard<std::mutex> lk(tuning_mutex_);          // (a launch reads its parameters under the same lock)
-    const int v = static_cast<int>(value);
-    if (key == "kernel") kernel_choice_ = v;
-    else if (key == "pool_min_steps") tuned_pool_min_steps_ = value;
-    else if (key == "pool_max_steps") tuned_pool_max_steps_ = value;
-    else if (key == "pool_ring") pool_ready_ = v;
-    else if (key == "k_new") k_new_ = v;
-    else if (key == "k_search") k_search_ = v;
-    else if (key == "slices") k_slices_ = v;
-    else if (key == "k_pop") k_pop_ = v;
-    else if (key == "k_wait") k_wait_ = v;
-    else if (key == "k_aim") k_aim_ = v;
-    else if (key == "grid") grid_ = v;
-    else if (key == "generic_kernels") generic_only_ = (v != 0);
-    else if (key == "result_min_records") min_result_records_ = static_cast<size_t>(value);
-    else if (key == "string_map_cells") table_tuning_.string_map_cells = v;
-    else if (key == "dom_map_cells") table_tuning_.dom_map_cells = v;
-    else if (key == "named_search") table_tuning_.named_search = (v != 0);
+    const TuningKey &k = tuning_key(key);
+    if (value < k.lo || value > k.hi)
+        throw Error(CLSIMHIP_ERR_ARGUMENT, "tuning " + key + ": " + std::to_string(value) + " is outside " + std::to_string(k.lo) + " ... " + std::to_string(k.hi));
+    if (k.shapes_tables && compiled_) throw Error(CLSIMHIP_ERR_STATE, "tuning " + key + " shapes a table of Compile(): set it before Compile()");
+    std::lock_guard<std::mutex> lk(tuning_mutex_);          // (a launch copies its tuning under the same lock)
+    k.set(tuning_, table_tuning_, value);
     if (initialized_) apply_kernel_choice();
 }
 
 long long Converter::get_tuning(const std::string &key) const
 {
+    const TuningKey &k = tuning_key(key);
     std::lock_guard<std::mutex> lk(tuning_mutex_);
-    if (key == "kernel") return kernel_choice_;
-    if (key == "pool_min_steps") return initialized_ ? static_cast<long long>(pool_min_steps_) : tuned_pool_min_steps_;
-    if (key == "pool_max_steps") return initialized_ ? static_cast<long long>(pool_max_steps_) : tuned_pool_max_steps_;
-    if (key == "pool_ring") return pool_ready_;
-    if (key == "k_new") return k_new_;
-    if (key == "k_search") return k_search_;
-    if (key == "slices") return k_slices_;
-    if (key == "k_pop") return k_pop_;
-    if (key == "k_wait") return k_wait_;
-    if (key == "k_aim") return k_aim_;
-    if (key == "grid") return grid_;
-    if (key == "generic_kernels") return generic_only_ ? 1 : 0;
-    if (key == "result_min_records") return static_cast<long long>(min_result_records_);
-    if (key == "string_map_cells") return table_tuning_.string_map_cells;
-    if (key == "dom_map_cells") return table_tuning_.dom_map_cells;
-    if (key == "named_search") return table_tuning_.named_search ? 1 : 0;
-    throw Error(CLSIMHIP_ERR_ARGUMENT, "no tuning key named " + key);
+    return k.get(tuning_, table_tuning_);
 }
 
 void Converter::set_concurrent_device_launches(int k)
 {
     if (k < 1 || k > 16) throw Error(CLSIMHIP_ERR_ARGUMENT, "concurrent device launches: 1 ... 16");
     concurrent_launches_ = k;
-}
-
-void Converter::hip_check(hipError_t e, const char *what) const
-{
-    if (e != hipSuccess) throw Error(CLSIMHIP_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
 }
 
 Converter::Converter(int device) : device_(device)
@@ -141,56 +136,18 @@ Converter::~Converter()
 
 void Converter::release_device()
 {
-    if (!stream_ && !d_tables_ && !d_rng_x_ && !slots_[0].d_steps) return;     // nothing was created
-    int previous = -1;
-    if (hipGetDevice(&previous) != hipSuccess) previous = -1;
-    (void)hipSetDevice(device_);
-    for (auto &p : pending_events_) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
-    for (auto &p : free_events_) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
-    pending_events_.clear(); free_events_.clear();
-    if (ev_start_) (void)hipEventDestroy(ev_start_);
-    if (ev_stop_) (void)hipEventDestroy(ev_stop_);
-    if (stream_) (void)hipStreamDestroy(stream_);
-    if (copy_stream_) (void)hipStreamDestroy(copy_stream_);
-    if (upload_stream_) (void)hipStreamDestroy(upload_stream_);
-    ev_start_ = ev_stop_ = nullptr;
-    stream_ = copy_stream_ = upload_stream_ = nullptr;
-    for (Slot &sl : slots_) {
-        if (sl.start) (void)hipEventDestroy(sl.start);
-        if (sl.stop) (void)hipEventDestroy(sl.stop);
-        if (sl.counted) (void)hipEventDestroy(sl.counted);
-        if (sl.uploaded) (void)hipEventDestroy(sl.uploaded);
-        (void)hipFree(sl.d_steps); (void)hipFree(sl.d_photons); (void)hipFree(sl.d_hit_count); (void)hipFree(sl.d_hist_out);
-        if (sl.h_hist) (void)hipHostFree(sl.h_hist);
-        if (sl.h_steps) (void)hipHostFree(sl.h_steps);
-        if (sl.step_buffer.p) (void)hipHostFree(sl.step_buffer.p);
-        if (sl.h_hit_count) (void)hipHostFree(sl.h_hit_count);
-        (void)hipFree(sl.d_mcpes); (void)hipFree(sl.d_mcpe_counters);
-        if (sl.h_mcpe_counters) (void)hipHostFree(sl.h_mcpe_counters);
-        sl = Slot();
-    }
-    for (const StepBuffer &b : free_step_buffers_) (void)hipHostFree(b.p);
-    free_step_buffers_.clear(); step_buffers_made_ = 0; step_pool_bytes_ = 0; step_pinning_refused_ = false; step_fallback_logged_ = false;
-    (void)hipFree(d_tables_); (void)hipFree(d_dom_tx_); (void)hipFree(d_dom_ty_); (void)hipFree(d_dom_tz_); (void)hipFree(d_len_table_); (void)hipFree(d_prox_map_); (void)hipFree(d_dom_prox_); (void)hipFree(d_dom_centres_); (void)hipFree(d_dom_named_); (void)hipFree(d_id_strings_); (void)hipFree(d_id_doms_); (void)hipFree(d_id_dom_start_);
-    for (const PinnedBuffer &b : free_result_buffers_) (void)hipHostFree(b.p);
-    free_result_buffers_.clear(); result_buffers_made_ = 0; pinning_refused_ = false;
-    for (const McpeBuffer &b : free_mcpe_buffers_) (void)hipHostFree(b.p);
-    free_mcpe_buffers_.clear(); mcpe_buffers_made_ = 0; mcpe_pinning_refused_ = false;
-    // results nobody released, and results nobody fetched: their page-locked buffers go with the converter
+    if (!dev_.stream) return;       // nothing was created
+    DeviceGuard on_device(device_, std::nothrow);
+    // results nobody released, and results nobody fetched: their page-locked buffers go back to the pools first
     handed_out_.clear();
     if (out_queue_) {
         Result r;
         while (out_queue_->get_for(r, 0)) {}
     }
-    (void)hipFree(d_rng_x_); (void)hipFree(d_rng_a_);
-    (void)hipFree(d_queue_); (void)hipFree(d_work_); (void)hipFree(d_hist_ring_);
-    d_tables_ = nullptr; d_dom_tx_ = d_dom_ty_ = nullptr; d_dom_tz_ = nullptr; d_len_table_ = nullptr; d_prox_map_ = nullptr; d_dom_prox_ = nullptr; d_dom_centres_ = nullptr; d_dom_named_ = nullptr; d_id_strings_ = nullptr; d_id_doms_ = nullptr; d_id_dom_start_ = nullptr;
-    d_rng_x_ = nullptr; d_rng_a_ = nullptr; d_queue_ = nullptr; d_work_ = nullptr; d_hist_ring_ = nullptr;
-    last_queue_ = nullptr;
-#ifdef CLSIMHIP_CENSUS
-    (void)hipFree(d_census_); d_census_ = nullptr;
-#endif
-    if (previous >= 0) (void)hipSetDevice(previous);
+    dev_ = DeviceState();           // (the slots' step buffers go back to their pool)
+    step_pool_.reset();
+    result_pool_.reset();
+    mcpe_pool_.reset();
 }
 
 void Converter::set_device(int device)
@@ -290,10 +247,14 @@ void Converter::compile()
     if (save_all_) throw Error(CLSIMHIP_ERR_CONFIG, "SaveAllPhotons is not available in the HIP propagator");
     if (history_entries_ > 1024) throw Error(CLSIMHIP_ERR_CONFIG, "PhotonHistoryEntries > 1024 is not supported");
 #ifdef CLSIMHIP_DEVELOPER
-    // (developer build only: the round 1-5 environment names of the three table keys)
-    if (const char *e = std::getenv("CLSIMHIP_PROX_N")) set_tuning("string_map_cells", std::max(8, std::min(4096, std::atoi(e))));
-    if (const char *e = std::getenv("CLSIMHIP_DOM_PROX_N")) set_tuning("dom_map_cells", std::max(4, std::min(512, std::atoi(e))));
-    if (const char *e = std::getenv("CLSIMHIP_NO_NAMED_SEARCH")) set_tuning("named_search", e[0] == '1' ? 0 : 1);
+    // (developer build only: the round 1-5 environment names of the three table keys; written directly, because set_tuning() is the
+    // callers' door and refuses these keys once a Compile() has happened)
+    {
+        std::lock_guard<std::mutex> lk(tuning_mutex_);
+        if (const char *e = std::getenv("CLSIMHIP_PROX_N")) table_tuning_.string_map_cells = std::max(8, std::min(4096, std::atoi(e)));
+        if (const char *e = std::getenv("CLSIMHIP_DOM_PROX_N")) table_tuning_.dom_map_cells = std::max(4, std::min(512, std::atoi(e)));
+        if (const char *e = std::getenv("CLSIMHIP_NO_NAMED_SEARCH")) table_tuning_.named_search = (e[0] != '1');
+    }
 #endif
     if (mcpe_) {
         // the generator reads IDs from the records: every DOM's pair must fit them (the host conversion reports such IDs only when a
@@ -392,22 +353,17 @@ void Converter::initialize_with_streams(const uint64_t *x, const uint32_t *a, si
             throw Error(CLSIMHIP_ERR_DEVICE, "no HIP device available (the propagator has no CPU fallback)");
         if (device_ >= count) throw Error(CLSIMHIP_ERR_ARGUMENT, "device ordinal out of range");
     }
-    // everything below runs with this converter's device current; the caller's current device is restored on return,
-    // and a failure half-way releases what was created (a retry starts from nothing)
+    // everything below runs with this converter's device current; the caller's current device is restored on return.  A failure
+    // half-way frees what `created` holds and leaves dev_ empty: a retry starts from nothing.
     DeviceGuard on_device(device_);
-    try {
-        hip_check(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking), "hipStreamCreate");
-        hip_check(hipStreamCreateWithFlags(&copy_stream_, hipStreamNonBlocking), "hipStreamCreate");
-        hip_check(hipStreamCreateWithFlags(&upload_stream_, hipStreamNonBlocking), "hipStreamCreate");
-        hip_check(hipEventCreate(&ev_start_), "hipEventCreate");
-        hip_check(hipEventCreate(&ev_stop_), "hipEventCreate");
-        setup_device_buffers();
-        hip_check(hipMemcpy(d_rng_x_, x, count * sizeof(uint64_t), hipMemcpyHostToDevice), "upload rng x");
-        hip_check(hipMemcpy(d_rng_a_, a, count * sizeof(uint32_t), hipMemcpyHostToDevice), "upload rng a");
-    } catch (...) {
-        release_device();
-        throw;
-    }
+    DeviceState created;
+    created.stream.create("hipStreamCreate");
+    created.copy_stream.create("hipStreamCreate");
+    created.upload_stream.create("hipStreamCreate");
+    setup_device_buffers(created);
+    hip_check(hipMemcpy(created.rng_x.get(), x, count * sizeof(uint64_t), hipMemcpyHostToDevice), "upload rng x");
+    hip_check(hipMemcpy(created.rng_a.get(), a, count * sizeof(uint32_t), hipMemcpyHostToDevice), "upload rng a");
+    dev_ = std::move(created);
 
     in_queue_.reset(new BoundedQueue<Job>(5));          // queueToOpenCL_(5), OpenCL.cxx:77
     out_queue_.reset(new BoundedQueue<Result>(0));      // queueFromOpenCL_(0): rendezvous, OpenCL.cxx:78
@@ -415,20 +371,20 @@ void Converter::initialize_with_streams(const uint64_t *x, const uint32_t *a, si
     worker_ = std::thread([this] { worker(); });
 }
 
-void Converter::setup_device_buffers()
+void Converter::setup_device_buffers(DeviceState &D)
 {
     const GeoTables &G = tables_.geo;
-    auto upload = [&](void **dst, const void *src, size_t bytes, const char *what) {
-        hip_check(hipMalloc(dst, std::max<size_t>(bytes, 16)), what);
-        if (bytes) hip_check(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice), what);
+    auto upload = [&](auto &dst, const auto &src, const char *what) {
+        dst.alloc(src.size(), what);
+        if (!src.empty()) hip_check(hipMemcpy(dst.get(), src.data(), src.size() * sizeof(src[0]), hipMemcpyHostToDevice), what);
     };
-    upload(reinterpret_cast<void **>(&d_tables_), tables_.lds_image.data(), tables_.lds_image.size() * 4, "tables");
-    upload(reinterpret_cast<void **>(&d_len_table_), tables_.len_table.data(), tables_.len_table.size() * 4, "length tables");
-    upload(reinterpret_cast<void **>(&d_prox_map_), tables_.prox_map.data(), tables_.prox_map.size() * sizeof(uint32_t), "string proximity map");
+    upload(D.tables, tables_.lds_image, "tables");
+    upload(D.len_table, tables_.len_table, "length tables");
+    upload(D.prox_map, tables_.prox_map, "string proximity map");
     {   // the DOM proximity map as the kernels read it: every cell with the centre of the DOM it names (kparams.h: dom_cells).  Built and
         // uploaded in pieces of a million cells: the whole image is up to 256 MB, which the host need not hold beside the words
         const size_t cells = tables_.dom_prox.size();
-        hip_check(hipMalloc(reinterpret_cast<void **>(&d_dom_prox_), std::max<size_t>(cells * 16, 16)), "DOM proximity map");
+        D.dom_prox.alloc(cells * 4, "DOM proximity map");
         constexpr size_t kPiece = size_t{1} << 20;
         std::vector<uint32_t> fused(4 * std::min(cells, kPiece));
         for (size_t first = 0; first < cells; first += kPiece) {
@@ -440,14 +396,14 @@ void Converter::setup_device_buffers()
                 if (id != 0xffffu && 4 * static_cast<size_t>(id) + 2 < tables_.dom_centres.size())
                     std::memcpy(&fused[4 * k + 1], &tables_.dom_centres[4 * static_cast<size_t>(id)], 12);
             }
-            hip_check(hipMemcpy(d_dom_prox_ + 4 * first, fused.data(), count * 16, hipMemcpyHostToDevice), "DOM proximity map");
+            hip_check(hipMemcpy(D.dom_prox.get() + 4 * first, fused.data(), count * 16, hipMemcpyHostToDevice), "DOM proximity map");
         }
     }
-    upload(reinterpret_cast<void **>(&d_dom_centres_), tables_.dom_centres.data(), tables_.dom_centres.size() * 4, "DOM centres");
-    upload(reinterpret_cast<void **>(&d_dom_named_), tables_.dom_named.data(), tables_.dom_named.size() * 4, "named-DOM records");
-    upload(reinterpret_cast<void **>(&d_dom_tx_), G.dom_tx.data(), G.dom_tx.size() * 2, "dom_tx");
-    upload(reinterpret_cast<void **>(&d_dom_ty_), G.dom_ty.data(), G.dom_ty.size() * 2, "dom_ty");
-    upload(reinterpret_cast<void **>(&d_dom_tz_), G.dom_tz.data(), G.dom_tz.size() * 4, "dom_tz");
+    upload(D.dom_centres, tables_.dom_centres, "DOM centres");
+    upload(D.dom_named, tables_.dom_named, "named-DOM records");
+    upload(D.dom_tx, G.dom_tx, "dom_tx");
+    upload(D.dom_ty, G.dom_ty, "dom_ty");
+    upload(D.dom_tz, G.dom_tz, "dom_tz");
     {   // index -> ID tables for assemble_hits_kernel; an ID that does not fit the record's short / ushort keeps the
         // conversion on the host, which reports it when a photon carries it (OpenCL.cxx:1577-1586)
         std::vector<int16_t> sid(G.string_index_to_id.size());
@@ -462,44 +418,44 @@ void Converter::setup_device_buffers()
         }
         start.back() = static_cast<uint32_t>(did.size());
         if (fits && !sid.empty()) {
-            upload(reinterpret_cast<void **>(&d_id_strings_), sid.data(), sid.size() * 2, "string IDs");
-            upload(reinterpret_cast<void **>(&d_id_doms_), did.data(), did.size() * 2, "OM IDs");
-            upload(reinterpret_cast<void **>(&d_id_dom_start_), start.data(), start.size() * 4, "OM ID offsets");
+            upload(D.id_strings, sid, "string IDs");
+            upload(D.id_doms, did, "OM IDs");
+            upload(D.id_dom_start, start, "OM ID offsets");
         }
     }
     if (history_entries_) {
-        const size_t bytes = prop_kernel_max_lanes() * history_entries_ * 16;
-        hip_check(hipMalloc(reinterpret_cast<void **>(&d_hist_ring_), bytes), "history ring");
-        hip_check(hipMemset(d_hist_ring_, 0, bytes), "history ring");
+        const size_t floats = prop_kernel_max_lanes() * history_entries_ * 4;
+        D.hist_ring.alloc(floats, "history ring");
+        hip_check(hipMemset(D.hist_ring.get(), 0, floats * 4), "history ring");
     }
-    hip_check(hipMalloc(reinterpret_cast<void **>(&d_rng_x_), max_workitems_ * sizeof(uint64_t)), "rng x");
-    hip_check(hipMalloc(reinterpret_cast<void **>(&d_rng_a_), max_workitems_ * sizeof(uint32_t)), "rng a");
+    D.rng_x.alloc(max_workitems_, "rng x");
+    D.rng_a.alloc(max_workitems_, "rng a");
     num_slots_ = double_buffering_ ? 2 : 1;
     for (int i = 0; i < num_slots_; ++i) {
-        Slot &sl = slots_[i];
-        hip_check(hipMalloc(reinterpret_cast<void **>(&sl.d_steps), max_workitems_ * sizeof(DevStep)), "steps");
-        hip_check(hipMalloc(reinterpret_cast<void **>(&sl.d_photons), static_cast<size_t>(max_output_photons_) * sizeof(DevPhoton)), "photons");
-        hip_check(hipMalloc(reinterpret_cast<void **>(&sl.d_hit_count), 16), "hit counter");
-        hip_check(hipHostMalloc(reinterpret_cast<void **>(&sl.h_steps), max_workitems_ * sizeof(clsimhip_step), hipHostMallocDefault), "pinned steps");
-        hip_check(hipHostMalloc(reinterpret_cast<void **>(&sl.h_hit_count), 16, hipHostMallocDefault), "pinned counter");
+        Slot &sl = D.slots[i];
+        sl.d_steps.alloc(max_workitems_, "steps");
+        sl.d_photons.alloc(max_output_photons_, "photons");
+        sl.d_hit_count.alloc(4, "hit counter");
+        sl.h_steps.alloc(max_workitems_, "pinned steps");
+        sl.h_hit_count.alloc(4, "pinned counter");
         if (history_entries_) {
-            const size_t bytes = static_cast<size_t>(max_output_photons_) * history_entries_ * 16;
-            hip_check(hipMalloc(reinterpret_cast<void **>(&sl.d_hist_out), bytes), "photon histories");
-            hip_check(hipHostMalloc(reinterpret_cast<void **>(&sl.h_hist), bytes, hipHostMallocDefault), "pinned photon histories");
+            const size_t floats = static_cast<size_t>(max_output_photons_) * history_entries_ * 4;
+            sl.d_hist_out.alloc(floats, "photon histories");
+            sl.h_hist.alloc(floats, "pinned photon histories");
         }
         if (mcpe_) {
-            if (!d_id_strings_) throw Error(CLSIMHIP_ERR_CONFIG, "MCPE generator: the geometry has no DOM");
-            hip_check(hipMalloc(reinterpret_cast<void **>(&sl.d_mcpes), static_cast<size_t>(max_output_photons_) * sizeof(clsimhip_mcpe)), "MCPEs");
-            hip_check(hipMalloc(reinterpret_cast<void **>(&sl.d_mcpe_counters), 32), "MCPE counters");
-            hip_check(hipHostMalloc(reinterpret_cast<void **>(&sl.h_mcpe_counters), 32, hipHostMallocDefault), "pinned MCPE counters");
+            if (!D.id_strings) throw Error(CLSIMHIP_ERR_CONFIG, "MCPE generator: the geometry has no DOM");
+            sl.d_mcpes.alloc(max_output_photons_, "MCPEs");
+            sl.d_mcpe_counters.alloc(8, "MCPE counters");
+            sl.h_mcpe_counters.alloc(8, "pinned MCPE counters");
         }
-        hip_check(hipEventCreate(&sl.start), "hipEventCreate");
-        hip_check(hipEventCreate(&sl.stop), "hipEventCreate");
-        hip_check(hipEventCreateWithFlags(&sl.counted, hipEventDisableTiming), "hipEventCreate");
-        hip_check(hipEventCreateWithFlags(&sl.uploaded, hipEventDisableTiming), "hipEventCreate");
+        sl.start.create("hipEventCreate");
+        sl.stop.create("hipEventCreate");
+        sl.counted.create_untimed("hipEventCreate");
+        sl.uploaded.create_untimed("hipEventCreate");
     }
-    hip_check(hipMalloc(reinterpret_cast<void **>(&d_queue_), static_cast<size_t>(kQueueWords) * kQueueSlots * sizeof(uint32_t)), "step queue");
-    hip_check(hipMalloc(reinterpret_cast<void **>(&d_work_), max_workitems_ * sizeof(WorkRecord)), "work records");
+    D.queue.alloc(static_cast<size_t>(kQueueWords) * kQueueSlots, "step queue");
+    D.work.alloc(max_workitems_, "work records");
 #ifdef CLSIMHIP_DEVELOPER
     // DEVELOPER BUILD ONLY (make DEVELOPER=1; tools/build_variant.sh, tools/scan_env.sh): the round 1-5 environment names, through the
     // same door as clsimhip_set_tuning.  The default build reads none of them.
@@ -517,56 +473,56 @@ void Converter::setup_device_buffers()
 #endif
     // photon histories are kept per lane and the pooled kernel moves photons between lanes; a very large table image
     // leaves its pools no LDS
+    std::lock_guard<std::mutex> lk(tuning_mutex_);
     pool_possible_ = history_entries_ == 0 &&
         pool_kernel_fits(static_cast<uint32_t>(tables_.lds_image.size()), stop_detected_ ? 0u : static_cast<uint32_t>(tables_.params.num_strings), tables_.params.num_layers);
     apply_kernel_choice();
 }
 
-KParams Converter::launch_params(const void *d_steps, size_t n, size_t rng_offset, void *d_photons, size_t capacity, void *d_hits, hipStream_t stream)
+KParams Converter::launch_params(const LaunchTuning &tuning, const void *d_steps, size_t n, size_t rng_offset, void *d_photons, size_t capacity, void *d_hits,
+                                 hipStream_t stream)
 {
+    DeviceState &D = dev_;
     KParams P = tables_.params;
-    P.tables = d_tables_;
+    P.tables = D.tables.get();
     P.steps = static_cast<const DevStep *>(d_steps);
     P.n_steps = static_cast<uint32_t>(n);
-    P.rng_x = d_rng_x_ + rng_offset;
-    P.rng_a = d_rng_a_ + rng_offset;
+    P.rng_x = D.rng_x.get() + rng_offset;
+    P.rng_a = D.rng_a.get() + rng_offset;
     P.out = static_cast<DevPhoton *>(d_photons);
     P.hit_count = static_cast<uint32_t *>(d_hits);
     P.max_hits = static_cast<uint32_t>(std::min<size_t>(capacity, 0xffffffffull));
     {   // step queue head for this launch (zeroed in stream order)
         std::lock_guard<std::mutex> lk(ev_mutex_);
-        P.queue = d_queue_ + static_cast<size_t>(kQueueWords) * (queue_slot_++ % kQueueSlots);
-        last_queue_ = P.queue;
+        P.queue = D.queue.get() + static_cast<size_t>(kQueueWords) * (queue_slot_++ % kQueueSlots);
+        D.last_queue = P.queue;
     }
     hip_check(hipMemsetAsync(P.queue, 0, kQueueWords * sizeof(uint32_t), stream), "reset step queue");
-    {
-        std::lock_guard<std::mutex> lk(tuning_mutex_);
-        P.k_new = k_new_;
-        P.k_search = k_search_;
-        P.slices = k_slices_;
-        P.k_pop = k_pop_;
-        P.k_wait = k_wait_;
-        P.k_aim = k_aim_;
-        P.pool_ready = pool_ready_;
-    }
+    P.k_new = tuning.k_new;
+    P.k_search = tuning.k_search;
+    P.slices = tuning.slices;
+    P.k_pop = tuning.k_pop;
+    P.k_wait = tuning.k_wait;
+    P.k_aim = tuning.k_aim;
+    P.pool_ready = tuning.pool_ring;
     P.chip_share = concurrent_launches_;
 #ifdef CLSIMHIP_CENSUS
-    if (!d_census_) hip_check(hipMalloc(reinterpret_cast<void **>(&d_census_), kCensusBytes), "census");
-    P.census = d_census_;
+    if (!D.census) D.census.alloc(kCensusBytes / sizeof(unsigned long long), "census");
+    P.census = D.census.get();
     hip_check(hipMemsetAsync(P.census, 0, kCensusBytes, stream), "reset census");
     hip_check(hipMemsetAsync(P.census + 8, 0xff, 8, stream), "reset census");
 #endif
-    P.work = d_work_ + rng_offset;       // work records live with the stream slots: launches on disjoint slots may overlap
-    P.len_table = d_len_table_;
-    P.prox_map = d_prox_map_;
-    P.dom_cells = reinterpret_cast<const uint4 *>(d_dom_prox_);
-    P.dom_centres = reinterpret_cast<const float4 *>(d_dom_centres_);
-    P.dom_named = reinterpret_cast<const uint4 *>(d_dom_named_);
-    P.hist_ring = d_hist_ring_;
+    P.work = D.work.get() + rng_offset;       // work records live with the stream slots: launches on disjoint slots may overlap
+    P.len_table = D.len_table.get();
+    P.prox_map = D.prox_map.get();
+    P.dom_cells = reinterpret_cast<const uint4 *>(D.dom_prox.get());
+    P.dom_centres = reinterpret_cast<const float4 *>(D.dom_centres.get());
+    P.dom_named = reinterpret_cast<const uint4 *>(D.dom_named.get());
+    P.hist_ring = D.hist_ring.get();
     P.hist_out = nullptr;               // set per slot by submit(); the device path has no history output
-    P.dom_tx = d_dom_tx_;
-    P.dom_ty = d_dom_ty_;
-    P.dom_tz = d_dom_tz_;
+    P.dom_tx = D.dom_tx.get();
+    P.dom_ty = D.dom_ty.get();
+    P.dom_tz = D.dom_tz.get();
     return P;
 }
 
@@ -583,128 +539,62 @@ void Converter::enqueue_steps(const clsimhip_step *steps, size_t n, uint32_t ide
     job.id = identifier;
     job.n = n;
     for (size_t i = 0; i < n; ++i) job.generated += steps[i].num_photons;
-    job.pinned = StepLease(this, take_step_buffer(n));
-    if (job.pinned.b.p) std::memcpy(job.pinned.b.p, steps, n * sizeof(clsimhip_step));
+    job.pinned = step_pool_.take(n, std::max(n, std::min(max_workitems_, n + n / 4)), device_);
+    if (job.pinned) std::memcpy(job.pinned.get(), steps, n * sizeof(clsimhip_step));
     else job.steps.assign(steps, steps + n);
     in_queue_->put(std::move(job));
-}
-
-Converter::StepBuffer Converter::take_step_buffer(size_t steps)
-{
-    StepBuffer b;
-    b.capacity = std::min(max_workitems_, steps + steps / 4);
-    if (b.capacity < steps) b.capacity = steps;
-    const size_t bytes = b.capacity * sizeof(clsimhip_step);
-    StepBuffer retired;                 // a free buffer that is too small, given up for one of the size that is needed
-    {
-        // one lock scope for "is there a buffer, may another be made, is one to be replaced" and the count (check and
-        // increment were in two scopes, so callers side by side could exceed kStepBuffers)
-        std::lock_guard<std::mutex> lk(step_pool_mutex_);
-        size_t best = free_step_buffers_.size();
-        for (size_t i = 0; i < free_step_buffers_.size(); ++i)
-            if (free_step_buffers_[i].capacity >= steps && (best == free_step_buffers_.size() || free_step_buffers_[i].capacity < free_step_buffers_[best].capacity)) best = i;
-        if (best != free_step_buffers_.size()) {
-            const StepBuffer found = free_step_buffers_[best];
-            free_step_buffers_.erase(free_step_buffers_.begin() + static_cast<std::ptrdiff_t>(best));
-            return found;
-        }
-        if (step_pinning_refused_) return StepBuffer();
-        const bool full = step_buffers_made_ >= kStepBuffers || (step_pool_bytes_ + bytes > kStepPoolBytes && step_buffers_made_ >= 3);
-        if (full) {
-            // A pool whose buffers were sized by small first bunches (warm-up, tests) must not stay too small for production bunches:
-            // the smallest FREE buffer goes and one of the needed size takes its place.  With none free every buffer is in flight:
-            // the steps travel in a vector this once.
-            if (free_step_buffers_.empty()) {
-                if (!step_fallback_logged_) {
-                    step_fallback_logged_ = true;
-                    std::fprintf(stderr, "clsimhip: all %d page-locked step buffers are in flight; this bunch of %zu steps is staged through pageable memory\n",
-                                 step_buffers_made_, steps);
-                }
-                return StepBuffer();
-            }
-            size_t smallest = 0;
-            for (size_t i = 1; i < free_step_buffers_.size(); ++i)
-                if (free_step_buffers_[i].capacity < free_step_buffers_[smallest].capacity) smallest = i;
-            retired = free_step_buffers_[smallest];
-            free_step_buffers_.erase(free_step_buffers_.begin() + static_cast<std::ptrdiff_t>(smallest));
-            step_pool_bytes_ -= retired.capacity * sizeof(clsimhip_step);
-            --step_buffers_made_;
-            if (step_pool_bytes_ + bytes > kStepPoolBytes && step_buffers_made_ >= 3) {     // (still over the byte budget: the pool shrinks by one)
-                free_step_buffers_.push_back(retired);
-                step_pool_bytes_ += retired.capacity * sizeof(clsimhip_step);
-                ++step_buffers_made_;
-                return StepBuffer();
-            }
-        }
-        ++step_buffers_made_;
-        step_pool_bytes_ += bytes;
-    }
-    DeviceGuard on_device(device_);
-    if (retired.p) (void)hipHostFree(retired.p);
-    if (hipHostMalloc(reinterpret_cast<void **>(&b.p), bytes, hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        std::lock_guard<std::mutex> lk(step_pool_mutex_);
-        --step_buffers_made_;
-        step_pool_bytes_ -= bytes;
-        step_pinning_refused_ = true;
-        return StepBuffer();
-    }
-    return b;
-}
-
-void Converter::give_step_buffer(StepBuffer b)
-{
-    if (!b.p) return;
-    std::lock_guard<std::mutex> lk(step_pool_mutex_);
-    free_step_buffers_.push_back(b);
 }
 
 // OpenCL.cxx:824-934: upload, launch; everything is queued on the compute stream, nothing waits
 void Converter::submit(Slot &s, Job &job)
 {
+    const LaunchTuning tuning = tuning_snapshot();      // one setting for the whole launch, whatever set_tuning() does meanwhile
+    const hipStream_t stream = dev_.stream.get(), upload_stream = dev_.upload_stream.get();
     const size_t n = job.n;
     s.id = job.id;
     s.generated = job.generated;
+    s.result_min_records = tuning.result_min_records;
     // (the slot's previous upload finished long ago: its kernel has, or the slot would not be free)
-    give_step_buffer(s.step_buffer);
-    s.step_buffer = job.pinned.release();
-    const clsimhip_step *source = s.step_buffer.p;
+    s.step_lease = std::move(job.pinned);
+    const clsimhip_step *source = s.step_lease.get();
     if (!source) {
-        std::memcpy(s.h_steps, job.steps.data(), n * sizeof(clsimhip_step));
-        source = s.h_steps;
+        std::memcpy(s.h_steps.get(), job.steps.data(), n * sizeof(clsimhip_step));
+        source = s.h_steps.get();
     }
     // the upload has a stream of its own: with double buffering it runs while the previous bunch's kernel does
-    hip_check(hipMemcpyAsync(s.d_steps, source, n * sizeof(DevStep), hipMemcpyHostToDevice, upload_stream_), "upload steps");
-    hip_check(hipEventRecord(s.uploaded, upload_stream_), "event");
-    hip_check(hipStreamWaitEvent(stream_, s.uploaded, 0), "wait for the upload");
-    hip_check(hipMemsetAsync(s.d_hit_count, 0, 4, stream_), "reset hit counter");
-    KParams P = launch_params(s.d_steps, n, 0, s.d_photons, max_output_photons_, s.d_hit_count, stream_);
-    P.hist_out = s.d_hist_out;
-    P.id_strings = d_id_strings_; P.id_doms = d_id_doms_; P.id_dom_start = d_id_dom_start_;
-    hip_check(hipEventRecord(s.start, stream_), "event");
-    hip_check(launch(P, stream_), "propagation kernel launch");
-    hip_check(hipEventRecord(s.stop, stream_), "event");
-    hip_check(hipMemcpyAsync(s.h_hit_count, s.d_hit_count, 4, hipMemcpyDeviceToHost, stream_), "download hit counter");
-    hip_check(hipMemcpyAsync(s.h_hit_count + 1, P.queue + 2, 12, hipMemcpyDeviceToHost, stream_), "download skipped-step and bad-record counters");
+    hip_check(hipMemcpyAsync(s.d_steps.get(), source, n * sizeof(DevStep), hipMemcpyHostToDevice, upload_stream), "upload steps");
+    hip_check(hipEventRecord(s.uploaded.get(), upload_stream), "event");
+    hip_check(hipStreamWaitEvent(stream, s.uploaded.get(), 0), "wait for the upload");
+    hip_check(hipMemsetAsync(s.d_hit_count.get(), 0, 4, stream), "reset hit counter");
+    KParams P = launch_params(tuning, s.d_steps.get(), n, 0, s.d_photons.get(), max_output_photons_, s.d_hit_count.get(), stream);
+    P.hist_out = s.d_hist_out.get();
+    P.id_strings = dev_.id_strings.get(); P.id_doms = dev_.id_doms.get(); P.id_dom_start = dev_.id_dom_start.get();
+    hip_check(hipEventRecord(s.start.get(), stream), "event");
+    hip_check(launch(P, tuning, stream), "propagation kernel launch");
+    hip_check(hipEventRecord(s.stop.get(), stream), "event");
+    hip_check(hipMemcpyAsync(s.h_hit_count.get(), s.d_hit_count.get(), 4, hipMemcpyDeviceToHost, stream), "download hit counter");
+    hip_check(hipMemcpyAsync(s.h_hit_count.get() + 1, P.queue + 2, 12, hipMemcpyDeviceToHost, stream), "download skipped-step and bad-record counters");
     if (mcpe_) {
         // behind assemble_hits_kernel on the bunch's stream, over the records the bunch stored (min(hit counter, capacity)); outside
         // the start / stop pair: the propagation kernel's time stays what it was
-        mcpe_->convert_device(device_, s.d_photons, s.d_hit_count, max_output_photons_, s.d_mcpes, max_output_photons_, s.d_mcpe_counters, stream_);
-        hip_check(hipMemcpyAsync(s.h_mcpe_counters, s.d_mcpe_counters, 20, hipMemcpyDeviceToHost, stream_), "download MCPE counters");
+        mcpe_->convert_device(device_, s.d_photons.get(), s.d_hit_count.get(), max_output_photons_, s.d_mcpes.get(), max_output_photons_, s.d_mcpe_counters.get(), stream);
+        hip_check(hipMemcpyAsync(s.h_mcpe_counters.get(), s.d_mcpe_counters.get(), 20, hipMemcpyDeviceToHost, stream), "download MCPE counters");
     }
-    hip_check(hipEventRecord(s.counted, stream_), "event");
+    hip_check(hipEventRecord(s.counted.get(), stream), "event");
 }
 
 // OpenCL.cxx:994-1086: wait for the bunch, download and convert its photons (on the copy stream, so that the
 // next bunch's kernel -- already queued on the compute stream -- runs meanwhile), hand the result out
 void Converter::finish(Slot &s, std::chrono::steady_clock::time_point &last_done, bool &first)
 {
-    hip_check(hipEventSynchronize(s.counted), "propagation kernel");
-    uint32_t hits = *s.h_hit_count;
-    if (s.h_hit_count[1] != 0)
+    const hipStream_t copy_stream = dev_.copy_stream.get();
+    hip_check(hipEventSynchronize(s.counted.get()), "propagation kernel");
+    const uint32_t *counters = s.h_hit_count.get();
+    uint32_t hits = counters[0];
+    if (counters[1] != 0)
         std::fprintf(stderr, "clsimhip: %u steps of bunch %u have non-finite position/direction/length/beta or a source type without spectrum and were not propagated\n",
-                     s.h_hit_count[1], s.id);
-    if (s.h_hit_count[3] != 0)           // (queue[4]: assemble_hits_kernel met records whose string / DOM indices name no DOM)
+                     counters[1], s.id);
+    if (counters[3] != 0)           // (queue[4]: assemble_hits_kernel met records whose string / DOM indices name no DOM)
         throw Error(CLSIMHIP_ERR_DEVICE, "photon record with out-of-range string/DOM index");
     if (hits > max_output_photons_) {
         // OpenCL.cxx:1027-1032: logged, truncated
@@ -717,7 +607,7 @@ void Converter::finish(Slot &s, std::chrono::steady_clock::time_point &last_done
     // the caller's hands the records go into a plain vector.
     uint32_t n_mcpes = 0;
     if (mcpe_) {
-        const uint32_t *mc = s.h_mcpe_counters;
+        const uint32_t *mc = s.h_mcpe_counters.get();
         if ((mc[1] | mc[2] | mc[3] | mc[4]) != 0u)      // log_fatal in the reference, all four (I3PhotonToMCPEConverter.cxx:606, 612, 630, 660)
             throw Error(CLSIMHIP_ERR_DEVICE, "MCPE generator, bunch " + std::to_string(s.id) + ": " + std::to_string(mc[1]) + " photons with negative weight, " +
                                                  std::to_string(mc[2]) + " not on the DOM surface, " + std::to_string(mc[3]) + " at a DOM without wavelength acceptance, " +
@@ -731,11 +621,9 @@ void Converter::finish(Slot &s, std::chrono::steady_clock::time_point &last_done
     std::unique_ptr<std::vector<clsimhip_photon>> photons;
     clsimhip_photon *where = nullptr;
     if (hits) {
-        const PinnedBuffer buf = take_result_buffer(hits);
-        if (buf.p) {
-            r.pinned.reset(buf.p);
-            r.pinned_capacity = buf.capacity;
-            where = buf.p;
+        r.pinned = result_pool_.take(hits, result_capacity(hits, s.result_min_records), device_);
+        if (r.pinned) {
+            where = r.pinned.get();
         } else {
             // every pool buffer is with the caller (or the host refuses to page-lock more): the download goes into pageable memory,
             // which is correct and slower -- said once, because nothing else shows it
@@ -747,36 +635,19 @@ void Converter::finish(Slot &s, std::chrono::steady_clock::time_point &last_done
             photons.reset(new std::vector<clsimhip_photon>(hits));
             where = photons->data();
         }
-        try {
-            hip_check(hipMemcpyAsync(where, s.d_photons, static_cast<size_t>(hits) * sizeof(DevPhoton), hipMemcpyDeviceToHost, copy_stream_), "download photons");
-            hip_check(hipStreamSynchronize(copy_stream_), "download photons");
-        } catch (...) {
-            // the pool buffer goes back to the pool (it stays counted in result_buffers_made_ and stays usable), not to hipHostFree
-            if (r.pinned) {
-                std::lock_guard<std::mutex> lk(result_pool_mutex_);
-                free_result_buffers_.push_back(PinnedBuffer{r.pinned.release(), r.pinned_capacity});
-            }
-            throw;
-        }
-        if (!d_id_strings_) replace_indices(where, hits);      // OpenCL.cxx:1604-1619 does this on the caller thread
+        // (a failure from here on drops r, whose pool buffers go back to their pools)
+        hip_check(hipMemcpyAsync(where, s.d_photons.get(), static_cast<size_t>(hits) * sizeof(DevPhoton), hipMemcpyDeviceToHost, copy_stream), "download photons");
+        hip_check(hipStreamSynchronize(copy_stream), "download photons");
+        if (!dev_.id_strings) replace_indices(where, hits);      // OpenCL.cxx:1604-1619 does this on the caller thread
     }
     if (mcpe_) {
         r.mcpe_count = n_mcpes;
         if (n_mcpes) {
-            const McpeBuffer buf = take_mcpe_buffer(n_mcpes);
-            clsimhip_mcpe *to = buf.p;
-            if (buf.p) { r.mcpe_pinned.reset(buf.p); r.mcpe_pinned_capacity = buf.capacity; }
-            else { r.mcpes.reset(new std::vector<clsimhip_mcpe>(n_mcpes)); to = r.mcpes->data(); }
-            try {
-                hip_check(hipMemcpyAsync(to, s.d_mcpes, static_cast<size_t>(n_mcpes) * sizeof(clsimhip_mcpe), hipMemcpyDeviceToHost, copy_stream_), "download MCPEs");
-                hip_check(hipStreamSynchronize(copy_stream_), "download MCPEs");
-            } catch (...) {
-                // both pool buffers go back to their pools, as above
-                std::lock_guard<std::mutex> lk(result_pool_mutex_);
-                if (r.pinned) free_result_buffers_.push_back(PinnedBuffer{r.pinned.release(), r.pinned_capacity});
-                if (r.mcpe_pinned) free_mcpe_buffers_.push_back(McpeBuffer{r.mcpe_pinned.release(), r.mcpe_pinned_capacity});
-                throw;
-            }
+            r.mcpe_pinned = mcpe_pool_.take(n_mcpes, result_capacity(n_mcpes, s.result_min_records), device_);
+            clsimhip_mcpe *to = r.mcpe_pinned.get();
+            if (!to) { r.mcpes.reset(new std::vector<clsimhip_mcpe>(n_mcpes)); to = r.mcpes->data(); }
+            hip_check(hipMemcpyAsync(to, s.d_mcpes.get(), static_cast<size_t>(n_mcpes) * sizeof(clsimhip_mcpe), hipMemcpyDeviceToHost, copy_stream), "download MCPEs");
+            hip_check(hipStreamSynchronize(copy_stream), "download MCPEs");
         }
         if (!hits) r.handle.reset(new clsimhip_photon());
     }
@@ -784,8 +655,8 @@ void Converter::finish(Slot &s, std::chrono::steady_clock::time_point &last_done
     if (hits && history_entries_) {
         // ConvertPhotonHistories (OpenCL.cxx:940-989): unroll each ring into forward order
         const size_t N = history_entries_;
-        hip_check(hipMemcpyAsync(s.h_hist, s.d_hist_out, static_cast<size_t>(hits) * N * 16, hipMemcpyDeviceToHost, copy_stream_), "download photon histories");
-        hip_check(hipStreamSynchronize(copy_stream_), "download photon histories");
+        hip_check(hipMemcpyAsync(s.h_hist.get(), s.d_hist_out.get(), static_cast<size_t>(hits) * N * 16, hipMemcpyDeviceToHost, copy_stream), "download photon histories");
+        hip_check(hipStreamSynchronize(copy_stream), "download photon histories");
         histories.reset(new std::vector<float>(static_cast<size_t>(hits) * N * 4, 0.f));
         for (size_t i = 0; i < hits; ++i) {
             const uint32_t num_scatters = where[i].num_scatters;
@@ -793,13 +664,13 @@ void Converter::finish(Slot &s, std::chrono::steady_clock::time_point &last_done
             const size_t recorded = std::min<size_t>(num_scatters, N);
             size_t cur = (num_scatters <= N) ? 0 : (num_scatters % N);
             for (size_t j = 0; j < recorded; ++j) {
-                std::memcpy(&(*histories)[(i * N + j) * 4], &s.h_hist[(i * N + cur) * 4], 16);
+                std::memcpy(&(*histories)[(i * N + j) * 4], &s.h_hist.get()[(i * N + cur) * 4], 16);
                 if (++cur >= N) cur = 0;
             }
         }
     }
     float ms = 0.f;
-    hip_check(hipEventElapsedTime(&ms, s.start, s.stop), "event time");
+    hip_check(hipEventElapsedTime(&ms, s.start.get(), s.stop.get()), "event time");
     const auto now = std::chrono::steady_clock::now();
     {
         std::lock_guard<std::mutex> lk(stats_mutex_);
@@ -826,6 +697,7 @@ void Converter::worker()
     auto last_done = std::chrono::steady_clock::now();
     bool first = true;
     int cur = 0, pending = -1;
+    Slot *const slots = dev_.slots;
     Job job;
     try {
         for (;;) {
@@ -837,24 +709,24 @@ void Converter::worker()
                 // a bunch is running: take the next one as soon as it arrives, but stop waiting when the kernel is done
                 have = false;
                 while (!(have = in_queue_->get_for(job, 200))) {
-                    if (hipEventQuery(slots_[pending].counted) == hipSuccess || in_queue_->closed()) break;
+                    if (hipEventQuery(slots[pending].counted.get()) == hipSuccess || in_queue_->closed()) break;
                 }
                 if (!have) {
-                    finish(slots_[pending], last_done, first);
+                    finish(slots[pending], last_done, first);
                     pending = -1;
                     continue;
                 }
             }
-            submit(slots_[cur], job);
-            if (pending >= 0) finish(slots_[pending], last_done, first);
+            submit(slots[cur], job);
+            if (pending >= 0) finish(slots[pending], last_done, first);
             if (num_slots_ == 2) {
                 pending = cur;
                 cur ^= 1;
             } else {
-                finish(slots_[cur], last_done, first);
+                finish(slots[cur], last_done, first);
             }
         }
-        if (pending >= 0) finish(slots_[pending], last_done, first);
+        if (pending >= 0) finish(slots[pending], last_done, first);
     } catch (const Error &e) {
         // The reference's worker log_fatal()s on device errors, which ends the process (OpenCL.cxx:768-774).  A C
         // library must not take its host down: the error is logged and kept, both queues are closed so that blocked
@@ -923,74 +795,21 @@ void Converter::result_mcpes(const clsimhip_photon *photons, const clsimhip_mcpe
 
 void Converter::release_result(const clsimhip_photon *photons)
 {
-    PinnedBuffer back;
-    McpeBuffer mcpe_back;
-    {
-        std::lock_guard<std::mutex> lk(results_mutex_);
-        auto it = handed_out_.find(photons);
-        if (it == handed_out_.end()) return;
-        back.capacity = it->second.pinned_capacity;
-        back.p = it->second.pinned.release();
-        mcpe_back.capacity = it->second.mcpe_pinned_capacity;
-        mcpe_back.p = it->second.mcpe_pinned.release();
-        handed_out_.erase(it);
-    }
-    if (back.p || mcpe_back.p) {
-        std::lock_guard<std::mutex> lk(result_pool_mutex_);
-        if (back.p) free_result_buffers_.push_back(back);
-        if (mcpe_back.p) free_mcpe_buffers_.push_back(mcpe_back);
-    }
+    Result gone;                    // (its pool buffers go back to their pools outside the lock)
+    std::lock_guard<std::mutex> lk(results_mutex_);
+    auto it = handed_out_.find(photons);
+    if (it == handed_out_.end()) return;
+    gone = std::move(it->second);
+    handed_out_.erase(it);
 }
 
-void Converter::Result::HostFree::operator()(clsimhip_photon *p) const { if (p) (void)hipHostFree(p); }
-void Converter::Result::McpeHostFree::operator()(clsimhip_mcpe *p) const { if (p) (void)hipHostFree(p); }
-
-// A page-locked buffer for `records` records of a result pool (photons: free_result_buffers_, MCPEs: free_mcpe_buffers_): the
-// smallest free buffer that holds them; else a new one (a quarter more, at least min_result_records_, never more than
-// max_output_photons_), for which -- kResultBuffers made -- the smallest free one makes room; {nullptr, 0} when every buffer is
-// with the caller or the host refuses to page-lock more.
-template <class Buffer>
-Buffer Converter::take_pinned_buffer(std::vector<Buffer> &free_buffers, int &made, bool &refused, size_t records)
+// what a new buffer of a result pool holds: a quarter more than the records that arrive, rounded to 4096, at least "result_min_records",
+// never more than max_output_photons_
+size_t Converter::result_capacity(size_t records, size_t min_records) const
 {
-    decltype(Buffer().p) too_small = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(result_pool_mutex_);
-        size_t best = free_buffers.size(), smallest = free_buffers.size();
-        for (size_t i = 0; i < free_buffers.size(); ++i) {
-            const size_t c = free_buffers[i].capacity;
-            if (c >= records && (best == free_buffers.size() || c < free_buffers[best].capacity)) best = i;
-            if (smallest == free_buffers.size() || c < free_buffers[smallest].capacity) smallest = i;
-        }
-        if (best != free_buffers.size()) {
-            const Buffer b = free_buffers[best];
-            free_buffers.erase(free_buffers.begin() + static_cast<std::ptrdiff_t>(best));
-            return b;
-        }
-        if (refused) return Buffer();
-        if (made >= kResultBuffers) {
-            if (free_buffers.empty()) return Buffer();                          // all of them are with the caller
-            too_small = free_buffers[smallest].p;                               // a free one makes room for a larger one
-            free_buffers.erase(free_buffers.begin() + static_cast<std::ptrdiff_t>(smallest));
-            --made;
-        }
-        ++made;
-    }
-    if (too_small) (void)hipHostFree(too_small);
-    Buffer b;
-    b.capacity = std::max(min_result_records_, (records + records / 4 + 4095) / 4096 * 4096);
-    b.capacity = std::max(records, std::min(b.capacity, static_cast<size_t>(max_output_photons_)));
-    if (hipHostMalloc(reinterpret_cast<void **>(&b.p), b.capacity * sizeof(*b.p), hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        std::lock_guard<std::mutex> lk(result_pool_mutex_);
-        --made;
-        refused = true;
-        return Buffer();
-    }
-    return b;
+    const size_t c = std::max(min_records, (records + records / 4 + 4095) / 4096 * 4096);
+    return std::max(records, std::min(c, static_cast<size_t>(max_output_photons_)));
 }
-
-Converter::McpeBuffer Converter::take_mcpe_buffer(size_t records) { return take_pinned_buffer(free_mcpe_buffers_, mcpe_buffers_made_, mcpe_pinning_refused_, records); }
-Converter::PinnedBuffer Converter::take_result_buffer(size_t records) { return take_pinned_buffer(free_result_buffers_, result_buffers_made_, pinning_refused_, records); }
 
 size_t Converter::queue_size() const { need_init(); return in_queue_->size(); }
 bool Converter::more_photons_available() const { need_init(); return !out_queue_->empty(); }
@@ -1049,34 +868,21 @@ void Converter::propagate_device(const void *d_steps, size_t n, size_t rng_offse
     if (rng_offset + n > max_workitems_) throw Error(CLSIMHIP_ERR_ARGUMENT, "Number of steps is greater than maximum number of work items!");
     if (history_entries_) throw Error(CLSIMHIP_ERR_STATE, "photon histories are only delivered through EnqueueSteps/GetConversionResult");
     DeviceGuard on_device(device_);
-    std::pair<hipEvent_t, hipEvent_t> ev;
+    const LaunchTuning tuning = tuning_snapshot();
+    std::pair<Event, Event> ev;
     {
         std::lock_guard<std::mutex> lk(ev_mutex_);
-        if (!free_events_.empty()) { ev = free_events_.back(); free_events_.pop_back(); }
-        else { hip_check(hipEventCreate(&ev.first), "hipEventCreate"); hip_check(hipEventCreate(&ev.second), "hipEventCreate"); }
+        if (!dev_.free_events.empty()) { ev = std::move(dev_.free_events.back()); dev_.free_events.pop_back(); }
     }
+    if (!ev.first.get()) { ev.first.create("hipEventCreate"); ev.second.create("hipEventCreate"); }
     hip_check(hipMemsetAsync(d_hit_count, 0, 4, stream), "reset hit counter");
-    const KParams P = launch_params(d_steps, n, rng_offset, d_photons, capacity, d_hit_count, stream);
-    hip_check(hipEventRecord(ev.first, stream), "event");
-    hip_check(launch(P, stream), "propagation kernel launch");
-    hip_check(hipEventRecord(ev.second, stream), "event");
+    const KParams P = launch_params(tuning, d_steps, n, rng_offset, d_photons, capacity, d_hit_count, stream);
+    hip_check(hipEventRecord(ev.first.get(), stream), "event");
+    hip_check(launch(P, tuning, stream), "propagation kernel launch");
+    hip_check(hipEventRecord(ev.second.get(), stream), "event");
     std::lock_guard<std::mutex> lk(ev_mutex_);
-    pending_events_.push_back(ev);
+    dev_.pending_events.push_back(std::move(ev));
 }
-
-namespace {
-struct Scratch {                       // device memory of one tester call
-    void *p = nullptr;
-    explicit Scratch(size_t bytes)
-    {
-        const hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
-        if (e != hipSuccess) throw Error(CLSIMHIP_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
-    }
-    ~Scratch() { if (p) (void)hipFree(p); }
-    Scratch(const Scratch &) = delete;
-    Scratch &operator=(const Scratch &) = delete;
-};
-} // namespace
 
 void Converter::eval_device_function(int what, int layer, bool fast, const float *in4, size_t n, float *out4)
 {
@@ -1087,15 +893,15 @@ void Converter::eval_device_function(int what, int layer, bool fast, const float
     if (fast && !tables_.variant.fast) throw Error(CLSIMHIP_ERR_STATE, "this configuration has no FAST instantiation (Compile() could not prove its ranges)");
     if (n > 0xffffffffull) throw Error(CLSIMHIP_ERR_ARGUMENT, "too many points");
     DeviceGuard on_device(device_);
-    Scratch in(n * 16), out(n * 16);
-    hip_check(hipMemcpy(in.p, in4, n * 16, hipMemcpyHostToDevice), "hipMemcpy");
+    DeviceBuffer<float4> in(n, "hipMalloc"), out(n, "hipMalloc");
+    hip_check(hipMemcpy(in.get(), in4, n * 16, hipMemcpyHostToDevice), "hipMemcpy");
     KParams P = tables_.params;
-    P.tables = d_tables_;
-    P.len_table = d_len_table_;
-    hip_check(launch_eval_function(P, tables_.variant.lengths, tables_.variant.tilt, fast, what, layer, static_cast<const float4 *>(in.p), static_cast<uint32_t>(n),
-                                   static_cast<float4 *>(out.p), nullptr), "function tester launch");
+    P.tables = dev_.tables.get();
+    P.len_table = dev_.len_table.get();
+    hip_check(launch_eval_function(P, tables_.variant.lengths, tables_.variant.tilt, fast, what, layer, in.get(), static_cast<uint32_t>(n), out.get(), nullptr),
+              "function tester launch");
     hip_check(hipDeviceSynchronize(), "function tester");
-    hip_check(hipMemcpy(out4, out.p, n * 16, hipMemcpyDeviceToHost), "hipMemcpy");
+    hip_check(hipMemcpy(out4, out.get(), n * 16, hipMemcpyDeviceToHost), "hipMemcpy");
 }
 
 void Converter::eval_device_random(int what, int generator, bool fast, uint64_t *x, const uint32_t *a, size_t n_streams, size_t draws, float *out)
@@ -1107,31 +913,33 @@ void Converter::eval_device_random(int what, int generator, bool fast, uint64_t 
     if (fast && !tables_.variant.fast) throw Error(CLSIMHIP_ERR_STATE, "this configuration has no FAST instantiation (Compile() could not prove its ranges)");
     if (n_streams > 0xffffffffull || draws > 0xffffffffull) throw Error(CLSIMHIP_ERR_ARGUMENT, "too many draws");
     DeviceGuard on_device(device_);
-    Scratch dx(n_streams * 8), da(n_streams * 4), dout(n_streams * draws * 4);
-    hip_check(hipMemcpy(dx.p, x, n_streams * 8, hipMemcpyHostToDevice), "hipMemcpy");
-    hip_check(hipMemcpy(da.p, a, n_streams * 4, hipMemcpyHostToDevice), "hipMemcpy");
+    DeviceBuffer<uint64_t> dx(n_streams, "hipMalloc");
+    DeviceBuffer<uint32_t> da(n_streams, "hipMalloc");
+    DeviceBuffer<float> dout(n_streams * draws, "hipMalloc");
+    hip_check(hipMemcpy(dx.get(), x, n_streams * 8, hipMemcpyHostToDevice), "hipMemcpy");
+    hip_check(hipMemcpy(da.get(), a, n_streams * 4, hipMemcpyHostToDevice), "hipMemcpy");
     KParams P = tables_.params;
-    P.tables = d_tables_;
-    P.len_table = d_len_table_;
-    hip_check(launch_eval_random(P, fast, what, generator, static_cast<uint64_t *>(dx.p), static_cast<const uint32_t *>(da.p), static_cast<uint32_t>(n_streams),
-                                 static_cast<uint32_t>(draws), static_cast<float *>(dout.p), nullptr), "distribution tester launch");
+    P.tables = dev_.tables.get();
+    P.len_table = dev_.len_table.get();
+    hip_check(launch_eval_random(P, fast, what, generator, dx.get(), da.get(), static_cast<uint32_t>(n_streams), static_cast<uint32_t>(draws), dout.get(), nullptr),
+              "distribution tester launch");
     hip_check(hipDeviceSynchronize(), "distribution tester");
-    hip_check(hipMemcpy(out, dout.p, n_streams * draws * 4, hipMemcpyDeviceToHost), "hipMemcpy");
-    hip_check(hipMemcpy(x, dx.p, n_streams * 8, hipMemcpyDeviceToHost), "hipMemcpy");
+    hip_check(hipMemcpy(out, dout.get(), n_streams * draws * 4, hipMemcpyDeviceToHost), "hipMemcpy");
+    hip_check(hipMemcpy(x, dx.get(), n_streams * 8, hipMemcpyDeviceToHost), "hipMemcpy");
 }
 
 void Converter::kernel_time(bool reset, double *total_ms, uint64_t *launches)
 {
     std::lock_guard<std::mutex> lk(ev_mutex_);
-    for (auto &ev : pending_events_) {
-        hip_check(hipEventSynchronize(ev.second), "hipEventSynchronize");
+    for (auto &ev : dev_.pending_events) {
+        hip_check(hipEventSynchronize(ev.second.get()), "hipEventSynchronize");
         float ms = 0.f;
-        hip_check(hipEventElapsedTime(&ms, ev.first, ev.second), "hipEventElapsedTime");
+        hip_check(hipEventElapsedTime(&ms, ev.first.get(), ev.second.get()), "hipEventElapsedTime");
         dev_total_ms_ += ms;
         ++dev_launches_;
-        free_events_.push_back(ev);
     }
-    pending_events_.clear();
+    for (auto &ev : dev_.pending_events) dev_.free_events.push_back(std::move(ev));
+    dev_.pending_events.clear();
     if (total_ms) *total_ms = dev_total_ms_;
     if (launches) *launches = dev_launches_;
     if (reset) { dev_total_ms_ = 0; dev_launches_ = 0; }
@@ -1168,9 +976,9 @@ void Converter::debug_counters(uint32_t out[4])
     DeviceGuard on_device(device_);
     hip_check(hipDeviceSynchronize(), "sync");
 #ifdef CLSIMHIP_CENSUS
-    hip_check(hipMemcpy(out, d_census_, kCensusBytes, hipMemcpyDeviceToHost), "download census");     // the caller passes kCensusBytes (4 MiB)
+    hip_check(hipMemcpy(out, dev_.census.get(), kCensusBytes, hipMemcpyDeviceToHost), "download census");     // the caller passes kCensusBytes (4 MiB)
 #else
-    if (last_queue_) hip_check(hipMemcpy(out, last_queue_, 16, hipMemcpyDeviceToHost), "download counters");
+    if (dev_.last_queue) hip_check(hipMemcpy(out, dev_.last_queue, 16, hipMemcpyDeviceToHost), "download counters");
 #endif
 }
 
@@ -1180,7 +988,7 @@ void Converter::get_rng_state(uint64_t *x, size_t count)
     if (!x || count > max_workitems_) throw Error(CLSIMHIP_ERR_ARGUMENT, "bad rng state request");
     DeviceGuard on_device(device_);
     hip_check(hipDeviceSynchronize(), "sync");
-    hip_check(hipMemcpy(x, d_rng_x_, count * sizeof(uint64_t), hipMemcpyDeviceToHost), "download rng state");
+    hip_check(hipMemcpy(x, dev_.rng_x.get(), count * sizeof(uint64_t), hipMemcpyDeviceToHost), "download rng state");
 }
 
 } // namespace clsimhip

@@ -3,15 +3,18 @@
 // MI355X-native counterpart of I3CLSimStepToPhotonConverterOpenCL
 // (private/opencl/I3CLSimStepToPhotonConverterOpenCL.cxx).
 #pragma once
-#include <chrono>
 #include <hip/hip_runtime.h>
 
+#include <atomic>
+#include <chrono>
 #include <condition_variable>
+#include <cstdio>
 #include <deque>
 #include <memory>
 #include <mutex>
 #include <thread>
 
+#include "hip_resources.h"
 #include "host_model.h"
 #include "kparams.h"
 
@@ -133,19 +136,146 @@ private:
     bool closed_ = false;
 };
 
-// hipSetDevice for the duration of a call made on the CALLER's thread; the caller's current device is restored
-struct DeviceGuard {
-    explicit DeviceGuard(int device)
+// Page-locked host buffers of T records that go out on loan and come back: the result photons, the MCPEs and the steps of a
+// converter each have one.  take() hands out the smallest free buffer that holds the records; else a new one of `new_capacity`
+// records (the caller's sizing rule), for which -- with the pool full -- the smallest free buffer is given back to the host; else
+// an empty lease (every buffer is out, or the host refuses to page-lock more: the caller then uses pageable memory).
+struct PinnedPoolPolicy {
+    int max_buffers;                // buffers that exist at a time
+    size_t max_bytes;               // ... and their bytes together, which counts once three exist
+    const char *all_out_notice;     // said once (buffers made, records asked for) when every buffer is out; null: nothing is said
+};
+
+template <class T>
+class PinnedPool {
+public:
+    // A buffer on loan.  Whoever drops it -- a result released or never fetched, a job the closed queue refused, a slot that takes the
+    // next bunch -- returns it to the pool.  The pool outlives its leases (Converter declares its pools before everything that holds
+    // one); a lease without a pool frees its buffer, so that no path frees twice or not at all.
+    class Lease {
+    public:
+        Lease() = default;
+        Lease(Lease &&o) noexcept = default;
+        Lease &operator=(Lease &&o) noexcept
+        {
+            if (this != &o) { drop(); pool_ = o.pool_; buf_ = std::move(o.buf_); capacity_ = o.capacity_; }
+            return *this;
+        }
+        ~Lease() { drop(); }
+        T *get() const { return buf_.get(); }
+        size_t capacity() const { return capacity_; }
+        explicit operator bool() const { return static_cast<bool>(buf_); }
+        void drop() { if (pool_ && buf_) pool_->give(std::move(buf_), capacity_); }
+    private:
+        friend class PinnedPool;
+        Lease(PinnedPool *pool, PinnedBuffer<T> buf, size_t capacity) : pool_(pool), buf_(std::move(buf)), capacity_(capacity) {}
+        PinnedPool *pool_ = nullptr;
+        PinnedBuffer<T> buf_;
+        size_t capacity_ = 0;
+    };
+
+    explicit PinnedPool(const PinnedPoolPolicy &policy) : policy_(policy) {}
+    Lease take(size_t records, size_t new_capacity, int device)
     {
-        if (hipGetDevice(&previous_) != hipSuccess) previous_ = -1;
-        const hipError_t e = hipSetDevice(device);
-        if (e != hipSuccess) throw Error(CLSIMHIP_ERR_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
+        const size_t bytes = new_capacity * sizeof(T);
+        PinnedBuffer<T> retired;
+        {
+            // one lock scope for "is there a buffer, may another be made, is one to be replaced" and the count (check and
+            // increment were in two scopes, so callers side by side could exceed the limit)
+            std::lock_guard<std::mutex> lk(mutex_);
+            size_t best = free_.size(), smallest = free_.size();
+            for (size_t i = 0; i < free_.size(); ++i) {
+                const size_t c = free_[i].capacity;
+                if (c >= records && (best == free_.size() || c < free_[best].capacity)) best = i;
+                if (smallest == free_.size() || c < free_[smallest].capacity) smallest = i;
+            }
+            if (best != free_.size()) {
+                Lease found(this, std::move(free_[best].buf), free_[best].capacity);
+                free_.erase(free_.begin() + static_cast<std::ptrdiff_t>(best));
+                return found;
+            }
+            if (refused_) return Lease();
+            if (made_ >= policy_.max_buffers || (bytes_ + bytes > policy_.max_bytes && made_ >= 3)) {
+                // A pool whose buffers were sized by small first bunches (warm-up, tests) must not stay too small for production bunches:
+                // the smallest FREE buffer goes and one of the needed size takes its place.  With none free every buffer is out.
+                if (free_.empty()) {
+                    if (policy_.all_out_notice && !noticed_) {
+                        noticed_ = true;
+                        std::fprintf(stderr, policy_.all_out_notice, made_, records);
+                    }
+                    return Lease();
+                }
+                const size_t gone = free_[smallest].capacity * sizeof(T);
+                if (bytes_ - gone + bytes > policy_.max_bytes && made_ - 1 >= 3) return Lease();     // (over the byte budget even so)
+                retired = std::move(free_[smallest].buf);
+                free_.erase(free_.begin() + static_cast<std::ptrdiff_t>(smallest));
+                bytes_ -= gone;
+                --made_;
+            }
+            ++made_;
+            bytes_ += bytes;
+        }
+        // (outside the lock: giving memory back to the host and page-locking more take milliseconds)
+        DeviceGuard on_device(device);
+        retired.reset();
+        PinnedBuffer<T> fresh;
+        if (!fresh.try_alloc(new_capacity)) {
+            std::lock_guard<std::mutex> lk(mutex_);
+            --made_;
+            bytes_ -= bytes;
+            refused_ = true;
+            return Lease();
+        }
+        return Lease(this, std::move(fresh), new_capacity);
     }
-    ~DeviceGuard() { if (previous_ >= 0) (void)hipSetDevice(previous_); }
-    DeviceGuard(const DeviceGuard &) = delete;
-    DeviceGuard &operator=(const DeviceGuard &) = delete;
+    // frees the free buffers and starts over (the converter's teardown, with every lease back and the device current)
+    void reset()
+    {
+        std::lock_guard<std::mutex> lk(mutex_);
+        free_.clear();
+        made_ = 0; bytes_ = 0; refused_ = false; noticed_ = false;
+    }
+
 private:
-    int previous_ = -1;
+    void give(PinnedBuffer<T> buf, size_t capacity)
+    {
+        std::lock_guard<std::mutex> lk(mutex_);
+        free_.push_back(Entry{std::move(buf), capacity});
+    }
+    struct Entry { PinnedBuffer<T> buf; size_t capacity; };
+    const PinnedPoolPolicy policy_;
+    std::mutex mutex_;
+    std::vector<Entry> free_;
+    int made_ = 0;
+    size_t bytes_ = 0;
+    bool refused_ = false;          // the host would not page-lock more
+    bool noticed_ = false;
+};
+
+// What a launch is tuned by ("kernel" ... "result_min_records" of clsimhip_set_tuning) and what Initialize() derives from it.
+// A launch works on ONE copy of this, taken under the converter's tuning mutex.
+struct LaunchTuning {
+    int kernel = 0;                              // "kernel": 0 automatic (by bunch size), 1 pooled, 2 classic for every bunch size
+    long long tuned_pool_min_steps = -1;         // "pool_min_steps": -1 = the default threshold
+    long long tuned_pool_max_steps = -1;         // "pool_max_steps": -1 = what the pending entries' step index can address; only ever lowers it
+    int pool_ring = 0, k_pop = 0;                // pooled kernel: ring entries per wave, lanes serviced at once, 0 = automatic
+    int k_new = 0, slices = 0;                   // creation threshold; slices per step, 0 = automatic
+    int k_search = 0;                            // lanes parked before a wave searches for DOMs, 0 = automatic
+    int k_wait = -1, k_aim = -1;                 // -1 = automatic (pooled kernel only: the classic and keep kernels have them as
+                                                 // constants); 0 is honoured: never wait / never ask
+    int grid = 0;
+    bool generic_only = false;                   // "generic_kernels"
+    size_t result_min_records = 65536;           // (tests make the result buffers grow with small bunches)
+    // derived by Converter::apply_kernel_choice() once initialized
+    bool derived = false;
+    bool use_pool = false;                       // pooled kernel allowed
+    size_t pool_min_steps = 0;                   // ... for bunches of at least this many steps
+    size_t pool_max_steps = 0;                   // ... and at most this many (pool_kernel_max_steps(): the pending entries' 23-bit step index)
+    // the pooled kernel pays from ~3 steps per unit slot on: a launch that owns 1/k of the chip reaches that with 1/k of the steps
+    bool pooled_for(size_t n_steps, int concurrent_launches) const
+    {
+        return use_pool && n_steps <= pool_max_steps && n_steps * static_cast<size_t>(concurrent_launches) >= pool_min_steps;
+    }
 };
 
 class Converter {
@@ -202,59 +332,37 @@ public:
     // SetDevice (OpenCL.cxx:1322-1331): the HIP device ordinal, before Initialize()
     void set_device(int device);
     int device() const { return device_; }
-    // the pooled kernel pays from ~3 steps per unit slot on: a launch that owns 1/k of the chip reaches that with 1/k of the steps
-    bool pooled_for(size_t n_steps) const
-    {
-        need_init();
-        std::lock_guard<std::mutex> lk(tuning_mutex_);
-        return use_pool_ && n_steps <= pool_max_steps_ && n_steps * static_cast<size_t>(concurrent_launches_) >= pool_min_steps_;
-    }
+    bool pooled_for(size_t n_steps) const { need_init(); return tuning_snapshot().pooled_for(n_steps, concurrent_launches_); }
     // clsimhip_set_tuning / clsimhip_get_tuning (include/clsimhip.h has the table of keys): launcher parameters, any time between
     // launches; the three table keys before Compile().  The DEFAULT build reads no tuning from the environment.
     void set_tuning(const std::string &key, long long value);
     long long get_tuning(const std::string &key) const;
     void set_concurrent_device_launches(int k);
     int concurrent_device_launches() const { return concurrent_launches_; }
-    bool uses_pooled_kernel() const { need_init(); std::lock_guard<std::mutex> lk(tuning_mutex_); return use_pool_ && pool_min_steps_ == 0; }     // for every bunch size
+    bool uses_pooled_kernel() const { need_init(); const LaunchTuning t = tuning_snapshot(); return t.use_pool && t.pool_min_steps == 0; }     // for every bunch size
 
 private:
+    using StepPool = PinnedPool<clsimhip_step>;
+    using PhotonPool = PinnedPool<clsimhip_photon>;
+    using McpePool = PinnedPool<clsimhip_mcpe>;
     // A bunch on its way to the worker: the caller's steps are copied ONCE, in the caller's thread, into a page-locked buffer of the
     // step pool, which the worker uploads from (round 5; before, a vector here and a second copy into the slot's staging buffer on
     // the worker thread -- 8 ms per million steps in front of the first kernel of a run).  With every pool buffer in flight the
     // steps travel in a vector as before.
-    struct StepBuffer { clsimhip_step *p = nullptr; size_t capacity = 0; };
-    // (a pool buffer on loan: whoever drops it -- a job the closed queue refused, a queue destroyed with jobs inside -- returns it)
-    struct StepLease {
-        Converter *owner = nullptr;
-        StepBuffer b;
-        StepLease() = default;
-        StepLease(Converter *o, StepBuffer buf) : owner(o), b(buf) {}
-        StepLease(StepLease &&o) noexcept : owner(o.owner), b(o.b) { o.b = StepBuffer(); }
-        StepLease &operator=(StepLease &&o) noexcept { if (this != &o) { drop(); owner = o.owner; b = o.b; o.b = StepBuffer(); } return *this; }
-        StepLease(const StepLease &) = delete;
-        StepLease &operator=(const StepLease &) = delete;
-        ~StepLease() { drop(); }
-        StepBuffer release() { const StepBuffer r = b; b = StepBuffer(); return r; }
-        void drop() { if (owner && b.p) owner->give_step_buffer(b); b = StepBuffer(); }
-    };
-    struct Job { uint32_t id = 0; size_t n = 0; uint64_t generated = 0; StepLease pinned; std::vector<clsimhip_step> steps; };
+    struct Job { uint32_t id = 0; size_t n = 0; uint64_t generated = 0; StepPool::Lease pinned; std::vector<clsimhip_step> steps; };
     // The photons of a result live in a page-locked buffer of the converter's pool (the download lands there and the
     // caller reads them there until ReleaseResult: no host copy in between), or -- when the pool is exhausted because the
     // caller holds more results than it has buffers -- in a vector of their own.
     struct Result {
         uint32_t id = 0;
-        struct HostFree { void operator()(clsimhip_photon *p) const; };
-        std::unique_ptr<clsimhip_photon, HostFree> pinned;  // pool buffer (returned to the pool by release_result; freed with a result nobody fetched)
-        size_t pinned_capacity = 0;                         // records `pinned` holds
+        PhotonPool::Lease pinned;                           // pool buffer (back to the pool with release_result, or with a result nobody fetched)
         size_t count = 0;
         std::unique_ptr<std::vector<clsimhip_photon>> photons;
         std::unique_ptr<std::vector<float>> histories;     // [photons][history_entries_][4], forward order
         const clsimhip_photon *data() const { return pinned ? pinned.get() : (photons ? photons->data() : nullptr); }
         // with an MCPE generator: the bunch's MCPEs, in a page-locked buffer of the MCPE pool or (pool exhausted) a vector, and --
         // when the result carries no photon record -- a record of its own whose address is the result's handle
-        struct McpeHostFree { void operator()(clsimhip_mcpe *p) const; };
-        std::unique_ptr<clsimhip_mcpe, McpeHostFree> mcpe_pinned;
-        size_t mcpe_pinned_capacity = 0;
+        McpePool::Lease mcpe_pinned;
         size_t mcpe_count = 0;
         std::unique_ptr<std::vector<clsimhip_mcpe>> mcpes;
         std::unique_ptr<clsimhip_photon> handle;
@@ -263,12 +371,13 @@ private:
 
     void guard() const { if (initialized_) throw Error(CLSIMHIP_ERR_STATE, "I3CLSimStepToPhotonConverterHIP already initialized!"); }
     void need_init() const { if (!initialized_) throw Error(CLSIMHIP_ERR_STATE, "I3CLSimStepToPhotonConverterHIP is not initialized!"); }
-    void setup_device_buffers();
+    struct DeviceState;
+    void setup_device_buffers(DeviceState &D);
     void release_device();      // frees every device / pinned allocation, stream and event (idempotent)
     void worker();
     void check_worker() const;  // throws the worker thread's device error, if it has died of one
-    void hip_check(hipError_t e, const char *what) const;
-    KParams launch_params(const void *d_steps, size_t n, size_t rng_offset, void *d_photons, size_t capacity, void *d_hits, hipStream_t stream);
+    KParams launch_params(const LaunchTuning &tuning, const void *d_steps, size_t n, size_t rng_offset, void *d_photons, size_t capacity, void *d_hits,
+                          hipStream_t stream);
 
     int device_;
     std::vector<RandomValueData> generators_;
@@ -286,107 +395,84 @@ private:
     std::shared_ptr<McpeGenerator> mcpe_;       // null: no MCPEs are made (the default)
     bool keep_photons_ = true;
 
-    bool compiled_ = false, initialized_ = false;
+    std::atomic<bool> compiled_{false}, initialized_{false};    // (atomic: set_tuning() reads them from any thread)
     CompiledTables tables_;
 
-    // device state
-    uint32_t *d_tables_ = nullptr;
-    int16_t *d_dom_tx_ = nullptr, *d_dom_ty_ = nullptr;
-    float *d_len_table_ = nullptr;
-    uint32_t *d_prox_map_ = nullptr;
-    uint32_t *d_dom_prox_ = nullptr;
-    uint32_t *d_dom_named_ = nullptr;
-    float *d_dom_centres_ = nullptr;
-    float *d_hist_ring_ = nullptr;           // per resident lane: the last history_entries_ scatter points
-    float *d_dom_tz_ = nullptr;
-    uint64_t *d_rng_x_ = nullptr;
-    uint32_t *d_rng_a_ = nullptr;
+    // The pools come before everything that holds a lease (the device state's slots, the queues, handed_out_): members go in reverse
+    // order, so every lease is back before its pool frees the buffers.
+    // Result buffers are sized by the photons that arrive: a bunch's download lands in a buffer of at least its own record count (a
+    // quarter more, at least "result_min_records", never more than max_output_photons_), which then IS the result until the caller
+    // releases it.  At most six exist at a time.  (Rounds 3-4 kept buffers of max_output_photons_ records each -- 840 MB at a
+    // million work items, six of them.)  The same for MCPEs (16-byte records).
+    PhotonPool result_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
+    McpePool mcpe_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
+    size_t result_capacity(size_t records, size_t min_records) const;
+    // Step buffers (see Job): input queue depth + one per slot + the one being filled, each sized by the bunch it first carried (a
+    // quarter more) and replaced by a larger one when a later bunch needs it, at most 1 GiB in all
+    StepPool step_pool_{PinnedPoolPolicy{8, size_t{1} << 30,
+        "clsimhip: all %d page-locked step buffers are in flight; this bunch of %zu steps is staged through pageable memory\n"}};
+
     // One buffer set per bunch in flight (OpenCL.cxx:296-340 allocates numBuffers = 1 or 2 of each): while
     // the kernel of bunch k+1 runs, the photons of bunch k are downloaded on the copy stream and converted.
+    // (In every struct here events come first: they go before the buffers their work touches.)
     struct Slot {
-        DevStep *d_steps = nullptr;
-        DevPhoton *d_photons = nullptr;
-        uint32_t *d_hit_count = nullptr;
-        float *d_hist_out = nullptr;            // photon histories of the slot's hits (history_entries_ float4 each)
-        float *h_hist = nullptr;
-        clsimhip_step *h_steps = nullptr;       // pinned staging (for a job that came without a pool buffer)
-        StepBuffer step_buffer;                 // the pool buffer the slot's upload reads; goes back to the pool when the slot is used again
-        uint32_t *h_hit_count = nullptr;
-        clsimhip_mcpe *d_mcpes = nullptr;       // with an MCPE generator: max_output_photons_ records, five counters (mcpe.h)
-        uint32_t *d_mcpe_counters = nullptr, *h_mcpe_counters = nullptr;
-        hipEvent_t start = nullptr, stop = nullptr, counted = nullptr, uploaded = nullptr;
+        Event start, stop, counted, uploaded;
+        DeviceBuffer<DevStep> d_steps;
+        DeviceBuffer<DevPhoton> d_photons;
+        DeviceBuffer<uint32_t> d_hit_count;
+        DeviceBuffer<float> d_hist_out;         // photon histories of the slot's hits (history_entries_ float4 each)
+        PinnedBuffer<float> h_hist;
+        PinnedBuffer<clsimhip_step> h_steps;    // pinned staging (for a job that came without a pool buffer)
+        StepPool::Lease step_lease;             // the pool buffer the slot's upload reads; goes back to the pool when the slot is used again
+        PinnedBuffer<uint32_t> h_hit_count;
+        DeviceBuffer<clsimhip_mcpe> d_mcpes;    // with an MCPE generator: max_output_photons_ records, five counters (mcpe.h)
+        DeviceBuffer<uint32_t> d_mcpe_counters;
+        PinnedBuffer<uint32_t> h_mcpe_counters;
         uint32_t id = 0;
         uint64_t generated = 0;
+        size_t result_min_records = 0;          // of the tuning the bunch was launched with
     };
-    Slot slots_[2];
+    // Everything Initialize() creates on the device.  Assigning an empty one releases it all, in declaration order: events and
+    // streams before the buffers.
+    struct DeviceState {
+        std::vector<std::pair<Event, Event>> pending_events, free_events;      // device-resident path: event pairs on the caller's stream (ev_mutex_)
+        Stream stream;                          // upload + kernels (bunches serialise here: they share the RNG streams)
+        Stream copy_stream;                     // photon download
+        Stream upload_stream;                   // step upload of the next bunch while the previous kernel runs
+        Slot slots[2];
+        DeviceBuffer<uint32_t> tables;
+        DeviceBuffer<int16_t> dom_tx, dom_ty;
+        DeviceBuffer<float> dom_tz;
+        DeviceBuffer<float> len_table;
+        DeviceBuffer<uint32_t> prox_map, dom_prox, dom_named;
+        DeviceBuffer<float> dom_centres;
+        DeviceBuffer<float> hist_ring;          // per resident lane: the last history_entries_ scatter points
+        DeviceBuffer<uint64_t> rng_x;
+        DeviceBuffer<uint32_t> rng_a;
+        // index -> ID tables on the device (host path: converted by assemble_hits_kernel); null when an ID does not fit the record
+        DeviceBuffer<int16_t> id_strings;
+        DeviceBuffer<uint16_t> id_doms;
+        DeviceBuffer<uint32_t> id_dom_start;
+        DeviceBuffer<WorkRecord> work;          // per step: work record (kparams.h), rebuilt by every launch
+        DeviceBuffer<uint32_t> queue;           // ring of step-queue heads, one per launch in flight
+        uint32_t *last_queue = nullptr;
+#ifdef CLSIMHIP_CENSUS
+        DeviceBuffer<unsigned long long> census;
+#endif
+    };
+    DeviceState dev_;
     int num_slots_ = 1;
-    // Page-locked result buffers, sized by the photons that arrive: a bunch's download lands in a buffer of at least its own record
-    // count (a quarter more, at least min_result_records_, never more than max_output_photons_), which then IS the result until the
-    // caller releases it.  At most kResultBuffers exist at a time; a free one that is too small is given back to the host for a
-    // larger one.  (Rounds 3-4 kept buffers of max_output_photons_ records each -- 840 MB at a million work items, six of them.)
-    struct PinnedBuffer { clsimhip_photon *p = nullptr; size_t capacity = 0; };
-    static constexpr int kResultBuffers = 6;
-    size_t min_result_records_ = 65536;                 // ("result_min_records": tests make the buffers grow with small bunches)
-    std::vector<PinnedBuffer> free_result_buffers_;
-    int result_buffers_made_ = 0;
-    bool pinning_refused_ = false;                      // the host would not page-lock more: results are copied out from then on
-    std::mutex result_pool_mutex_;
-    PinnedBuffer take_result_buffer(size_t records);    // {nullptr, 0} when every buffer is with the caller (or the host refuses)
-    // the same for MCPEs (16-byte records), at most kResultBuffers as well
-    struct McpeBuffer { clsimhip_mcpe *p = nullptr; size_t capacity = 0; };
-    std::vector<McpeBuffer> free_mcpe_buffers_;
-    int mcpe_buffers_made_ = 0;
-    bool mcpe_pinning_refused_ = false;
-    McpeBuffer take_mcpe_buffer(size_t records);
-    template <class Buffer> Buffer take_pinned_buffer(std::vector<Buffer> &free_buffers, int &made, bool &refused, size_t records);    // the one routine behind both
-    // Page-locked step buffers (see Job): input queue depth + one per slot + the one being filled, each sized by the bunch it first
-    // carried (a quarter more) and replaced by a larger one when a later bunch needs it, at most kStepPoolBytes in all
-    static constexpr int kStepBuffers = 8;
-    static constexpr size_t kStepPoolBytes = size_t{1} << 30;
-    std::vector<StepBuffer> free_step_buffers_;
-    int step_buffers_made_ = 0;
-    size_t step_pool_bytes_ = 0;
-    bool step_pinning_refused_ = false;
-    bool step_fallback_logged_ = false;                 // the pageable fallback is reported once (like finish() does for result buffers)
-    std::mutex step_pool_mutex_;
-    StepBuffer take_step_buffer(size_t steps);
-    void give_step_buffer(StepBuffer b);
-    // index -> ID tables on the device (host path: converted by assemble_hits_kernel); null when an ID does not fit the record
-    int16_t *d_id_strings_ = nullptr;
-    uint16_t *d_id_doms_ = nullptr;
-    uint32_t *d_id_dom_start_ = nullptr;
     void submit(Slot &s, Job &job);
     void finish(Slot &s, std::chrono::steady_clock::time_point &last_done, bool &first);
-    WorkRecord *d_work_ = nullptr;           // per step: work record (kparams.h), rebuilt by every launch
-    uint32_t *d_queue_ = nullptr;            // ring of step-queue heads, one per launch in flight
     uint32_t queue_slot_ = 0;
     int concurrent_launches_ = 1;            // device path: launches the caller keeps in flight side by side (chip share of each)
-    uint32_t *last_queue_ = nullptr;
-#ifdef CLSIMHIP_CENSUS
-    unsigned long long *d_census_ = nullptr;
-#endif
-    int k_wait_ = -1, k_aim_ = -1;               // -1 = automatic; "k_wait", "k_aim" (pooled kernel only: the classic and keep
-                                                 // kernels have them as constants); 0 is honoured: never wait / never ask
-    int k_search_ = 0;                           // lanes parked before a wave searches for DOMs, 0 = automatic ("k_search")
-    int k_new_ = 0, k_slices_ = 0;               // creation threshold; slices per step, 0 = automatic ("k_new", "slices")
-    int k_pop_ = 0, pool_ready_ = 0;             // pooled kernel: lanes serviced at once, ring entries per wave, 0 = automatic ("k_pop", "pool_ring")
-    bool use_pool_ = false;                      // pooled kernel allowed (derived by apply_kernel_choice())
-    size_t pool_min_steps_ = 0;                  // ... for bunches of at least this many steps
-    size_t pool_max_steps_ = 0;                  // ... and at most this many (pool_kernel_max_steps(): the pending entries' 23-bit step index)
-    int kernel_choice_ = 0;                      // "kernel": 0 automatic (by bunch size), 1 pooled, 2 classic for every bunch size
-    long long tuned_pool_min_steps_ = -1;        // "pool_min_steps": -1 = the default threshold
-    long long tuned_pool_max_steps_ = -1;        // "pool_max_steps": -1 = what the pending entries' step index can address; only ever lowers it
-    int grid_ = 0;                               // "grid"
-    bool generic_only_ = false;                  // "generic_kernels"
+    LaunchTuning tuning_;
     TableTuning table_tuning_;
     bool pool_possible_ = false;                 // set by Initialize(): no photon histories, the table image leaves the pools their LDS
-    void apply_kernel_choice();
-    mutable std::mutex tuning_mutex_;            // the tuning members above: set_tuning() against the launches that read them
-    hipError_t launch(const KParams &P, hipStream_t stream) const;
-    hipStream_t stream_ = nullptr;           // upload + kernels (bunches serialise here: they share the RNG streams)
-    hipStream_t copy_stream_ = nullptr;      // photon download
-    hipStream_t upload_stream_ = nullptr;    // step upload of the next bunch while the previous kernel runs
-    hipEvent_t ev_start_ = nullptr, ev_stop_ = nullptr;
+    void apply_kernel_choice();                  // (the caller holds tuning_mutex_)
+    mutable std::mutex tuning_mutex_;            // tuning_, table_tuning_, pool_possible_: set_tuning() against the launches that read them
+    LaunchTuning tuning_snapshot() const { std::lock_guard<std::mutex> lk(tuning_mutex_); return tuning_; }
+    hipError_t launch(const KParams &P, const LaunchTuning &tuning, hipStream_t stream) const;
 
     // worker + queues (in: capacity 5 like queueToOpenCL_, OpenCL.cxx:77)
     std::unique_ptr<BoundedQueue<Job>> in_queue_;
@@ -403,9 +489,8 @@ private:
     mutable std::mutex stats_mutex_;
     uint64_t total_device_ns_ = 0, total_host_ns_ = 0, num_kernel_calls_ = 0, photons_generated_ = 0, photons_at_doms_ = 0;
 
-    // device-resident path: event pairs on the caller's stream
+    // device-resident path: the event pairs of DeviceState
     std::mutex ev_mutex_;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending_events_, free_events_;
     double dev_total_ms_ = 0;
     uint64_t dev_launches_ = 0;
 };

@@ -23,54 +23,40 @@ extern "C" const char *clsimhip_last_error(const clsimhip_converter *c);
 
 namespace clsimhip {
 
-namespace {
-void hip_must(hipError_t e, const char *what)
-{
-    if (e != hipSuccess) throw Error(CLSIMHIP_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
-}
-} // namespace
-
 StepProducer::~StepProducer()
 {
-    if (!stream_ && !d_steps_ && !h_steps_) return;
-    int previous = -1;
-    if (hipGetDevice(&previous) != hipSuccess) previous = -1;
-    (void)hipSetDevice(device_);
-    if (stream_) { (void)hipStreamSynchronize(stream_); (void)hipStreamDestroy(stream_); }
-    (void)hipFree(d_steps_); (void)hipFree(d_req_); (void)hipFree(d_first_);
-    if (h_steps_) (void)hipHostFree(h_steps_);
-    if (h_req_) (void)hipHostFree(h_req_);
-    if (h_first_) (void)hipHostFree(h_first_);
-    if (previous >= 0) (void)hipSetDevice(previous);
+    if (!r_.stream && !r_.d_steps && !r_.h_steps) return;
+    DeviceGuard on_device(device_, std::nothrow);
+    if (r_.stream) (void)hipStreamSynchronize(r_.stream.get());
+    r_ = Resources();
 }
 
 // stream and buffers (the caller has selected the device)
 void StepProducer::ensure(size_t steps, size_t requests)
 {
-    if (!stream_) {
+    if (!r_.stream) {
         int least = 0, greatest = 0;
-        hip_must(hipDeviceGetStreamPriorityRange(&least, &greatest), "stream priorities");
-        hip_must(hipStreamCreateWithPriority(&stream_, hipStreamNonBlocking, greatest), "step producer stream");
+        hip_check(hipDeviceGetStreamPriorityRange(&least, &greatest), "stream priorities");
+        r_.stream.create_with_priority(greatest, "step producer stream");
     }
     if (steps > cap_steps_) {
         const size_t cap = steps + steps / 4;
-        (void)hipFree(d_steps_); d_steps_ = nullptr;
-        if (h_steps_) { (void)hipHostFree(h_steps_); h_steps_ = nullptr; }
+        r_.d_steps.reset();
+        r_.h_steps.reset();
         cap_steps_ = 0;
-        hip_must(hipMalloc(&d_steps_, cap * sizeof(clsimhip_step)), "step buffer");
-        hip_must(hipHostMalloc(reinterpret_cast<void **>(&h_steps_), cap * sizeof(clsimhip_step), hipHostMallocDefault), "pinned step buffer");
+        r_.d_steps.alloc(cap, "step buffer");
+        r_.h_steps.alloc(cap, "pinned step buffer");
         cap_steps_ = cap;
     }
     if (requests > cap_req_) {
         const size_t cap = 2 * requests;
-        (void)hipFree(d_req_); (void)hipFree(d_first_); d_req_ = d_first_ = nullptr;
-        if (h_req_) { (void)hipHostFree(h_req_); h_req_ = nullptr; }
-        if (h_first_) { (void)hipHostFree(h_first_); h_first_ = nullptr; }
+        r_.d_req.reset(); r_.d_first.reset();
+        r_.h_req.reset(); r_.h_first.reset();
         cap_req_ = 0;
-        hip_must(hipMalloc(&d_req_, cap * sizeof(clsimhip_step_request)), "request buffer");
-        hip_must(hipMalloc(&d_first_, cap * sizeof(uint64_t)), "offset buffer");
-        hip_must(hipHostMalloc(&h_req_, cap * sizeof(clsimhip_step_request), hipHostMallocDefault), "pinned request buffer");
-        hip_must(hipHostMalloc(&h_first_, cap * sizeof(uint64_t), hipHostMallocDefault), "pinned offset buffer");
+        r_.d_req.alloc(cap, "request buffer");
+        r_.d_first.alloc(cap, "offset buffer");
+        r_.h_req.alloc(cap, "pinned request buffer");
+        r_.h_first.alloc(cap, "pinned offset buffer");
         cap_req_ = cap;
     }
 }
@@ -108,15 +94,16 @@ const clsimhip_step *StepProducer::generate(const std::vector<clsimhip_step_requ
     if (device_ < 0 || device_ >= count) throw Error(CLSIMHIP_ERR_DEVICE, "device ordinal out of range");
     DeviceGuard on_device(device_);
     ensure(padded, n + 1);
-    if (n) std::memcpy(h_req_, requests.data(), n * sizeof(clsimhip_step_request));
-    std::memcpy(h_first_, first.data(), (n + 1) * sizeof(uint64_t));
-    if (n) hip_must(hipMemcpyAsync(d_req_, h_req_, n * sizeof(clsimhip_step_request), hipMemcpyHostToDevice, stream_), "upload requests");
-    hip_must(hipMemcpyAsync(d_first_, h_first_, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream_), "upload offsets");
-    hip_must(launch_generate_steps(static_cast<const clsimhip_step_request *>(d_req_), static_cast<const uint64_t *>(d_first_),
-                                   static_cast<uint32_t>(n ? n : 1), real, padded, seed, d_steps_, stream_), "step generation kernel launch");
-    hip_must(hipMemcpyAsync(h_steps_, d_steps_, padded * sizeof(clsimhip_step), hipMemcpyDeviceToHost, stream_), "download steps");
-    hip_must(hipStreamSynchronize(stream_), "step generation");
-    return h_steps_;
+    const hipStream_t stream = r_.stream.get();
+    if (n) std::memcpy(r_.h_req.get(), requests.data(), n * sizeof(clsimhip_step_request));
+    std::memcpy(r_.h_first.get(), first.data(), (n + 1) * sizeof(uint64_t));
+    if (n) hip_check(hipMemcpyAsync(r_.d_req.get(), r_.h_req.get(), n * sizeof(clsimhip_step_request), hipMemcpyHostToDevice, stream), "upload requests");
+    hip_check(hipMemcpyAsync(r_.d_first.get(), r_.h_first.get(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream), "upload offsets");
+    hip_check(launch_generate_steps(r_.d_req.get(), r_.d_first.get(), static_cast<uint32_t>(n ? n : 1), real, padded, seed, r_.d_steps.get(), stream),
+              "step generation kernel launch");
+    hip_check(hipMemcpyAsync(r_.h_steps.get(), r_.d_steps.get(), padded * sizeof(clsimhip_step), hipMemcpyDeviceToHost, stream), "download steps");
+    hip_check(hipStreamSynchronize(stream), "step generation");
+    return r_.h_steps.get();
 }
 
 Feeder::Feeder(const PPCConverter *ppc, int device, uint64_t seed, size_t max_bunch_size, size_t granularity, size_t queue_depth)

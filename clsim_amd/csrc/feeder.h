@@ -14,7 +14,7 @@ namespace clsimhip {
 
 // The feeder's GPU step producer: one HIP stream of its own (non-blocking, highest priority: a propagator on the same GPU
 // runs persistent grids, and a launch that has to share the chip with one gets slivers of it), device and page-locked host
-// buffers that only grow.  (The stateless clsimhip_generate_steps allocates and frees device memory per call; hipFree
+// buffers that only grow.  (The stateless clsimhip_generate_steps allocates and frees device memory per call; freeing
 // waits for the whole device, i.e. for the propagation kernel that happens to be running.)
 class StepProducer {
 public:
@@ -32,10 +32,16 @@ public:
 private:
     void ensure(size_t steps, size_t requests);
     int device_;
-    hipStream_t stream_ = nullptr;
-    void *d_steps_ = nullptr, *d_req_ = nullptr, *d_first_ = nullptr;
-    clsimhip_step *h_steps_ = nullptr;
-    void *h_req_ = nullptr, *h_first_ = nullptr;
+    struct Resources {              // (the stream goes before the buffers its work touches)
+        Stream stream;
+        DeviceBuffer<clsimhip_step> d_steps;
+        DeviceBuffer<clsimhip_step_request> d_req;
+        DeviceBuffer<uint64_t> d_first;
+        PinnedBuffer<clsimhip_step> h_steps;
+        PinnedBuffer<clsimhip_step_request> h_req;
+        PinnedBuffer<uint64_t> h_first;
+    };
+    Resources r_;
     size_t cap_steps_ = 0, cap_req_ = 0;
 };
 

@@ -79,11 +79,11 @@ McpeGenerator::McpeGenerator(const std::vector<FunctionData> &classes, size_t n_
 
 McpeGenerator::~McpeGenerator()
 {
+    // (mcpe.h is shared with the kernel and keeps plain pointers in its images: they are handed to owners here to be freed)
     for (auto &kv : images_) {
-        int previous = -1;
-        if (hipGetDevice(&previous) != hipSuccess) previous = -1;
-        if (hipSetDevice(kv.first) == hipSuccess) { (void)hipFree(kv.second.values); (void)hipFree(kv.second.dom_table); }
-        if (previous >= 0) (void)hipSetDevice(previous);
+        DeviceGuard on_device(kv.first, std::nothrow);
+        DeviceBuffer<double> values(kv.second.values);
+        DeviceBuffer<uint64_t> dom_table(kv.second.dom_table);
     }
 }
 
@@ -118,19 +118,11 @@ McpeGenerator::DeviceImage McpeGenerator::image_on(int device)
     std::lock_guard<std::mutex> lk(device_mutex_);
     auto it = images_.find(device);
     if (it != images_.end()) return it->second;
-    DeviceImage im;
-    auto check = [](hipError_t e, const char *what) {
-        if (e != hipSuccess) throw Error(CLSIMHIP_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
-    };
-    try {
-        check(hipMalloc(reinterpret_cast<void **>(&im.values), values_.size() * sizeof(double)), "MCPE acceptance tables");
-        check(hipMalloc(reinterpret_cast<void **>(&im.dom_table), dom_table_.size() * sizeof(uint64_t)), "MCPE DOM classes");
-        check(hipMemcpy(im.values, values_.data(), values_.size() * sizeof(double), hipMemcpyHostToDevice), "MCPE acceptance tables");
-        check(hipMemcpy(im.dom_table, dom_table_.data(), dom_table_.size() * sizeof(uint64_t), hipMemcpyHostToDevice), "MCPE DOM classes");
-    } catch (...) {
-        (void)hipFree(im.values); (void)hipFree(im.dom_table);
-        throw;
-    }
+    DeviceBuffer<double> values(values_.size(), "MCPE acceptance tables");
+    DeviceBuffer<uint64_t> dom_table(dom_table_.size(), "MCPE DOM classes");
+    hip_check(hipMemcpy(values.get(), values_.data(), values_.size() * sizeof(double), hipMemcpyHostToDevice), "MCPE acceptance tables");
+    hip_check(hipMemcpy(dom_table.get(), dom_table_.data(), dom_table_.size() * sizeof(uint64_t), hipMemcpyHostToDevice), "MCPE DOM classes");
+    const DeviceImage im{values.release(), dom_table.release()};
     images_[device] = im;
     return im;
 }

@@ -27,11 +27,6 @@ double AxisData::bin_edge(unsigned i) const
     return transform(imin + i * istep);
 }
 
-void Tabulator::hip_check(hipError_t e, const char *what) const
-{
-    if (e != hipSuccess) throw Error(CLSIMHIP_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
-}
-
 // GetMinimumRefractiveIndex (StepToTableConverter.cxx:96-120), as written: the scan point is wmin + i*(wmax-wmin)
 static std::pair<double, double> minimum_refractive_index(const MediumData &m)
 {
@@ -196,38 +191,34 @@ Tabulator::Tabulator(int device, int axes_kind, std::vector<AxisData> axes, bool
         throw Error(CLSIMHIP_ERR_DEVICE, "no HIP device available (the tabulator has no CPU fallback)");
     if (device_ < 0 || device_ >= count) throw Error(CLSIMHIP_ERR_ARGUMENT, "device ordinal out of range");
     DeviceGuard on_device(device_);
-    hip_check(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking), "hipStreamCreate");
-    hip_check(hipEventCreate(&ev_start_), "hipEventCreate");
-    hip_check(hipEventCreate(&ev_stop_), "hipEventCreate");
-    auto upload = [&](void **dst, const void *src, size_t bytes, const char *what) {
-        hip_check(hipMalloc(dst, std::max<size_t>(bytes, 16)), what);
-        if (bytes) hip_check(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice), what);
+    stream_.create("hipStreamCreate");
+    ev_start_.create("hipEventCreate");
+    ev_stop_.create("hipEventCreate");
+    auto upload = [&](auto &dst, const auto *src, size_t count, const char *what) {
+        dst.alloc(count, what);
+        if (count) hip_check(hipMemcpy(dst.get(), src, count * sizeof(*src), hipMemcpyHostToDevice), what);
     };
-    upload(reinterpret_cast<void **>(&d_tables_), tables_.lds_image.data(), tables_.lds_image.size() * 4, "tables");
-    upload(reinterpret_cast<void **>(&d_len_table_), tables_.len_table.data(), tables_.len_table.size() * 4, "length tables");
-    upload(reinterpret_cast<void **>(&d_rng_x_), x, streams * 8, "rng x");
-    upload(reinterpret_cast<void **>(&d_rng_a_), a, streams * 4, "rng a");
-    hip_check(hipMalloc(reinterpret_cast<void **>(&d_bins_), n_device_bins_ * sizeof(double)), "table bins");
-    hip_check(hipMemset(d_bins_, 0, n_device_bins_ * sizeof(double)), "table bins");
+    upload(d_tables_, tables_.lds_image.data(), tables_.lds_image.size(), "tables");
+    upload(d_len_table_, tables_.len_table.data(), tables_.len_table.size(), "length tables");
+    upload(d_rng_x_, x, streams, "rng x");
+    upload(d_rng_a_, a, streams, "rng a");
+    d_bins_.alloc(n_device_bins_, "table bins");
+    hip_check(hipMemset(d_bins_.get(), 0, n_device_bins_ * sizeof(double)), "table bins");
     if (squared_) {
-        hip_check(hipMalloc(reinterpret_cast<void **>(&d_sq_bins_), n_device_bins_ * sizeof(double)), "squared weights");
-        hip_check(hipMemset(d_sq_bins_, 0, n_device_bins_ * sizeof(double)), "squared weights");
+        d_sq_bins_.alloc(n_device_bins_, "squared weights");
+        hip_check(hipMemset(d_sq_bins_.get(), 0, n_device_bins_ * sizeof(double)), "squared weights");
     }
-    hip_check(hipMalloc(reinterpret_cast<void **>(&d_steps_), streams * sizeof(DevStep)), "steps");
-    hip_check(hipMalloc(reinterpret_cast<void **>(&d_queue_), static_cast<size_t>(kQueueWords) * kQueueSlots * sizeof(uint32_t)), "step queue");
-    hip_check(hipMalloc(reinterpret_cast<void **>(&d_work_), streams * sizeof(WorkRecord)), "work records");
-    hip_check(hipHostMalloc(reinterpret_cast<void **>(&h_steps_), streams * sizeof(clsimhip_step), hipHostMallocDefault), "pinned steps");
+    d_steps_.alloc(streams, "steps");
+    d_queue_.alloc(static_cast<size_t>(kQueueWords) * kQueueSlots, "step queue");
+    d_work_.alloc(streams, "work records");
+    h_steps_.alloc(streams, "pinned steps");
 }
 
+// (the members free themselves, with the table maker's device current)
 Tabulator::~Tabulator()
 {
     (void)hipSetDevice(device_);
-    if (stream_) { (void)hipStreamSynchronize(stream_); (void)hipStreamDestroy(stream_); }
-    if (ev_start_) (void)hipEventDestroy(ev_start_);
-    if (ev_stop_) (void)hipEventDestroy(ev_stop_);
-    (void)hipFree(d_tables_); (void)hipFree(d_len_table_); (void)hipFree(d_bins_); (void)hipFree(d_sq_bins_);
-    (void)hipFree(d_rng_x_); (void)hipFree(d_rng_a_); (void)hipFree(d_steps_); (void)hipFree(d_queue_); (void)hipFree(d_work_);
-    if (h_steps_) (void)hipHostFree(h_steps_);
+    if (stream_) (void)hipStreamSynchronize(stream_.get());
 }
 
 // EnqueueSteps (StepToTableConverter.cxx:272-285) + one pass of FetchSteps (:399-460) without the entry buffers
@@ -239,10 +230,10 @@ void Tabulator::enqueue_steps(const clsimhip_step *steps, size_t n, const double
     std::lock_guard<std::mutex> lk(mutex_);
     DeviceGuard on_device(device_);
     // the previous bunch still reads the pinned staging buffer and the slice counters
-    hip_check(hipStreamSynchronize(stream_), "previous bunch");
+    hip_check(hipStreamSynchronize(stream_.get()), "previous bunch");
     if (pending_event_) {
         float ms = 0.f;
-        hip_check(hipEventElapsedTime(&ms, ev_start_, ev_stop_), "event time");
+        hip_check(hipEventElapsedTime(&ms, ev_start_.get(), ev_stop_.get()), "event time");
         device_ms_ += ms;
         pending_event_ = false;
     }
@@ -250,23 +241,23 @@ void Tabulator::enqueue_steps(const clsimhip_step *steps, size_t n, const double
         num_photons_ += steps[i].num_photons;
         sum_of_photon_weights_ += static_cast<double>(steps[i].num_photons) * static_cast<double>(steps[i].weight);
     }
-    std::memcpy(h_steps_, steps, n * sizeof(clsimhip_step));
-    hip_check(hipMemcpyAsync(d_steps_, h_steps_, n * sizeof(DevStep), hipMemcpyHostToDevice, stream_), "upload steps");
+    std::memcpy(h_steps_.get(), steps, n * sizeof(clsimhip_step));
+    hip_check(hipMemcpyAsync(d_steps_.get(), h_steps_.get(), n * sizeof(DevStep), hipMemcpyHostToDevice, stream_.get()), "upload steps");
     KParams P = tables_.params;
-    P.tables = d_tables_;
-    P.len_table = d_len_table_;
-    P.steps = d_steps_;
+    P.tables = d_tables_.get();
+    P.len_table = d_len_table_.get();
+    P.steps = d_steps_.get();
     P.n_steps = static_cast<uint32_t>(n);
-    P.rng_x = d_rng_x_;
-    P.rng_a = d_rng_a_;
-    P.queue = d_queue_ + static_cast<size_t>(kQueueWords) * (queue_slot_++ % kQueueSlots);
-    hip_check(hipMemsetAsync(P.queue, 0, kQueueWords * sizeof(uint32_t), stream_), "reset step queue");
+    P.rng_x = d_rng_x_.get();
+    P.rng_a = d_rng_a_.get();
+    P.queue = d_queue_.get() + static_cast<size_t>(kQueueWords) * (queue_slot_++ % kQueueSlots);
+    hip_check(hipMemsetAsync(P.queue, 0, kQueueWords * sizeof(uint32_t), stream_.get()), "reset step queue");
     P.k_new = 12;
     P.k_search = 1;
     P.slices = 0;
-    P.work = d_work_;
-    P.tab_bins = d_bins_;
-    P.tab_sq_bins = d_sq_bins_;
+    P.work = d_work_.get();
+    P.tab_bins = d_bins_.get();
+    P.tab_sq_bins = d_sq_bins_.get();
     {   // I3CLSimReferenceParticle (StepToTableConverter.cxx:64-93)
         const double dx = ref[4], dy = ref[5], dz = ref[6];
         const double perpz = std::hypot(dx, dy);
@@ -280,13 +271,13 @@ void Tabulator::enqueue_steps(const clsimhip_step *steps, size_t n, const double
         const double v[12] = {ref[0], ref[1], ref[2], ref[3], dx, dy, dz, 0., px, py, pz, 0.};
         for (int k = 0; k < 12; ++k) P.tab_ref[k] = static_cast<float>(v[k]);
     }
-    hip_check(hipEventRecord(ev_start_, stream_), "event");
+    hip_check(hipEventRecord(ev_start_.get(), stream_.get()), "event");
     if (!standard_sampler_) P.tab_std = 0u;          // ("standard_sampler" 0: the generic sampler also for the standard table; tests compare the two)
     KVariant variant = tables_.variant;
     variant.tab_fast = fast_kernels_;
     variant.grid = grid_;
-    hip_check(launch_tab_kernel(P, variant, stream_), "tabulation kernel launch");
-    hip_check(hipEventRecord(ev_stop_, stream_), "event");
+    hip_check(launch_tab_kernel(P, variant, stream_.get()), "tabulation kernel launch");
+    hip_check(hipEventRecord(ev_stop_.get(), stream_.get()), "event");
     pending_event_ = true;
     ++launches_;
 }
@@ -305,10 +296,10 @@ void Tabulator::finish()
 {
     std::lock_guard<std::mutex> lk(mutex_);
     DeviceGuard on_device(device_);
-    hip_check(hipStreamSynchronize(stream_), "tabulation kernel");
+    hip_check(hipStreamSynchronize(stream_.get()), "tabulation kernel");
     if (pending_event_) {
         float ms = 0.f;
-        hip_check(hipEventElapsedTime(&ms, ev_start_, ev_stop_), "event time");
+        hip_check(hipEventElapsedTime(&ms, ev_start_.get(), ev_stop_.get()), "event time");
         device_ms_ += ms;
         pending_event_ = false;
     }
@@ -336,12 +327,12 @@ void Tabulator::bin_content_double(double *out, size_t n, bool squared)
     finish();
     std::lock_guard<std::mutex> lk(mutex_);
     if (!tiled_) {
-        hip_check(hipMemcpy(out, squared ? d_sq_bins_ : d_bins_, n * sizeof(double), hipMemcpyDeviceToHost), "download table");
+        hip_check(hipMemcpy(out, squared ? d_sq_bins_.get() : d_bins_.get(), n * sizeof(double), hipMemcpyDeviceToHost), "download table");
         return;
     }
     // the device's tiled order -> the reference's (sample_bin in prop_kernel.hip forms the same index)
     std::vector<double> device(n_device_bins_);
-    hip_check(hipMemcpy(device.data(), squared ? d_sq_bins_ : d_bins_, n_device_bins_ * sizeof(double), hipMemcpyDeviceToHost), "download table");
+    hip_check(hipMemcpy(device.data(), squared ? d_sq_bins_.get() : d_bins_.get(), n_device_bins_ * sizeof(double), hipMemcpyDeviceToHost), "download table");
     size_t at = 0;
     for (size_t b0 = 0; b0 < shape_[0]; ++b0)
         for (size_t b1 = 0; b1 < shape_[1]; ++b1)
@@ -385,7 +376,7 @@ void Tabulator::get_rng_state(uint64_t *x, size_t count)
     if (!x || count > streams_) throw Error(CLSIMHIP_ERR_ARGUMENT, "bad rng state request");
     finish();
     std::lock_guard<std::mutex> lk(mutex_);
-    hip_check(hipMemcpy(x, d_rng_x_, count * sizeof(uint64_t), hipMemcpyDeviceToHost), "download rng state");
+    hip_check(hipMemcpy(x, d_rng_x_.get(), count * sizeof(uint64_t), hipMemcpyDeviceToHost), "download rng state");
 }
 
 long Tabulator::get_table(const std::string &name, double *out, size_t cap) const

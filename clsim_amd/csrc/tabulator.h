@@ -53,7 +53,6 @@ public:
     long get_table(const std::string &name, double *out, size_t cap) const;
 
 private:
-    void hip_check(hipError_t e, const char *what) const;
     int device_;
     int axes_kind_;
     std::vector<AxisData> axes_;
@@ -71,17 +70,18 @@ private:
     double spectral_bias_factor_ = 1.;  // spectralBiasFactor_ (StepToTableConverter.cxx:142-152)
     CompiledTables tables_;
     size_t streams_;
-    uint32_t *d_tables_ = nullptr;
-    float *d_len_table_ = nullptr;
-    double *d_bins_ = nullptr, *d_sq_bins_ = nullptr;
-    uint64_t *d_rng_x_ = nullptr;
-    uint32_t *d_rng_a_ = nullptr;
-    DevStep *d_steps_ = nullptr;
-    uint32_t *d_queue_ = nullptr;
-    WorkRecord *d_work_ = nullptr;
-    clsimhip_step *h_steps_ = nullptr;
-    hipStream_t stream_ = nullptr;
-    hipEvent_t ev_start_ = nullptr, ev_stop_ = nullptr;
+    // (destroyed in reverse order: events and stream before the buffers their work touches)
+    DeviceBuffer<uint32_t> d_tables_;
+    DeviceBuffer<float> d_len_table_;
+    DeviceBuffer<double> d_bins_, d_sq_bins_;
+    DeviceBuffer<uint64_t> d_rng_x_;
+    DeviceBuffer<uint32_t> d_rng_a_;
+    DeviceBuffer<DevStep> d_steps_;
+    DeviceBuffer<uint32_t> d_queue_;
+    DeviceBuffer<WorkRecord> d_work_;
+    PinnedBuffer<clsimhip_step> h_steps_;
+    Stream stream_;
+    Event ev_start_, ev_stop_;
     uint32_t queue_slot_ = 0;
     std::mutex mutex_;
     uint64_t num_photons_ = 0, launches_ = 0;

@@ -243,3 +243,61 @@ def test_tuning_goes_through_the_c_abi_and_not_through_the_environment():
     assert err.value.code == _lib.ERR_STATE
     conv.SetTuning("k_new", 3)
     assert conv.GetTuning("k_new") == 3
+
+
+def header_tuning_table():
+    """(key, lo, hi, shapes_tables) for every row of the table in front of clsimhip_set_tuning; hi is None where the header gives
+    no upper end ("-1 | >= 0", ">= 1")."""
+    txt = open(os.path.join(ROOT, "include", "clsimhip.h")).read()
+    block = txt[re.search(r"key +values +meaning \(default\)", txt).start():txt.index("int clsimhip_set_tuning(")]
+    number = lambda t: 2 ** int(t.strip()[2:]) if t.strip().startswith("2^") else int(t)
+    rows, shapes_tables = [], False
+    for line in block.splitlines():
+        if "shape tables of Compile()" in line:
+            shapes_tables = True
+        m = re.match(r'\s*\*\s+"(\w+)"\s+(.{16})', line)
+        if not m:
+            continue
+        values = m.group(2).strip()
+        if "..." in values:
+            lo, hi = (number(t) for t in values.split("..."))
+        else:
+            parts = [t.strip() for t in values.split("|")]
+            lo = min(number(t.lstrip(">= ")) for t in parts)
+            hi = None if any(t.startswith(">=") for t in parts) else max(number(t) for t in parts)
+        rows.append((m.group(1), lo, hi, shapes_tables))
+    return rows
+
+
+def test_every_tuning_key_of_the_header_is_set_read_and_range_checked():
+    """Every row of the header's table: what is set is what is read, one below the lower end and one above the upper end are
+    CLSIMHIP_ERR_ARGUMENT (rows whose upper end the header leaves open are only checked below), so is a key the table does not
+    have, and the three keys that shape Compile()'s tables are CLSIMHIP_ERR_STATE afterwards.  Host side only."""
+    table = header_tuning_table()
+    assert len(table) == 16 and sum(1 for row in table if row[3]) == 3, table
+    conv = CV.I3CLSimStepToPhotonConverterHIP(0)
+    for key, lo, hi, _ in table:
+        for value in (lo, hi if hi is not None else lo + 12345, lo + 1):
+            conv.SetTuning(key, value)
+            assert conv.GetTuning(key) == value, (key, value)
+        for value in (lo - 1,) + ((hi + 1,) if hi is not None else ()):
+            with pytest.raises(CV.I3CLSimStepToPhotonConverter_exception) as err:
+                conv.SetTuning(key, value)
+            assert err.value.code == _lib.ERR_ARGUMENT, (key, value)
+            assert conv.GetTuning(key) == lo + 1, (key, value)
+    for call in (lambda: conv.SetTuning("no_such_key", 1), lambda: conv.GetTuning("no_such_key")):
+        with pytest.raises(CV.I3CLSimStepToPhotonConverter_exception) as err:
+            call()
+        assert err.value.code == _lib.ERR_ARGUMENT
+    conv = common.product_converter(common.config("c1"), 512, initialize=False)
+    conv.Compile()
+    for key, lo, hi, shapes_tables in table:
+        if shapes_tables:
+            before = conv.GetTuning(key)
+            with pytest.raises(CV.I3CLSimStepToPhotonConverter_exception) as err:
+                conv.SetTuning(key, lo)
+            assert err.value.code == _lib.ERR_STATE, key
+            assert conv.GetTuning(key) == before, key
+        else:
+            conv.SetTuning(key, lo)
+            assert conv.GetTuning(key) == lo, key
