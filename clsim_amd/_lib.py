@@ -107,6 +107,7 @@ SYMBOLS = [
     "clsimhip_eval_math", "clsimhip_check_math_exhaustive", "clsimhip_version",
     "clsimhip_eval_device_function", "clsimhip_eval_device_random", "clsimhip_get_option",
     "clsimhip_set_tuning", "clsimhip_get_tuning", "clsimhip_tabulator_set_tuning",
+    "clsimhip_get_last_launch", "clsimhip_tabulator_get_last_launch",
     "clsimhip_count_generated_steps", "clsimhip_generate_steps_device", "clsimhip_generate_steps",
     "clsimhip_ppc_create", "clsimhip_ppc_destroy", "clsimhip_ppc_photons_per_meter", "clsimhip_ppc_enqueue", "clsimhip_shower_parameters",
     "clsimhip_flasher_correction_factor", "clsimhip_flasher_enqueue",
@@ -126,6 +127,19 @@ SYMBOLS = [
     "clsimhip_mcpe_generator_create", "clsimhip_mcpe_generator_destroy", "clsimhip_mcpe_generator_last_error",
     "clsimhip_mcpe_convert_host", "clsimhip_mcpe_convert_device", "clsimhip_set_mcpe_generator", "clsimhip_get_result_mcpes",
 ]
+
+# clsimhip_get_last_launch: CLSIMHIP_FAMILY_* and CLSIMHIP_LENGTHS_* by name
+KERNEL_FAMILIES = ("classic", "keep", "pool", "pool_keep", "tab4", "tab5")
+LENGTHS_KINDS = ("constant", "icecube", "table")
+
+
+def launched_dict(out):
+    """{family, lengths, tilt, aniso, flasher, fast} from the six ints of clsimhip_get_last_launch; None before the first launch"""
+    v = [int(x) for x in out]
+    if v[0] < 0:
+        return None
+    return dict(family=KERNEL_FAMILIES[v[0]], lengths=LENGTHS_KINDS[v[1]], tilt=bool(v[2]), aniso=bool(v[3]), flasher=bool(v[4]), fast=bool(v[5]))
+
 
 _lib = None
 
@@ -219,6 +233,8 @@ def load():
         "clsimhip_set_tuning": (i32, [vp, C.c_char_p, C.c_longlong]),
         "clsimhip_get_tuning": (i32, [vp, C.c_char_p, C.POINTER(C.c_longlong)]),
         "clsimhip_tabulator_set_tuning": (i32, [vp, C.c_char_p, C.c_longlong]),
+        "clsimhip_get_last_launch": (i32, [vp, C.POINTER(C.c_int)]),
+        "clsimhip_tabulator_get_last_launch": (i32, [vp, C.POINTER(C.c_int)]),
         "clsimhip_eval_device_function": (i32, [vp, i32, i32, i32, vp, sz, vp]),
         "clsimhip_eval_device_random": (i32, [vp, i32, i32, i32, vp, vp, sz, sz, vp]),
         "clsimhip_check_math_exhaustive": (i32, [i32, i32, i32, i32, vp, sz]),

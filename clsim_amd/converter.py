@@ -645,6 +645,14 @@ class I3CLSimStepToPhotonConverterHIP:
         self._call("clsimhip_uses_pooled_kernel", C.byref(v))
         return bool(v.value)
 
+    def GetLastLaunch(self):
+        """clsimhip_get_last_launch: the kernel instantiation the last launch dispatched to, as a dict
+        {family: 'classic' | 'keep' | 'pool' | 'pool_keep', lengths: 'constant' | 'icecube' | 'table', tilt, aniso, flasher, fast};
+        None before the first launch"""
+        out = (C.c_int * 6)()
+        self._call("clsimhip_get_last_launch", out)
+        return _lib.launched_dict(out)
+
     # ---- the reference's tester classes (private/test/I3CLSim*Tester): single functions evaluated on the device ----
     EVAL = {"lengths": 0, "refraction": 1, "wavelength_bias": 2, "tilt": 3, "abs_len_scaling": 4, "pre_scatter_transform": 5,
             "post_scatter_transform": 6}

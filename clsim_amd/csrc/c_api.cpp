@@ -570,6 +570,14 @@ long clsimhip_get_table(const clsimhip_converter *c, const char *name, double *o
     const int rc = guarded_const(c, [&] { need(c, "converter"); need(name, "name"); n = c->impl.get_table(name, out, cap); });
     return rc == CLSIMHIP_OK ? n : rc;
 }
+static void copy_launched(const clsimhip::KLaunched &l, int out[6])
+{
+    out[0] = l.family; out[1] = l.lengths; out[2] = l.tilt; out[3] = l.aniso; out[4] = l.flasher; out[5] = l.fast;
+}
+int clsimhip_get_last_launch(const clsimhip_converter *c, int out[6])
+{
+    return guarded_const(c, [&] { need(c, "converter"); need(out, "out"); copy_launched(c->impl.last_launch(), out); });
+}
 int clsimhip_get_rng_state(clsimhip_converter *c, uint64_t *x_out, size_t count)
 {
     return guarded(c, [&] { need(c, "converter"); c->impl.get_rng_state(x_out, count); });
@@ -917,6 +925,10 @@ int clsimhip_tabulator_write_fits_file(clsimhip_tabulator *t, const char *path, 
         }
         t->impl->write_fits_file(path, header);
     });
+}
+int clsimhip_tabulator_get_last_launch(const clsimhip_tabulator *t, int out[6])
+{
+    return guarded_tab(const_cast<clsimhip_tabulator *>(t), [&] { need(t, "tabulator"); need(out, "out"); copy_launched(t->impl->last_launch(), out); });
 }
 long clsimhip_tabulator_get_table(const clsimhip_tabulator *t, const char *name, double *out, size_t cap)
 {

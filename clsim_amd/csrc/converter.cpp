@@ -33,8 +33,15 @@ hipError_t Converter::launch(const KParams &P, const LaunchTuning &tuning, hipSt
     const bool pooled = tuning.pooled_for(P.n_steps, concurrent_launches_);
     v.grid = tuning.grid;
     v.generic_only = tuning.generic_only;
-    if (v.keep_detected) return pooled ? launch_pool_keep_kernel(P, v, stream) : launch_keep_kernel(P, v, stream);
-    return pooled ? launch_pool_kernel(P, v, stream) : launch_prop_kernel(P, v, stream);
+    KLaunched launched;
+    v.launched = &launched;
+    const hipError_t err = v.keep_detected ? (pooled ? launch_pool_keep_kernel(P, v, stream) : launch_keep_kernel(P, v, stream))
+                                           : (pooled ? launch_pool_kernel(P, v, stream) : launch_prop_kernel(P, v, stream));
+    if (launched.family >= 0) {              // (an empty bunch launches nothing: the report of the last real launch stays)
+        std::lock_guard<std::mutex> lk(launched_mutex_);
+        launched_ = launched;
+    }
+    return err;
 }
 
 // ---- tuning (include/clsimhip.h: clsimhip_set_tuning) -----------------------------------------------------------------
@@ -952,6 +959,12 @@ long Converter::get_table(const std::string &name, double *out, size_t cap) cons
         const size_t n = tables_.dom_prox.size();
         if (out) for (size_t i = 0; i < std::min(n, cap); ++i) out[i] = tables_.dom_prox[i];
         return static_cast<long>(n);
+    }
+    if (name == "kernel_variant") {                     // the struct the launchers dispatch on, as Compile() derived it
+        const KVariant &v = tables_.variant;
+        const double values[6] = {double(v.lengths), v.tilt ? 1. : 0., v.aniso ? 1. : 0., v.flasher ? 1. : 0., v.keep_detected ? 1. : 0., v.fast ? 1. : 0.};
+        if (out) std::memcpy(out, values, std::min<size_t>(6, cap) * sizeof(double));
+        return 6;
     }
     if (name == "dom_named") {
         const size_t n = tables_.dom_named.size();

@@ -340,6 +340,8 @@ public:
     void set_concurrent_device_launches(int k);
     int concurrent_device_launches() const { return concurrent_launches_; }
     bool uses_pooled_kernel() const { need_init(); const LaunchTuning t = tuning_snapshot(); return t.use_pool && t.pool_min_steps == 0; }     // for every bunch size
+    // clsimhip_get_last_launch: the instantiation the last launch (worker or device path) dispatched to, every field -1 before the first
+    KLaunched last_launch() const { std::lock_guard<std::mutex> lk(launched_mutex_); return launched_; }
 
 private:
     using StepPool = PinnedPool<clsimhip_step>;
@@ -473,6 +475,8 @@ private:
     mutable std::mutex tuning_mutex_;            // tuning_, table_tuning_, pool_possible_: set_tuning() against the launches that read them
     LaunchTuning tuning_snapshot() const { std::lock_guard<std::mutex> lk(tuning_mutex_); return tuning_; }
     hipError_t launch(const KParams &P, const LaunchTuning &tuning, hipStream_t stream) const;
+    mutable std::mutex launched_mutex_;          // launched_: the worker (or a device-path caller) writes, any thread reads
+    mutable KLaunched launched_;
 
     // worker + queues (in: capacity 5 like queueToOpenCL_, OpenCL.cxx:77)
     std::unique_ptr<BoundedQueue<Job>> in_queue_;

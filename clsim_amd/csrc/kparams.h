@@ -219,6 +219,12 @@ struct KParams {
     uint32_t k_packed;
 };
 
+// The instantiation a launch dispatched to: the template arguments of launch_variant / launch_pool_variant, written by them on the host
+// where the kernel is launched (clsimhip_get_last_launch; family: CLSIMHIP_FAMILY_*, -1 before the first launch)
+struct KLaunched {
+    int family = -1, lengths = -1, tilt = -1, aniso = -1, flasher = -1, fast = -1;
+};
+
 // kernel variants (the reference's #ifdef switches, OpenCL.cxx:390-442 and the
 // generated *_IS_CONSTANT / NO_FLASHER hints)
 struct KVariant {
@@ -234,6 +240,7 @@ struct KVariant {
     int grid = 0;                   // workgroups of the propagation launch ("grid")
     bool generic_only = false;      // the generic instantiation also where Compile() found every proof ("generic_kernels")
     bool tab_fast = false;          // table maker: the FAST instantiation (measured slower, prop_kernel.hip: launch_tab_kernel) ("fast_kernels")
+    KLaunched *launched = nullptr;  // where the launcher reports the instantiation it took (host memory of the caller; may be null)
 };
 
 } // namespace clsimhip

@@ -1367,10 +1367,13 @@ hipError_t launch_assemble_hits(const KParams &P, bool flasher, int device, hipS
 #endif
 
 template <int MED, bool TILT, bool ANISO, bool FLASHER, int TAB, bool FAST = false>
-static hipError_t launch_variant(const KParams &Pin, hipStream_t stream, int grid_wanted = 0)
+static hipError_t launch_variant(const KParams &Pin, hipStream_t stream, int grid_wanted = 0, KLaunched *launched = nullptr)
 {
     KParams P = Pin;
     constexpr bool TABULATE = (TAB == 1) || (TAB == 2);
+    // (clsimhip_get_last_launch: the template arguments of THIS function, not what the dispatcher meant to choose)
+    if (launched) *launched = KLaunched{TAB == 0 ? CLSIMHIP_FAMILY_CLASSIC : TAB == 3 ? CLSIMHIP_FAMILY_KEEP : TAB == 1 ? CLSIMHIP_FAMILY_TAB4 : CLSIMHIP_FAMILY_TAB5,
+                                        MED, TILT, ANISO, FLASHER, FAST};
     // (without STOP_PHOTONS_ON_DETECTION: one more word per lane and 64 strings, find_collisions_keep's string mask)
     const size_t lds_bytes = TABULATE ? (size_t)(((P.table_words + 16 + 3) & ~3u) + kWavesPerBlock * kTabWaveWords) * 4
                                       : (size_t)(P.table_words + kWavesPerBlock * kStageRecords * kStubWords + kBlock
@@ -1470,7 +1473,7 @@ hipError_t launch_prop_kernel(const KParams &P, const KVariant &v, hipStream_t s
     const int key = 8 * v.lengths + (v.tilt ? 4 : 0) + (v.aniso ? 2 : 0) + (v.flasher ? 1 : 0);
     const bool fast = v.fast && P.history_n == 0 && !v.generic_only;
     switch (key) {
-#define CASE(k, a, b, c, d) case k: return fast ? launch_variant<a, b, c, d, 0, true>(P, stream, v.grid) : launch_variant<a, b, c, d, 0, false>(P, stream, v.grid);
+#define CASE(k, a, b, c, d) case k: return fast ? launch_variant<a, b, c, d, 0, true>(P, stream, v.grid, v.launched) : launch_variant<a, b, c, d, 0, false>(P, stream, v.grid, v.launched);
 #define CASES(m) \
     CASE(8 * m + 0, m, false, false, false) CASE(8 * m + 1, m, false, false, true) \
     CASE(8 * m + 2, m, false, true, false)  CASE(8 * m + 3, m, false, true, true)  \
@@ -1494,7 +1497,7 @@ hipError_t launch_keep_kernel(const KParams &P, const KVariant &v, hipStream_t s
     const int key = 8 * v.lengths + (v.tilt ? 4 : 0) + (v.aniso ? 2 : 0) + (v.flasher ? 1 : 0);
     const bool fast = v.fast && P.history_n == 0 && !v.generic_only;       // (as launch_prop_kernel)
     switch (key) {
-#define CASE(k, a, b, c, d) case k: return fast ? launch_variant<a, b, c, d, 3, true>(P, stream, v.grid) : launch_variant<a, b, c, d, 3, false>(P, stream, v.grid);
+#define CASE(k, a, b, c, d) case k: return fast ? launch_variant<a, b, c, d, 3, true>(P, stream, v.grid, v.launched) : launch_variant<a, b, c, d, 3, false>(P, stream, v.grid, v.launched);
 #define CASES(m) \
     CASE(8 * m + 0, m, false, false, false) CASE(8 * m + 1, m, false, false, true) \
     CASE(8 * m + 2, m, false, true, false)  CASE(8 * m + 3, m, false, true, true)  \
@@ -1524,8 +1527,8 @@ hipError_t launch_tab_kernel(const KParams &P, const KVariant &v, hipStream_t st
     // allocation costs.  So the generic instantiation runs; clsimhip_tabulator_set_tuning("fast_kernels", 1) selects the other one.
     const bool fast = v.fast && v.tab_fast;
     switch (key) {
-#define CASE(k, m, t, a) case k: return (P.tab_ndim > 4) ? (fast ? launch_variant<m, t, a, true, 2, true>(P, stream, v.grid) : launch_variant<m, t, a, true, 2, false>(P, stream, v.grid)) \
-                                                         : (fast ? launch_variant<m, t, a, true, 1, true>(P, stream, v.grid) : launch_variant<m, t, a, true, 1, false>(P, stream, v.grid));
+#define CASE(k, m, t, a) case k: return (P.tab_ndim > 4) ? (fast ? launch_variant<m, t, a, true, 2, true>(P, stream, v.grid, v.launched) : launch_variant<m, t, a, true, 2, false>(P, stream, v.grid, v.launched)) \
+                                                         : (fast ? launch_variant<m, t, a, true, 1, true>(P, stream, v.grid, v.launched) : launch_variant<m, t, a, true, 1, false>(P, stream, v.grid, v.launched));
 #define CASES(m) CASE(4 * m + 0, m, false, false) CASE(4 * m + 1, m, false, true) CASE(4 * m + 2, m, true, false) CASE(4 * m + 3, m, true, true)
     CASES(CLSIMHIP_LENGTHS_CONSTANT) CASES(CLSIMHIP_LENGTHS_ICECUBE) CASES(CLSIMHIP_LENGTHS_TABLE)
 #undef CASES

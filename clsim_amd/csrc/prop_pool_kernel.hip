@@ -574,9 +574,10 @@ hipError_t launch_scan_steps(const KParams &P, hipStream_t stream);
 hipError_t launch_assemble_hits(const KParams &P, bool flasher, int device, hipStream_t stream);
 
 template <int MED, bool TILT, bool ANISO, bool FLASHER, bool FAST, bool KEEP>
-static hipError_t launch_pool_variant(const KParams &Pin, hipStream_t stream, int grid_wanted = 0)
+static hipError_t launch_pool_variant(const KParams &Pin, hipStream_t stream, int grid_wanted = 0, KLaunched *launched = nullptr)
 {
     KParams P = Pin;
+    if (launched) *launched = KLaunched{KEEP ? CLSIMHIP_FAMILY_POOL_KEEP : CLSIMHIP_FAMILY_POOL, MED, TILT, ANISO, FLASHER, FAST};      // (as launch_variant)
     int dev = 0;
     {
         const hipError_t e = hipGetDevice(&dev);
@@ -704,7 +705,7 @@ hipError_t CLSIMHIP_POOL_LAUNCHER(const KParams &P, const KVariant &v, hipStream
     // clsimhip_set_tuning("generic_kernels", 1): the generic instantiation also where Compile() found every proof (tests compare the two)
     const bool fast = v.fast && !v.generic_only;
     switch (key) {
-#define CASE(k, a, b, c, d) case k: return fast ? launch_pool_variant<a, b, c, d, true, CLSIMHIP_POOL_KEEP>(P, stream, v.grid) : launch_pool_variant<a, b, c, d, false, CLSIMHIP_POOL_KEEP>(P, stream, v.grid);
+#define CASE(k, a, b, c, d) case k: return fast ? launch_pool_variant<a, b, c, d, true, CLSIMHIP_POOL_KEEP>(P, stream, v.grid, v.launched) : launch_pool_variant<a, b, c, d, false, CLSIMHIP_POOL_KEEP>(P, stream, v.grid, v.launched);
 #define CASES(m) \
     CASE(8 * m + 0, m, false, false, false) CASE(8 * m + 1, m, false, false, true) \
     CASE(8 * m + 2, m, false, true, false)  CASE(8 * m + 3, m, false, true, true)  \

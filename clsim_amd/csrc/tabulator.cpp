@@ -276,7 +276,13 @@ void Tabulator::enqueue_steps(const clsimhip_step *steps, size_t n, const double
     KVariant variant = tables_.variant;
     variant.tab_fast = fast_kernels_;
     variant.grid = grid_;
+    KLaunched launched;
+    variant.launched = &launched;
     hip_check(launch_tab_kernel(P, variant, stream_.get()), "tabulation kernel launch");
+    if (launched.family >= 0) {
+        std::lock_guard<std::mutex> lk(launched_mutex_);
+        launched_ = launched;
+    }
     hip_check(hipEventRecord(ev_stop_.get(), stream_.get()), "event");
     pending_event_ = true;
     ++launches_;
@@ -381,6 +387,12 @@ void Tabulator::get_rng_state(uint64_t *x, size_t count)
 
 long Tabulator::get_table(const std::string &name, double *out, size_t cap) const
 {
+    if (name == "kernel_variant") {                     // (as Converter::get_table; the fifth entry is the number of axes here)
+        const KVariant &v = tables_.variant;
+        const double values[6] = {double(v.lengths), v.tilt ? 1. : 0., v.aniso ? 1. : 0., v.flasher ? 1. : 0., double(shape_.size()), v.fast ? 1. : 0.};
+        if (out) std::memcpy(out, values, std::min<size_t>(6, cap) * sizeof(double));
+        return 6;
+    }
     auto it = tables_.named.find(name);
     if (it == tables_.named.end()) throw Error(CLSIMHIP_ERR_ARGUMENT, "no table named " + name);
     const size_t n = it->second.size();

@@ -51,6 +51,8 @@ public:
     double spectral_bias_factor() const { return spectral_bias_factor_; }
     void get_rng_state(uint64_t *x, size_t count);
     long get_table(const std::string &name, double *out, size_t cap) const;
+    // clsimhip_tabulator_get_last_launch: the instantiation the last launch dispatched to, every field -1 before the first
+    KLaunched last_launch() const { std::lock_guard<std::mutex> lk(launched_mutex_); return launched_; }
 
 private:
     int device_;
@@ -87,6 +89,8 @@ private:
     uint64_t num_photons_ = 0, launches_ = 0;
     double sum_of_photon_weights_ = 0, device_ms_ = 0;
     bool pending_event_ = false;
+    mutable std::mutex launched_mutex_;
+    KLaunched launched_;
 };
 
 } // namespace clsimhip

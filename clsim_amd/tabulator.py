@@ -120,6 +120,12 @@ class I3CLSimStepToTableConverterHIP:
         """clsimhip_tabulator_set_tuning: "fast_kernels" 0 | 1, "grid" (no result depends on either)"""
         self._call("clsimhip_tabulator_set_tuning", key.encode(), int(value))
 
+    def GetLastLaunch(self):
+        """clsimhip_tabulator_get_last_launch: as the converter's GetLastLaunch, family 'tab4' | 'tab5'; None before the first launch"""
+        out = (C.c_int * 6)()
+        self._call("clsimhip_tabulator_get_last_launch", out)
+        return _lib.launched_dict(out)
+
     def Finish(self):
         self._call("clsimhip_tabulator_finish")
 

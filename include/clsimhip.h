@@ -383,8 +383,23 @@ int clsimhip_gather_hits(clsimhip_comm *comm, const void *d_photons, const void 
  * (clsimhip_uses_pooled_kernel then reports 1 / 0), CLSIMHIP_POOL_MIN_STEPS moves the threshold. */
 int clsimhip_kernel_for_bunch(const clsimhip_converter *c, size_t n_steps, int *out);
 int clsimhip_uses_pooled_kernel(const clsimhip_converter *c, int *out);
+/* Which of the compiled kernel instantiations the LAST launch of this converter dispatched to.  The launchers choose among
+ * (lengths kind, tilt, anisotropy, flasher) x (generic, FAST) per kernel family; the report is written where the kernel is
+ * launched, from that launch's own template arguments, so a test can assert that it ran the instantiation it meant to run.
+ * out = {family (CLSIMHIP_FAMILY_*), lengths kind (CLSIMHIP_LENGTHS_*), tilt, anisotropy, flasher, FAST}, the last four 0 | 1;
+ * every entry is -1 before the first launch.  Read-only; a launch in flight on another thread may or may not be seen yet. */
+#define CLSIMHIP_FAMILY_CLASSIC 0   /* one photon per lane, STOP_PHOTONS_ON_DETECTION          */
+#define CLSIMHIP_FAMILY_KEEP 1      /* one photon per lane, without STOP_PHOTONS_ON_DETECTION  */
+#define CLSIMHIP_FAMILY_POOL 2      /* per-wave photon pools, STOP_PHOTONS_ON_DETECTION        */
+#define CLSIMHIP_FAMILY_POOL_KEEP 3 /* per-wave photon pools, without it                       */
+#define CLSIMHIP_FAMILY_TAB4 4      /* table maker, 4 axes                                     */
+#define CLSIMHIP_FAMILY_TAB5 5      /* table maker, 5 axes (impact angle)                      */
+int clsimhip_get_last_launch(const clsimhip_converter *c, int out[6]);
 /* copies the compiled table `name` (e.g. "geoStringPosX", "aDust400") converted to
- * double into out[0..cap); returns the entry count or a negative status */
+ * double into out[0..cap); returns the entry count or a negative status.
+ * "kernel_variant" (after Compile, no GPU needed): the key the launchers dispatch on, as Compile() derived it from the
+ * configuration -- {lengths kind, tilt, anisotropy, flasher, without STOP_PHOTONS_ON_DETECTION, FAST proofs complete}; the
+ * table maker's fifth entry is its number of axes. */
 long clsimhip_get_table(const clsimhip_converter *c, const char *name, double *out, size_t cap);
 /* current RNG state words (after the bunches run so far) */
 int clsimhip_get_rng_state(clsimhip_converter *c, uint64_t *x_out, size_t count);
@@ -707,6 +722,8 @@ int clsimhip_tabulator_write_fits_file(clsimhip_tabulator *t, const char *path, 
                                        const int64_t *int_values, const double *double_values, size_t n_keys);
 int clsimhip_tabulator_get_rng_state(clsimhip_tabulator *t, uint64_t *x, size_t count);
 long clsimhip_tabulator_get_table(const clsimhip_tabulator *t, const char *name, double *out, size_t cap);
+/* the instantiation of the table maker's last launch: out as clsimhip_get_last_launch (family TAB4 or TAB5, flasher always 1) */
+int clsimhip_tabulator_get_last_launch(const clsimhip_tabulator *t, int out[6]);
 
 /* ---- MCPE generator: detected photons -> photo-electrons (no device counterpart in the reference) --------------------
  * The stage behind the propagator: I3CLSimPhotonToMCPEConverterForDOMs::Convert (private/clsim/dom/

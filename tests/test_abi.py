@@ -301,3 +301,33 @@ def test_every_tuning_key_of_the_header_is_set_read_and_range_checked():
         else:
             conv.SetTuning(key, lo)
             assert conv.GetTuning(key) == lo, key
+
+
+def test_launch_report_and_dispatch_key_queries():
+    """clsimhip_get_last_launch / clsimhip_tabulator_get_last_launch and the named table "kernel_variant": read-only, argument
+    checked like every other entry, -1 in every field before the first launch, and the dispatch key is readable after Compile()
+    without a GPU (tests/test_kernel_matrix.py asserts it for every key; the launches themselves: tests/test_kernel_matrix_gpu.py)."""
+    lib = _lib.load()
+    out = (C.c_int * 6)(*[7] * 6)
+    assert lib.clsimhip_get_last_launch(None, out) == _lib.ERR_ARGUMENT
+    assert lib.clsimhip_tabulator_get_last_launch(None, out) == _lib.ERR_ARGUMENT
+    assert list(out) == [7] * 6                                     # a refused call writes nothing
+    txt = open(os.path.join(ROOT, "include", "clsimhip.h")).read()
+    families = dict(re.findall(r"#define CLSIMHIP_FAMILY_(\w+) (\d+)", txt))
+    assert [name.lower() for name, _ in sorted(families.items(), key=lambda kv: int(kv[1]))] == list(_lib.KERNEL_FAMILIES)
+    lengths = dict(re.findall(r"#define CLSIMHIP_LENGTHS_(\w+) (\d+)", txt))
+    assert [name.lower() for name, _ in sorted(lengths.items(), key=lambda kv: int(kv[1]))] == list(_lib.LENGTHS_KINDS)
+    conv = common.product_converter(common.config("flasher"), 512, initialize=False, stop_detected=False)
+    assert lib.clsimhip_get_last_launch(conv._h, None) == _lib.ERR_ARGUMENT
+    assert lib.clsimhip_get_last_launch(conv._h, out) == 0 and list(out) == [-1] * 6
+    assert conv.GetLastLaunch() is None
+    with pytest.raises(CV.I3CLSimStepToPhotonConverter_exception) as err:
+        conv.GetTable("kernel_variant")                             # the key is Compile()'s
+    assert err.value.code == _lib.ERR_STATE
+    conv.Compile()
+    # SPICE-Lea, two generators, without STOP_PHOTONS_ON_DETECTION: {icecube, tilt, aniso, flasher, keep, FAST}
+    assert list(conv.GetTable("kernel_variant")) == [1.0, 1.0, 1.0, 1.0, 1.0, conv.GetTable("fast_variant")[0]]
+    assert lib.clsimhip_get_last_launch(conv._h, out) == 0 and list(out) == [-1] * 6          # compiling launches nothing
+    conv = common.product_converter(common.config("c1"), 512, initialize=False)
+    conv.Compile()
+    assert list(conv.GetTable("kernel_variant"))[:5] == [0.0, 0.0, 0.0, 0.0, 0.0]

@@ -164,13 +164,17 @@ def test_standard_table_sampler_matches_the_oracle(kind, ice, step_length, stand
     check_table_against_the_oracle(kind, ice, step_length, squared=False, standard_sampler=standard)
 
 
-def check_table_against_the_oracle(kind, ice, step_length, expect_fast="by medium", fast_kernels=False, squared=True, standard_sampler=None):
+def check_table_against_the_oracle(kind, ice, step_length, expect_fast="by medium", fast_kernels=False, squared=True, standard_sampler=None,
+                                   launch_key=None):
     """prop_kernel<TAB> adds every path sample to its bin with an fp64 atomic; the oracle writes the reference's
     (bin, weight) entries.  Same samples <=> the double precision sums agree to rounding; the float image agrees with
     the reference's in-order float accumulation to float accuracy.  step_length 0.2 m makes most waves exceed the
     sample pool, i.e. exercises the per-lane walk next to the pooled one.  The "5" kinds have the impact-angle axis:
-    two random numbers per sample from the photon's own stream, so the final stream states check the draw count."""
-    cfg = common.config(ice)
+    two random numbers per sample from the photon's own stream, so the final stream states check the draw count.
+    ice: a name for common.config, or a configuration in its form (tests/kernel_matrix.py); fast_kernels: one setting or several --
+    each gets a table maker of its own, checked against the one oracle run; launch_key: the (lengths, tilt, anisotropy) whose
+    instantiation every launch must report (clsimhip_tabulator_get_last_launch)."""
+    cfg = ice if isinstance(ice, dict) else common.config(ice)
     o, p = axes_pair(kind)
     okind = "cylindrical" if kind.startswith("cylindrical") else "spherical"
     fine = step_length != 1.0
@@ -199,6 +203,16 @@ def check_table_against_the_oracle(kind, ice, step_length, expect_fast="by mediu
             np.add.at(bins64, ent["index"][i, :k], ent["weight"][i, :k].astype(np.float64))
             np.add.at(sq64, ent["index"][i, :k], ent["weight"][i, :k].astype(np.float64) ** 2)
             np.add.at(bins32, ent["index"][i, :k], ent["weight"][i, :k])
+    for fast_setting in (fast_kernels if isinstance(fast_kernels, (tuple, list)) else (fast_kernels,)):
+        check_product_table(cfg, kind, okind, o, p, tb, steps, (x, a), xo, ref7, step_length, squared, standard_sampler, fast_setting, expect_fast,
+                            launch_key, bins64, sq64, bins32)
+
+
+def check_product_table(cfg, kind, okind, o, p, tb, steps, streams, xo, ref7, step_length, squared, standard_sampler, fast_kernels, expect_fast,
+                        launch_key, bins64, sq64, bins32):
+    """the product's half of check_table_against_the_oracle: one table maker, two bunches, every comparison"""
+    x, a = streams
+    n = len(steps)
     tab = TB.I3CLSimStepToTableConverterHIP(0, p, squared, cfg["med_p"], DOM_AREA, CV.GetIceCubeDOMAcceptance(),
                                             TB.I3CLSimFunctionPolynomial(ANGULAR), (x, a), stepLength=step_length)
     assert tab.n_bins == tb["n_bins"] and list(tab.shape) == tb["shape"]
@@ -212,7 +226,10 @@ def check_table_against_the_oracle(kind, ice, step_length, expect_fast="by mediu
         with pytest.raises(CV.I3CLSimStepToPhotonConverter_exception):
             tab.SetTuning("no_such_key", 1)
     if expect_fast == "by medium":
-        assert int(tab.GetTable("fast_variant")[0]) == (0 if ice.startswith("photonics") else 1)
+        assert int(tab.GetTable("fast_variant")[0]) == (0 if cfg["name"].startswith("photonics") else 1)
+    elif isinstance(expect_fast, int):
+        assert int(tab.GetTable("fast_variant")[0]) == expect_fast
+    assert tab.GetLastLaunch() is None
     for k in range(len(o)):
         assert np.array_equal(tab.GetBinEdges(k), B.axis_bin_edges(o[k]))
     assert np.array_equal(tab.GetTable("TABULATOR_SCALE"), np.array(tb["scale"], dtype=np.float64))
@@ -221,6 +238,11 @@ def check_table_against_the_oracle(kind, ice, step_length, expect_fast="by mediu
     assert t[0] == tb["n_group"] and t[1] == tb["n_phase"] and t[2] == tb["min_inv_groupvel"] and t[3] == tb["tan_thetac"]
     for bunch in range(2):
         tab.EnqueueSteps(steps, ref7)
+        if launch_key is not None:
+            # the instantiation the launch took: FAST only when asked for AND proven (prop_kernel.hip: launch_tab_kernel)
+            want = dict(family="tab5" if len(o) > 4 else "tab4", lengths=launch_key[0], tilt=launch_key[1], aniso=launch_key[2], flasher=True,
+                        fast=bool(fast_kernels) and int(tab.GetTable("fast_variant")[0]) == 1)
+            assert tab.GetLastLaunch() == want, (tab.GetLastLaunch(), want)
     tab.Finish()
     got = tab.GetBinSums()
     assert bins64.sum() > 100 and (bins64 > 0).sum() > 1000
