@@ -126,6 +126,8 @@ SYMBOLS = [
     "clsimhip_tabulator_write_fits_file",
     "clsimhip_mcpe_generator_create", "clsimhip_mcpe_generator_destroy", "clsimhip_mcpe_generator_last_error",
     "clsimhip_mcpe_convert_host", "clsimhip_mcpe_convert_device", "clsimhip_set_mcpe_generator", "clsimhip_get_result_mcpes",
+    "clsimhip_mcpe_series_host", "clsimhip_mcpe_series_workspace_bytes", "clsimhip_mcpe_series_device", "clsimhip_set_mcpe_series",
+    "clsimhip_enqueue_steps_with_particles", "clsimhip_get_result_mcpe_series",
 ]
 
 # clsimhip_get_last_launch: CLSIMHIP_FAMILY_* and CLSIMHIP_LENGTHS_* by name
@@ -290,6 +292,12 @@ def load():
         "clsimhip_mcpe_convert_device": (i32, [vp, i32, vp, vp, sz, vp, sz, vp, vp]),
         "clsimhip_set_mcpe_generator": (i32, [vp, vp, i32]),
         "clsimhip_get_result_mcpes": (i32, [vp, vp, C.POINTER(vp), C.POINTER(sz)]),
+        "clsimhip_mcpe_series_host": (i32, [vp, vp, sz, vp, sz, vp, sz, vp, vp, C.POINTER(sz), C.POINTER(sz), vp]),
+        "clsimhip_mcpe_series_workspace_bytes": (sz, [sz, sz, sz]),
+        "clsimhip_mcpe_series_device": (i32, [vp, i32, vp, vp, sz, vp, sz, vp, sz, vp, vp, vp, vp, sz, vp]),
+        "clsimhip_set_mcpe_series": (i32, [vp, i32]),
+        "clsimhip_enqueue_steps_with_particles": (i32, [vp, vp, sz, u32, vp, sz, vp, sz]),
+        "clsimhip_get_result_mcpe_series": (i32, [vp, vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(u64)]),
         "clsimhip_tabulator_write_fits_file": (i32, [vp, C.c_char_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double), sz]),
     }
     for name in SYMBOLS:

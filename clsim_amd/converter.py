@@ -326,6 +326,22 @@ class I3CLSimSimpleGeometry:
 # clsimhip_mcpe: I3MCPE(particle, npe = 1, time) with the DOM it belongs to; `id` is the step's / photon's identifier
 MCPE_DTYPE = np.dtype([("id", "<u4"), ("stringID", "<i2"), ("omID", "<u2"), ("time", "<f8")])
 MCPE_CONDITIONS = ("negative_weight", "off_surface", "unknown_dom", "probability_above_one")
+# MCPE series (include/clsimhip.h): one entry of the particle cache, one masked module of one frame, one series of the result
+MCPE_PARTICLE_DTYPE = np.dtype([("id", "<u4"), ("frame", "<u4"), ("timeShift", "<f8")])
+MCPE_MASK_DTYPE = np.dtype([("frame", "<u4"), ("stringID", "<i2"), ("omID", "<u2")])
+MCPE_SERIES_DTYPE = np.dtype([("frame", "<u4"), ("stringID", "<i2"), ("omID", "<u2"), ("first", "<u4"), ("count", "<u4")])
+MCPE_SERIES_COUNTERS = ("unknown_particle", "masked", "unknown_dom")
+
+
+def _series_inputs(particles, masked):
+    """(particles array or None, pointer, n, masked array, pointer, n) as the C ABI takes them; particles=None: no table"""
+    if particles is not None:
+        particles = np.ascontiguousarray(particles, dtype=MCPE_PARTICLE_DTYPE)
+    masked = np.ascontiguousarray(masked if masked is not None else [], dtype=MCPE_MASK_DTYPE)
+    # (an empty table is still a table: it gets an address of its own)
+    keep = np.zeros(1, dtype=MCPE_PARTICLE_DTYPE) if particles is not None and len(particles) == 0 else particles
+    pp = C.c_void_p(keep.ctypes.data) if keep is not None else C.c_void_p()
+    return keep, pp, (len(particles) if particles is not None else 0), masked, C.c_void_p(masked.ctypes.data if len(masked) else None), len(masked)
 
 
 class MCPEGenerator:
@@ -380,12 +396,44 @@ class MCPEGenerator:
         _check(self._lib.clsimhip_mcpe_convert_device(self._h, int(device), C.c_void_p(d_photons), C.c_void_p(d_hit_count), int(capacity),
                                                       C.c_void_p(d_mcpes), int(mcpe_capacity), C.c_void_p(d_counters), C.c_void_p(stream)))
 
+    def MakeSeriesHost(self, mcpes, particles=None, masked=None):
+        """(records, series, counters): the host twin of the MCPE series stage.  mcpes: MCPE_DTYPE; particles: MCPE_PARTICLE_DTYPE,
+        strictly increasing in `id`, or None (every identifier is frame 0 with shift 0); masked: MCPE_MASK_DTYPE or None.  records:
+        the kept MCPEs with shifted times, ascending in (frame, stringID, omID, time key, id); series: MCPE_SERIES_DTYPE, one entry per
+        non-empty (frame, DOM); counters = {name: count} (MCPE_SERIES_COUNTERS)"""
+        mcpes = np.ascontiguousarray(mcpes, dtype=MCPE_DTYPE)
+        keep, pp, n_p, masked, mp, n_m = _series_inputs(particles, masked)
+        out = np.zeros(len(mcpes), dtype=MCPE_DTYPE)
+        series = np.zeros(len(mcpes), dtype=MCPE_SERIES_DTYPE)
+        n_kept, n_series, counters = C.c_size_t(), C.c_size_t(), np.zeros(3, dtype=np.uint64)
+        _check(self._lib.clsimhip_mcpe_series_host(self._h, mcpes.ctypes.data_as(C.c_void_p), len(mcpes), pp, n_p, mp, n_m,
+                                                   out.ctypes.data_as(C.c_void_p), series.ctypes.data_as(C.c_void_p), C.byref(n_kept),
+                                                   C.byref(n_series), counters.ctypes.data_as(C.c_void_p)))
+        return out[:n_kept.value], series[:n_series.value], dict(zip(MCPE_SERIES_COUNTERS, (int(c) for c in counters)))
+
+    @staticmethod
+    def SeriesWorkspaceBytes(capacity, n_particles=0, n_masked=0):
+        return int(_lib.load().clsimhip_mcpe_series_workspace_bytes(int(capacity), int(n_particles), int(n_masked)))
+
+    def MakeSeriesDevice(self, d_mcpes, d_count, capacity, d_out, d_series, d_counts, d_workspace, workspace_bytes, particles=None, masked=None,
+                         device=0, stream=0):
+        """the kernels on device-resident MCPEs (addresses): min(*d_count, capacity) records; d_out / d_series: `capacity` entries,
+        d_counts: five uint32 (kept, series, then MCPE_SERIES_COUNTERS), d_workspace: SeriesWorkspaceBytes(capacity, len(particles),
+        len(masked)) bytes.  particles / masked are host arrays as for MakeSeriesHost."""
+        keep, pp, n_p, masked, mp, n_m = _series_inputs(particles, masked)
+        _check(self._lib.clsimhip_mcpe_series_device(self._h, int(device), C.c_void_p(d_mcpes), C.c_void_p(d_count), int(capacity), pp, n_p, mp, n_m,
+                                                     C.c_void_p(d_out), C.c_void_p(d_series), C.c_void_p(d_counts), C.c_void_p(d_workspace),
+                                                     int(workspace_bytes), C.c_void_p(stream)))
+
 
 class ConversionResult(tuple):
     """What GetConversionResult / GetConversionResultInPlace return: the tuple (identifier, photons[, histories]) / (identifier,
     photons, release), with the bunch's MCPEs (MCPE_DTYPE) as attribute `mcpes` when the converter has an MCPE generator (None
-    otherwise)"""
+    otherwise).  With the MCPE series stage `mcpes` are the sorted records, `series` their series table (MCPE_SERIES_DTYPE) and
+    `masked` the bunch's MASKED count."""
     mcpes = None
+    series = None
+    masked = None
 
 
 class I3CLSimStepToPhotonConverterHIP:
@@ -397,6 +445,7 @@ class I3CLSimStepToPhotonConverterHIP:
         _check(self._lib.clsimhip_create(int(device), C.byref(self._h)))
         self._history_entries = 0
         self._mcpe = None
+        self._series = False
 
     def __del__(self):
         try:
@@ -447,6 +496,11 @@ class I3CLSimStepToPhotonConverterHIP:
         the device (the client module's two switches, frame->photons / frame->hits)"""
         self._call("clsimhip_set_mcpe_generator", generator._h if generator is not None else None, int(bool(keepPhotons)))
         self._mcpe = generator
+    def SetMCPESeries(self, on=True):
+        """the sorting stage behind the MCPE generator: every result's MCPEs come back as per-frame, per-DOM time-sorted series
+        (result attributes `mcpes`, `series`, `masked`).  Before Initialize() only; Compile() refuses it without a generator."""
+        self._call("clsimhip_set_mcpe_series", int(bool(on)))
+        self._series = bool(on)
     def SetWorkgroupSize(self, v): self._call("clsimhip_set_workgroup_size", int(v))
     def SetMaxNumWorkitems(self, v): self._call("clsimhip_set_max_num_workitems", int(v))
 
@@ -468,16 +522,32 @@ class I3CLSimStepToPhotonConverterHIP:
         return bool(self._lib.clsimhip_is_initialized(self._h))
 
     # ---- steady state ----
-    def EnqueueSteps(self, steps, identifier):
+    def EnqueueSteps(self, steps, identifier, particles=None, masked=None):
+        """particles (MCPE_PARTICLE_DTYPE, strictly increasing in `id`) and masked (MCPE_MASK_DTYPE): the bunch's particle table and
+        ignored modules for the MCPE series stage (SetMCPESeries); without them the bunch is one frame, 0, with no shift"""
         if steps is None:
             raise I3CLSimStepToPhotonConverter_exception("Steps pointer is (null)!", _lib.ERR_ARGUMENT)
         steps = np.ascontiguousarray(steps, dtype=STEP_DTYPE)
-        self._call("clsimhip_enqueue_steps", steps.ctypes.data_as(C.c_void_p), len(steps), int(identifier))
+        if particles is None and masked is None:
+            self._call("clsimhip_enqueue_steps", steps.ctypes.data_as(C.c_void_p), len(steps), int(identifier))
+            return
+        keep, pp, n_p, masked, mp, n_m = _series_inputs(particles, masked)
+        self._call("clsimhip_enqueue_steps_with_particles", steps.ctypes.data_as(C.c_void_p), len(steps), int(identifier), pp, n_p, mp, n_m)
 
     def _result_mcpes(self, ptr):
-        """copy of the MCPEs of the result `ptr` belongs to (None without a generator)"""
+        """copy of the MCPEs of the result `ptr` belongs to (None without a generator); with the MCPE series stage the tuple
+        (sorted records, series table, MASKED count)"""
         if self._mcpe is None:
             return None
+        if self._series:
+            mp, mn, sp, sn, masked = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_size_t(), C.c_uint64()
+            self._call("clsimhip_get_result_mcpe_series", ptr, C.byref(mp), C.byref(mn), C.byref(sp), C.byref(sn), C.byref(masked))
+            mcpes, series = np.zeros(mn.value, dtype=MCPE_DTYPE), np.zeros(sn.value, dtype=MCPE_SERIES_DTYPE)
+            if mn.value:
+                C.memmove(mcpes.ctypes.data, mp.value, mn.value * 16)
+            if sn.value:
+                C.memmove(series.ctypes.data, sp.value, sn.value * 16)
+            return mcpes, series, int(masked.value)
         mp, mn = C.c_void_p(), C.c_size_t()
         self._call("clsimhip_get_result_mcpes", ptr, C.byref(mp), C.byref(mn))
         mcpes = np.zeros(mn.value, dtype=MCPE_DTYPE)
@@ -523,7 +593,7 @@ class I3CLSimStepToPhotonConverterHIP:
             if n.value or self._mcpe is not None:
                 self._call("clsimhip_release_result", ptr)
         result = ConversionResult((ident.value, photons, histories) if with_histories else (ident.value, photons))
-        result.mcpes = mcpes
+        self._attach_mcpes(result, mcpes)
         return result
 
     def GetConversionResultInPlace(self):
@@ -548,8 +618,14 @@ class I3CLSimStepToPhotonConverterHIP:
             view = np.frombuffer(buf, dtype=PHOTON_DTYPE)
             view.flags.writeable = False
             result = ConversionResult((ident.value, view, (lambda: self._call("clsimhip_release_result", ptr))))
-        result.mcpes = mcpes
+        self._attach_mcpes(result, mcpes)
         return result
+
+    def _attach_mcpes(self, result, mcpes):
+        if self._series and mcpes is not None:
+            result.mcpes, result.series, result.masked = mcpes
+        else:
+            result.mcpes = mcpes
 
     def _size(self, name):
         v = C.c_size_t()
@@ -693,11 +769,11 @@ def initializeHIP(device, geometry, medium, wavelengthGenerationBias, wavelength
                   enableDoubleBuffering=False, doublePrecision=False, stopDetectedPhotons=True, saveAllPhotons=False,
                   saveAllPhotonsPrescale=0.01, fixedNumberOfAbsorptionLengths=float("nan"), pancakeFactor=1.0,
                   photonHistoryEntries=0, limitWorkgroupSize=0, approximateNumberOfWorkItems=262144,
-                  seed=12345, streams=None, tuning=None, mcpeGenerator=None, keepPhotons=True):
+                  seed=12345, streams=None, tuning=None, mcpeGenerator=None, keepPhotons=True, mcpeSeries=False):
     """Canonical configuration sequence, I3CLSimModuleHelper::initializeOpenCL
     (ModuleHelper.cxx:303-372).  tuning: {key: value} for clsimhip_set_tuning, applied before Compile().
     mcpeGenerator: an MCPEGenerator that turns every bunch's photons into MCPEs on the GPU (result attribute `mcpes`);
-    keepPhotons=False then leaves the photon records on the device."""
+    keepPhotons=False then leaves the photon records on the device; mcpeSeries=True sorts them into per-frame, per-DOM series."""
     conv = I3CLSimStepToPhotonConverterHIP(device)
     for key, value in (tuning or {}).items():
         conv.SetTuning(key, value)
@@ -715,6 +791,8 @@ def initializeHIP(device, geometry, medium, wavelengthGenerationBias, wavelength
     conv.SetPhotonHistoryEntries(photonHistoryEntries)
     if mcpeGenerator is not None:
         conv.SetMCPEGenerator(mcpeGenerator, keepPhotons)
+    if mcpeSeries:
+        conv.SetMCPESeries(True)
     conv.Compile()
     max_wg = conv.GetMaxWorkgroupSize()
     if limitWorkgroupSize:

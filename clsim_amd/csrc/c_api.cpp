@@ -978,4 +978,45 @@ int clsimhip_get_result_mcpes(clsimhip_converter *c, const clsimhip_photon *phot
     return guarded(c, [&] { need(c, "converter"); c->impl.result_mcpes(photons, mcpes, n); });
 }
 
+// ---- MCPE series (mcpe_series.h) ----
+int clsimhip_mcpe_series_host(const clsimhip_mcpe_generator *g, const clsimhip_mcpe *mcpes, size_t n, const clsimhip_mcpe_particle *particles,
+                              size_t n_particles, const clsimhip_mcpe_mask *masked, size_t n_masked, clsimhip_mcpe *out,
+                              clsimhip_mcpe_series *series, size_t *n_kept, size_t *n_series, uint64_t counters[3])
+{
+    return guarded(nullptr, [&] {
+        need(g, "generator");
+        if (counters) std::memset(counters, 0, 3 * sizeof(uint64_t));
+        g->impl->series_host(mcpes, n, particles, n_particles, masked, n_masked, out, series, n_kept, n_series, counters);
+    });
+}
+size_t clsimhip_mcpe_series_workspace_bytes(size_t capacity, size_t n_particles, size_t n_masked)
+{
+    return mcpe_series_workspace_bytes(capacity, n_particles, n_masked);
+}
+int clsimhip_mcpe_series_device(clsimhip_mcpe_generator *g, int device, const void *d_mcpes, const void *d_count, size_t capacity,
+                                const clsimhip_mcpe_particle *particles, size_t n_particles, const clsimhip_mcpe_mask *masked, size_t n_masked,
+                                void *d_out, void *d_series, void *d_counts, void *d_workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return guarded(nullptr, [&] {
+        need(g, "generator");
+        g->impl->series_device(device, d_mcpes, d_count, capacity, particles, n_particles, masked, n_masked, d_out, d_series, d_counts, d_workspace,
+                               workspace_bytes, static_cast<hipStream_t>(hip_stream));
+    });
+}
+int clsimhip_set_mcpe_series(clsimhip_converter *c, int on)
+{
+    return guarded(c, [&] { need(c, "converter"); c->impl.set_mcpe_series(on != 0); });
+}
+int clsimhip_enqueue_steps_with_particles(clsimhip_converter *c, const clsimhip_step *steps, size_t n, uint32_t identifier,
+                                          const clsimhip_mcpe_particle *particles, size_t n_particles, const clsimhip_mcpe_mask *masked,
+                                          size_t n_masked)
+{
+    return guarded(c, [&] { need(c, "converter"); c->impl.enqueue_steps(steps, n, identifier, particles, n_particles, masked, n_masked); });
+}
+int clsimhip_get_result_mcpe_series(clsimhip_converter *c, const clsimhip_photon *photons, const clsimhip_mcpe **mcpes, size_t *n,
+                                    const clsimhip_mcpe_series **series, size_t *n_series, uint64_t *n_masked)
+{
+    return guarded(c, [&] { need(c, "converter"); c->impl.result_mcpe_series(photons, mcpes, n, series, n_series, n_masked); });
+}
+
 } // extern "C"

@@ -155,6 +155,8 @@ void Converter::release_device()
     step_pool_.reset();
     result_pool_.reset();
     mcpe_pool_.reset();
+    series_pool_.reset();
+    bunch_pool_.reset();
 }
 
 void Converter::set_device(int device)
@@ -263,6 +265,7 @@ void Converter::compile()
         if (const char *e = std::getenv("CLSIMHIP_NO_NAMED_SEARCH")) table_tuning_.named_search = (e[0] != '1');
     }
 #endif
+    if (series_ && !mcpe_) throw Error(CLSIMHIP_ERR_CONFIG, "MCPE series need an MCPE generator (clsimhip_set_mcpe_generator)");
     if (mcpe_) {
         // the generator reads IDs from the records: every DOM's pair must fit them (the host conversion reports such IDs only when a
         // photon carries them, OpenCL.cxx:1577-1586) and must have a class (log_fatal per photon in the reference, :628-630)
@@ -456,6 +459,14 @@ void Converter::setup_device_buffers(DeviceState &D)
             sl.d_mcpe_counters.alloc(8, "MCPE counters");
             sl.h_mcpe_counters.alloc(8, "pinned MCPE counters");
         }
+        if (series_) {
+            sl.series_workspace_bytes = mcpe_series_workspace_bytes(max_output_photons_, 0, 0);
+            sl.d_series_workspace.alloc(sl.series_workspace_bytes, "MCPE series workspace");
+            sl.d_sorted.alloc(max_output_photons_, "sorted MCPEs");
+            sl.d_series.alloc(max_output_photons_, "MCPE series table");
+            sl.d_series_counts.alloc(8, "MCPE series counts");
+            sl.h_series_counts.alloc(8, "pinned MCPE series counts");
+        }
         sl.start.create("hipEventCreate");
         sl.stop.create("hipEventCreate");
         sl.counted.create_untimed("hipEventCreate");
@@ -536,7 +547,15 @@ KParams Converter::launch_params(const LaunchTuning &tuning, const void *d_steps
 // OpenCL.cxx:1525-1544
 void Converter::enqueue_steps(const clsimhip_step *steps, size_t n, uint32_t identifier)
 {
+    enqueue_steps(steps, n, identifier, nullptr, 0, nullptr, 0);
+}
+
+void Converter::enqueue_steps(const clsimhip_step *steps, size_t n, uint32_t identifier, const clsimhip_mcpe_particle *particles, size_t n_particles,
+                              const clsimhip_mcpe_mask *masked, size_t n_masked)
+{
     need_init();
+    if ((particles || n_particles || masked || n_masked) && !series_)
+        throw Error(CLSIMHIP_ERR_STATE, "a particle table or mask needs the MCPE series stage (clsimhip_set_mcpe_series)");
     check_worker();
     if (!steps) throw Error(CLSIMHIP_ERR_ARGUMENT, "Steps pointer is (null)!");
     if (n == 0) throw Error(CLSIMHIP_ERR_ARGUMENT, "Steps are empty!");
@@ -549,6 +568,17 @@ void Converter::enqueue_steps(const clsimhip_step *steps, size_t n, uint32_t ide
     job.pinned = step_pool_.take(n, std::max(n, std::min(max_workitems_, n + n / 4)), device_);
     if (job.pinned) std::memcpy(job.pinned.get(), steps, n * sizeof(clsimhip_step));
     else job.steps.assign(steps, steps + n);
+    if (series_) {
+        // checked and brought into the stage's form here, in the caller's thread: a bad table is the caller's error, not the worker's
+        const size_t bytes = mcpe_series_blob_bytes(n_particles, n_masked);
+        job.bunch_pinned = bunch_pool_.take(bytes, bytes + bytes / 4, device_);
+        uint8_t *blob = job.bunch_pinned.get();
+        if (!blob) {
+            job.bunch_blob.resize((bytes + 15u) / 16u);
+            blob = job.bunch_blob.data()->bytes;
+        }
+        job.bunch = mcpe_->prepare_series(particles, n_particles, masked, n_masked, blob);
+    }
     in_queue_->put(std::move(job));
 }
 
@@ -587,6 +617,29 @@ void Converter::submit(Slot &s, Job &job)
         mcpe_->convert_device(device_, s.d_photons.get(), s.d_hit_count.get(), max_output_photons_, s.d_mcpes.get(), max_output_photons_, s.d_mcpe_counters.get(), stream);
         hip_check(hipMemcpyAsync(s.h_mcpe_counters.get(), s.d_mcpe_counters.get(), 20, hipMemcpyDeviceToHost, stream), "download MCPE counters");
     }
+    if (series_) {
+        // behind the hit maker on the same stream, over the MCPEs it stored; all counts stay on the device until finish() fetches them
+        s.bunch_lease = std::move(job.bunch_pinned);
+        const uint8_t *blob = s.bunch_lease.get();
+        if (!blob) {
+            if (s.h_bunch_bytes < job.bunch.bytes) {
+                s.h_bunch.reset();
+                s.h_bunch.alloc(job.bunch.bytes, "pinned MCPE series bunch");
+                s.h_bunch_bytes = job.bunch.bytes;
+            }
+            std::memcpy(s.h_bunch.get(), job.bunch_blob.data(), job.bunch.bytes);
+            blob = s.h_bunch.get();
+        }
+        const size_t need = mcpe_series_workspace_bytes(max_output_photons_, job.bunch.n_particles, job.bunch.n_masked) + 64;
+        if (s.series_workspace_bytes < need) {          // (the slot is free: nothing on the device uses its workspace)
+            s.d_series_workspace.reset();
+            s.d_series_workspace.alloc(need + need / 4, "MCPE series workspace");
+            s.series_workspace_bytes = need + need / 4;
+        }
+        mcpe_->series_device_prepared(device_, s.d_mcpes.get(), s.d_mcpe_counters.get(), max_output_photons_, job.bunch, blob, s.d_sorted.get(),
+                                      s.d_series.get(), s.d_series_counts.get(), s.d_series_workspace.get(), s.series_workspace_bytes, stream);
+        hip_check(hipMemcpyAsync(s.h_series_counts.get(), s.d_series_counts.get(), 20, hipMemcpyDeviceToHost, stream), "download MCPE series counts");
+    }
     hip_check(hipEventRecord(s.counted.get(), stream), "event");
 }
 
@@ -621,6 +674,16 @@ void Converter::finish(Slot &s, std::chrono::steady_clock::time_point &last_done
                                                  std::to_string(mc[4]) + " with hit probability above 1");
         n_mcpes = std::min(mc[0], max_output_photons_);
     }
+    uint32_t n_series = 0;
+    if (series_) {
+        const uint32_t *sc = s.h_series_counts.get();       // kept, series, UNKNOWN_PARTICLE, MASKED, UNKNOWN_DOM
+        if ((sc[2] | sc[4]) != 0u)                          // log_fatal in the reference (I3CLSimClientModule.cxx:388-390)
+            throw Error(CLSIMHIP_ERR_DEVICE, "MCPE series, bunch " + std::to_string(s.id) + ": " + std::to_string(sc[2]) +
+                                                 " MCPEs of particles the bunch's particle table does not have, " + std::to_string(sc[4]) +
+                                                 " at DOMs the generator does not have");
+        n_mcpes = std::min(sc[0], max_output_photons_);
+        n_series = std::min(sc[1], n_mcpes);
+    }
     const uint32_t detected = hits;
     if (mcpe_ && !keep_photons_) hits = 0;              // the records stay on the device
     Result r;
@@ -653,9 +716,19 @@ void Converter::finish(Slot &s, std::chrono::steady_clock::time_point &last_done
             r.mcpe_pinned = mcpe_pool_.take(n_mcpes, result_capacity(n_mcpes, s.result_min_records), device_);
             clsimhip_mcpe *to = r.mcpe_pinned.get();
             if (!to) { r.mcpes.reset(new std::vector<clsimhip_mcpe>(n_mcpes)); to = r.mcpes->data(); }
-            hip_check(hipMemcpyAsync(to, s.d_mcpes.get(), static_cast<size_t>(n_mcpes) * sizeof(clsimhip_mcpe), hipMemcpyDeviceToHost, copy_stream), "download MCPEs");
+            const clsimhip_mcpe *from = series_ ? s.d_sorted.get() : s.d_mcpes.get();
+            hip_check(hipMemcpyAsync(to, from, static_cast<size_t>(n_mcpes) * sizeof(clsimhip_mcpe), hipMemcpyDeviceToHost, copy_stream), "download MCPEs");
+            if (n_series) {
+                r.series_pinned = series_pool_.take(n_series, result_capacity(n_series, s.result_min_records), device_);
+                clsimhip_mcpe_series *table = r.series_pinned.get();
+                if (!table) { r.series.reset(new std::vector<clsimhip_mcpe_series>(n_series)); table = r.series->data(); }
+                hip_check(hipMemcpyAsync(table, s.d_series.get(), static_cast<size_t>(n_series) * sizeof(clsimhip_mcpe_series), hipMemcpyDeviceToHost, copy_stream),
+                          "download MCPE series table");
+            }
             hip_check(hipStreamSynchronize(copy_stream), "download MCPEs");
         }
+        r.series_count = n_series;
+        if (series_) r.masked = s.h_series_counts.get()[3];
         if (!hits) r.handle.reset(new clsimhip_photon());
     }
     std::unique_ptr<std::vector<float>> histories;
@@ -798,6 +871,24 @@ void Converter::result_mcpes(const clsimhip_photon *photons, const clsimhip_mcpe
     if (it == handed_out_.end()) throw Error(CLSIMHIP_ERR_ARGUMENT, "not a result handed out by GetConversionResult (or already released)");
     *n = it->second.mcpe_count;
     if (it->second.mcpe_count) *mcpes = it->second.mcpe_data();
+}
+
+void Converter::result_mcpe_series(const clsimhip_photon *photons, const clsimhip_mcpe **mcpes, size_t *n, const clsimhip_mcpe_series **series, size_t *n_series,
+                                   uint64_t *n_masked)
+{
+    need_init();
+    if (!mcpes || !n || !series || !n_series) throw Error(CLSIMHIP_ERR_ARGUMENT, "output pointers are (null)");
+    if (!series_) throw Error(CLSIMHIP_ERR_STATE, "the MCPE series stage is off (clsimhip_set_mcpe_series)");
+    *mcpes = nullptr; *series = nullptr;
+    *n = 0; *n_series = 0;
+    std::lock_guard<std::mutex> lk(results_mutex_);
+    auto it = handed_out_.find(photons);
+    if (it == handed_out_.end()) throw Error(CLSIMHIP_ERR_ARGUMENT, "not a result handed out by GetConversionResult (or already released)");
+    *n = it->second.mcpe_count;
+    *n_series = it->second.series_count;
+    if (it->second.mcpe_count) *mcpes = it->second.mcpe_data();
+    if (it->second.series_count) *series = it->second.series_data();
+    if (n_masked) *n_masked = it->second.masked;
 }
 
 void Converter::release_result(const clsimhip_photon *photons)

@@ -45,6 +45,7 @@ size_t prop_kernel_max_lanes();
 size_t prop_kernel_lds_budget();
 
 class McpeGenerator;            // mcpe.h
+struct alignas(16) SeriesParticle16 { uint8_t bytes[16]; };     // 16-byte aligned storage for a bunch's table and mask (mcpe_series.h)
 
 // RCCL gather of detected photons (comm.cpp)
 struct Comm;
@@ -300,6 +301,8 @@ public:
     void set_max_num_workitems(size_t v);
     // clsimhip_set_mcpe_generator: the hit maker runs behind every bunch's propagation (null: off)
     void set_mcpe_generator(std::shared_ptr<McpeGenerator> g, bool keep_photons);
+    // clsimhip_set_mcpe_series: the sorting stage behind the hit maker (mcpe_series.h); needs a generator (Compile() checks)
+    void set_mcpe_series(bool on) { guard(); compiled_ = false; series_ = on; }
 
     void compile();
     void initialize(uint64_t seed);
@@ -310,9 +313,14 @@ public:
     size_t max_num_workitems() const { return max_workitems_; }
 
     void enqueue_steps(const clsimhip_step *steps, size_t n, uint32_t identifier);
+    // clsimhip_enqueue_steps_with_particles: particles = nullptr is "no table"
+    void enqueue_steps(const clsimhip_step *steps, size_t n, uint32_t identifier, const clsimhip_mcpe_particle *particles, size_t n_particles,
+                       const clsimhip_mcpe_mask *masked, size_t n_masked);
     void get_result(uint32_t *identifier, const clsimhip_photon **photons, size_t *n);
     void result_histories(const clsimhip_photon *photons, const float **histories, uint32_t *entries);
     void result_mcpes(const clsimhip_photon *photons, const clsimhip_mcpe **mcpes, size_t *n);
+    void result_mcpe_series(const clsimhip_photon *photons, const clsimhip_mcpe **mcpes, size_t *n, const clsimhip_mcpe_series **series, size_t *n_series,
+                            uint64_t *n_masked);
     void release_result(const clsimhip_photon *photons);
     size_t queue_size() const;
     bool more_photons_available() const;
@@ -347,11 +355,17 @@ private:
     using StepPool = PinnedPool<clsimhip_step>;
     using PhotonPool = PinnedPool<clsimhip_photon>;
     using McpePool = PinnedPool<clsimhip_mcpe>;
+    using SeriesPool = PinnedPool<clsimhip_mcpe_series>;
+    using BlobPool = PinnedPool<uint8_t>;
     // A bunch on its way to the worker: the caller's steps are copied ONCE, in the caller's thread, into a page-locked buffer of the
     // step pool, which the worker uploads from (round 5; before, a vector here and a second copy into the slot's staging buffer on
     // the worker thread -- 8 ms per million steps in front of the first kernel of a run).  With every pool buffer in flight the
     // steps travel in a vector as before.
-    struct Job { uint32_t id = 0; size_t n = 0; uint64_t generated = 0; StepPool::Lease pinned; std::vector<clsimhip_step> steps; };
+    // With the MCPE series stage the bunch's particle table and mask travel the same way, in the form the stage reads (mcpe_series.h).
+    struct Job {
+        uint32_t id = 0; size_t n = 0; uint64_t generated = 0; StepPool::Lease pinned; std::vector<clsimhip_step> steps;
+        SeriesBunch bunch; BlobPool::Lease bunch_pinned; std::vector<SeriesParticle16> bunch_blob;
+    };
     // The photons of a result live in a page-locked buffer of the converter's pool (the download lands there and the
     // caller reads them there until ReleaseResult: no host copy in between), or -- when the pool is exhausted because the
     // caller holds more results than it has buffers -- in a vector of their own.
@@ -369,6 +383,12 @@ private:
         std::unique_ptr<std::vector<clsimhip_mcpe>> mcpes;
         std::unique_ptr<clsimhip_photon> handle;
         const clsimhip_mcpe *mcpe_data() const { return mcpe_pinned ? mcpe_pinned.get() : (mcpes ? mcpes->data() : nullptr); }
+        // with the MCPE series stage: the series table of the (then sorted) MCPEs and the MASKED count
+        SeriesPool::Lease series_pinned;
+        size_t series_count = 0;
+        uint64_t masked = 0;
+        std::unique_ptr<std::vector<clsimhip_mcpe_series>> series;
+        const clsimhip_mcpe_series *series_data() const { return series_pinned ? series_pinned.get() : (series ? series->data() : nullptr); }
     };
 
     void guard() const { if (initialized_) throw Error(CLSIMHIP_ERR_STATE, "I3CLSimStepToPhotonConverterHIP already initialized!"); }
@@ -396,6 +416,7 @@ private:
 
     std::shared_ptr<McpeGenerator> mcpe_;       // null: no MCPEs are made (the default)
     bool keep_photons_ = true;
+    bool series_ = false;                       // the MCPE series stage runs behind the hit maker
 
     std::atomic<bool> compiled_{false}, initialized_{false};    // (atomic: set_tuning() reads them from any thread)
     CompiledTables tables_;
@@ -408,6 +429,9 @@ private:
     // million work items, six of them.)  The same for MCPEs (16-byte records).
     PhotonPool result_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
     McpePool mcpe_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
+    SeriesPool series_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
+    // particle tables and masks of the bunches on their way (input queue depth + one per slot + the one being filled)
+    BlobPool bunch_pool_{PinnedPoolPolicy{8, size_t{1} << 28, nullptr}};
     size_t result_capacity(size_t records, size_t min_records) const;
     // Step buffers (see Job): input queue depth + one per slot + the one being filled, each sized by the bunch it first carried (a
     // quarter more) and replaced by a larger one when a later bunch needs it, at most 1 GiB in all
@@ -430,6 +454,16 @@ private:
         DeviceBuffer<clsimhip_mcpe> d_mcpes;    // with an MCPE generator: max_output_photons_ records, five counters (mcpe.h)
         DeviceBuffer<uint32_t> d_mcpe_counters;
         PinnedBuffer<uint32_t> h_mcpe_counters;
+        // with the MCPE series stage: its workspace (grown when a bunch's table needs it), sorted records, series table, five counts
+        DeviceBuffer<uint8_t> d_series_workspace;
+        size_t series_workspace_bytes = 0;
+        DeviceBuffer<clsimhip_mcpe> d_sorted;
+        DeviceBuffer<clsimhip_mcpe_series> d_series;
+        DeviceBuffer<uint32_t> d_series_counts;
+        PinnedBuffer<uint32_t> h_series_counts;
+        BlobPool::Lease bunch_lease;            // the pool buffer the slot's table upload reads; back to the pool when the slot is used again
+        PinnedBuffer<uint8_t> h_bunch;          // pinned staging (for a job that came without a pool buffer)
+        size_t h_bunch_bytes = 0;
         uint32_t id = 0;
         uint64_t generated = 0;
         size_t result_min_records = 0;          // of the tuning the bunch was launched with

@@ -133,4 +133,13 @@ void series_encode(const void *records, size_t n, size_t record, unsigned versio
 void series_decode(const uint8_t *in, size_t bytes, size_t record, unsigned version, const char *class_name, void *out, size_t cap,
                    size_t *n_out, size_t *consumed);
 
+// mcpe_series.cpp: what McpeGenerator::prepare_series made of one bunch's particle table and mask, and the sizes that go with it
+struct SeriesBunch {
+    uint32_t n_particles = 0, n_frames = 1, n_masked = 0;
+    bool have_table = false, consecutive = false;
+    size_t frames_offset = 0, masked_offset = 0, bytes = 0;     // within the blob
+};
+size_t mcpe_series_blob_bytes(size_t n_particles, size_t n_masked);
+size_t mcpe_series_workspace_bytes(size_t capacity, size_t n_particles, size_t n_masked);
+
 } // namespace clsimhip

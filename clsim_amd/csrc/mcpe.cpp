@@ -1,6 +1,7 @@
 // The MCPE generator object: see mcpe.h.  Configuration and the host twin here, the kernel in mcpe_kernel.hip.
 #include "mcpe.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 
@@ -72,6 +73,20 @@ McpeGenerator::McpeGenerator(const std::vector<FunctionData> &classes, size_t n_
             throw Error(CLSIMHIP_ERR_ARGUMENT, "DOM (" + std::to_string(string_ids[i]) + ", " + std::to_string(om_ids[i]) + ") is given two different classes");
         dom_table_[slot] = entry;
     }
+    // MCPE series: every DOM's rank in ascending (string ID signed, OM ID) order -- OMKey::operator< with PMT 0 -- in an array of
+    // its own beside the table (the table's entries, and what mcpe_class_of reads in them, stay what they are)
+    for (uint64_t e : dom_table_)
+        if (e != 0u) dom_of_rank_.push_back(static_cast<uint32_t>(e));
+    std::sort(dom_of_rank_.begin(), dom_of_rank_.end(), [](uint32_t a, uint32_t b) {
+        const int16_t sa = static_cast<int16_t>(a & 0xffffu), sb = static_cast<int16_t>(b & 0xffffu);
+        return sa != sb ? sa < sb : (a >> 16) < (b >> 16);
+    });
+    dom_ranks_.assign(slots, 0u);
+    for (size_t r = 0; r < dom_of_rank_.size(); ++r) {
+        uint32_t slot = mcpe_dom_slot(dom_of_rank_[r], P.dom_mask);
+        while (static_cast<uint32_t>(dom_table_[slot]) != dom_of_rank_[r] || dom_table_[slot] == 0u) slot = (slot + 1u) & P.dom_mask;
+        dom_ranks_[slot] = static_cast<uint32_t>(r);
+    }
     if (values_.empty()) values_.push_back(0.);         // (never read: only constant classes)
     P.values = values_.data();
     P.dom_table = dom_table_.data();
@@ -84,6 +99,12 @@ McpeGenerator::~McpeGenerator()
         DeviceGuard on_device(kv.first, std::nothrow);
         DeviceBuffer<double> values(kv.second.values);
         DeviceBuffer<uint64_t> dom_table(kv.second.dom_table);
+        DeviceBuffer<uint32_t> dom_ranks(kv.second.dom_ranks), dom_of_rank(kv.second.dom_of_rank);
+    }
+    // (a stage exists from the first series call on a device on, whether or not that call got as far as the device's image)
+    for (auto &kv : stages_) {
+        DeviceGuard on_device(kv.first, std::nothrow);
+        kv.second = SeriesStage();
     }
 }
 
@@ -122,7 +143,11 @@ McpeGenerator::DeviceImage McpeGenerator::image_on(int device)
     DeviceBuffer<uint64_t> dom_table(dom_table_.size(), "MCPE DOM classes");
     hip_check(hipMemcpy(values.get(), values_.data(), values_.size() * sizeof(double), hipMemcpyHostToDevice), "MCPE acceptance tables");
     hip_check(hipMemcpy(dom_table.get(), dom_table_.data(), dom_table_.size() * sizeof(uint64_t), hipMemcpyHostToDevice), "MCPE DOM classes");
-    const DeviceImage im{values.release(), dom_table.release()};
+    DeviceBuffer<uint32_t> dom_ranks(dom_ranks_.size(), "MCPE DOM ranks"), dom_of_rank(dom_of_rank_.size(), "MCPE DOMs by rank");
+    hip_check(hipMemcpy(dom_ranks.get(), dom_ranks_.data(), dom_ranks_.size() * sizeof(uint32_t), hipMemcpyHostToDevice), "MCPE DOM ranks");
+    if (!dom_of_rank_.empty())
+        hip_check(hipMemcpy(dom_of_rank.get(), dom_of_rank_.data(), dom_of_rank_.size() * sizeof(uint32_t), hipMemcpyHostToDevice), "MCPE DOMs by rank");
+    const DeviceImage im{values.release(), dom_table.release(), dom_ranks.release(), dom_of_rank.release()};
     images_[device] = im;
     return im;
 }

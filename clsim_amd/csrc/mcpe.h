@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "detmath.hip.h"
+#include "hip_resources.h"
 #include "host_model.h"
 
 namespace clsimhip {
@@ -218,14 +219,39 @@ public:
     bool has_class(int32_t string_id, uint32_t om_id) const;
     double pancake() const { return pancake_; }
 
+    // ---- MCPE series (mcpe_series.h; mcpe_series.cpp) ----
+    size_t num_doms() const { return dom_of_rank_.size(); }             // distinct (string ID, OM ID) pairs
+    // One bunch's particle table and mask, checked and brought into the form the stage reads (mcpe_series_blob_bytes(n_particles,
+    // n_masked) bytes at `blob`, 16-byte aligned): CLSIMHIP_ERR_ARGUMENT for a table that is not strictly increasing in
+    // `identifier`, CLSIMHIP_ERR_CONFIG for frames x DOMs >= 2^32.  particles = nullptr: no table.
+    SeriesBunch prepare_series(const clsimhip_mcpe_particle *particles, size_t n_particles, const clsimhip_mcpe_mask *masked, size_t n_masked,
+                               uint8_t *blob) const;
+    // host twin: out and series hold n entries each; counters[3] += UNKNOWN_PARTICLE, MASKED, UNKNOWN_DOM
+    void series_host(const clsimhip_mcpe *in, size_t n, const clsimhip_mcpe_particle *particles, size_t n_particles, const clsimhip_mcpe_mask *masked,
+                     size_t n_masked, clsimhip_mcpe *out, clsimhip_mcpe_series *series, size_t *n_kept, size_t *n_series, uint64_t counters[3]) const;
+    // the kernels on `stream` of `device`, over min(*d_count, capacity) records; d_counts: five uint32 (kept, series, the counters)
+    void series_device(int device, const void *d_mcpes, const void *d_count, size_t capacity, const clsimhip_mcpe_particle *particles,
+                       size_t n_particles, const clsimhip_mcpe_mask *masked, size_t n_masked, void *d_out, void *d_series, void *d_counts,
+                       void *d_workspace, size_t workspace_bytes, hipStream_t stream);
+    // the same for a bunch prepared into page-locked memory that stays as it is until the stream has passed the copy this call
+    // begins with; `uploaded` (may be null) is recorded behind that copy
+    void series_device_prepared(int device, const void *d_mcpes, const void *d_count, size_t capacity, const SeriesBunch &bunch, const uint8_t *h_blob,
+                                void *d_out, void *d_series, void *d_counts, void *d_workspace, size_t workspace_bytes, hipStream_t stream,
+                                hipEvent_t uploaded = nullptr);
+
 private:
     McpeParams params_{};
     std::vector<double> values_;
     std::vector<uint64_t> dom_table_;
     double pancake_ = 1.;
-    struct DeviceImage { double *values = nullptr; uint64_t *dom_table = nullptr; };
-    std::mutex device_mutex_;
+    std::vector<uint32_t> dom_ranks_;       // beside dom_table_, slot by slot: the DOM's rank in ascending (string ID, OM ID) order
+    std::vector<uint32_t> dom_of_rank_;     // record word 11 (string ID | OM ID << 16) by rank
+    struct DeviceImage { double *values = nullptr; uint64_t *dom_table = nullptr; uint32_t *dom_ranks = nullptr, *dom_of_rank = nullptr; };
+    // page-locked staging of the stand-alone series call's bunch, one per device, reused once its upload has been passed
+    struct SeriesStage { Event done; PinnedBuffer<uint8_t> buffer; size_t bytes = 0; };
+    std::mutex device_mutex_, series_mutex_;
     std::map<int, DeviceImage> images_;
+    std::map<int, SeriesStage> stages_;
     DeviceImage image_on(int device);
 };
 

@@ -212,10 +212,18 @@ public:
         check(clsimhip_get_conversion_result(handle_, &r.identifier, &p, &n));
         r.photons = I3CLSimPhotonSeriesPtr(new I3CLSimPhotonSeries(n));
         lastMCPEs_.clear();
+        lastSeries_.clear();
+        lastMasked_ = 0;
         if (mcpeGenerator_) {       // (ConversionResult_t has no place for them: GetLastMCPEs())
             const clsimhip_mcpe *m = nullptr;
             size_t nm = 0;
-            check(clsimhip_get_result_mcpes(handle_, p, &m, &nm));
+            if (mcpeSeries_) {
+                const clsimhip_mcpe_series *s = nullptr;
+                size_t ns = 0;
+                check(clsimhip_get_result_mcpe_series(handle_, p, &m, &nm, &s, &ns, &lastMasked_));
+                lastSeries_.assign(s, s + ns);
+            } else
+                check(clsimhip_get_result_mcpes(handle_, p, &m, &nm));
             lastMCPEs_.assign(m, m + nm);
             if (!n) check(clsimhip_release_result(handle_, p));     // the handle of a result without photon records
         }
@@ -330,8 +338,40 @@ public:
         check(clsimhip_set_mcpe_generator(handle_, generator, keepPhotons ? 1 : 0));
         mcpeGenerator_ = generator != nullptr;
     }
-    // the MCPEs of the bunch the last GetConversionResult() returned (its identifier: that result's), in no particular order
+    // the MCPEs of the bunch the last GetConversionResult() returned (its identifier: that result's), in no particular order --
+    // with SetMCPESeries(true) in the order of the series
     const std::vector<clsimhip_mcpe> &GetLastMCPEs() const { return lastMCPEs_; }
+
+    // ---- MCPE series (include/clsimhip.h, "MCPE series"): what replaces the client module's AddPhotonsToFrames loop and the per-DOM
+    // time sort.  Before Initialize(); needs a generator.  A bunch is enqueued with its particle table (strictly increasing in
+    // identifier) and its frames' ignored modules; its result's MCPEs come back per frame, per DOM in OMKey order, in time order. ----
+    void SetMCPESeries(bool on = true)
+    {
+        check(clsimhip_set_mcpe_series(handle_, on ? 1 : 0));
+        mcpeSeries_ = on;
+    }
+    void EnqueueSteps(I3CLSimStepSeriesConstPtr steps, uint32_t identifier, const std::vector<clsimhip_mcpe_particle> &particles,
+                      const std::vector<clsimhip_mcpe_mask> &ignored = std::vector<clsimhip_mcpe_mask>())
+    {
+        if (!steps) throw I3CLSimStepToPhotonConverter_exception("Steps pointer is (null)!");
+        static const clsimhip_mcpe_particle none = {0u, 0u, 0.};       // (an empty table is still a table)
+        check(clsimhip_enqueue_steps_with_particles(handle_, reinterpret_cast<const clsimhip_step *>(steps->data()), steps->size(), identifier,
+                                                    particles.empty() ? &none : particles.data(), particles.size(),
+                                                    ignored.empty() ? nullptr : ignored.data(), ignored.size()));
+    }
+    // the flat views of the last result: GetLastMCPEs() and its series table (entries partition the records), the MASKED count
+    const std::vector<clsimhip_mcpe_series> &GetLastMCPESeries() const { return lastSeries_; }
+    uint64_t GetLastMaskedMCPEs() const { return lastMasked_; }
+    // ... and as the frames receive them: frame -> (string ID, OM ID) -> time-ordered MCPEs (an I3MCPESeriesMap per frame)
+    typedef std::map<std::pair<int, unsigned>, std::vector<clsimhip_mcpe> > MCPESeriesMap;
+    std::map<uint32_t, MCPESeriesMap> GetLastMCPESeriesMaps() const
+    {
+        std::map<uint32_t, MCPESeriesMap> frames;
+        for (const clsimhip_mcpe_series &s : lastSeries_)
+            frames[s.frame][std::make_pair(static_cast<int>(s.string_id), static_cast<unsigned>(s.om_id))]
+                .assign(lastMCPEs_.begin() + s.first, lastMCPEs_.begin() + s.first + s.count);
+        return frames;
+    }
 
 private:
     void check(int rc) const
@@ -350,6 +390,9 @@ private:
     uint64_t seed_;
     bool mcpeGenerator_ = false;
     std::vector<clsimhip_mcpe> lastMCPEs_;
+    bool mcpeSeries_ = false;
+    std::vector<clsimhip_mcpe_series> lastSeries_;
+    uint64_t lastMasked_ = 0;
 #ifdef CLSIMHIP_WITH_ICETRAY
     I3RandomServicePtr randomService_;
 #endif

@@ -785,6 +785,80 @@ int clsimhip_set_mcpe_generator(clsimhip_converter *c, clsimhip_mcpe_generator *
  * CLSIMHIP_ERR_DEVICE with the four counts in the text). */
 int clsimhip_get_result_mcpes(clsimhip_converter *c, const clsimhip_photon *photons, const clsimhip_mcpe **mcpes, size_t *n);
 
+/* ---- MCPE series: a bunch's MCPEs as per-frame, per-DOM time-sorted series ---------------------------------------------
+ * What the reference's client module does with every MCPE on a host thread before a frame receives its I3MCPESeriesMap:
+ * AddPhotonsToFrames (private/clsim/I3CLSimClientModule.cxx:359-439: particle cache lookup, ignoreModules, time shift,
+ * (*frame->hits)[omkey]) and the per-DOM time order (private/clsim/dom/I3PhotonToMCPEConverter.cxx:524-526), as a sorting stage
+ * behind the MCPE kernel.  Per record, in this order:
+ *     its DOM is not one of the generator's -> UNKNOWN_DOM, no record (the generator's own MCPEs never meet this);
+ *     its identifier is not in the particle table -> UNKNOWN_PARTICLE, no record (log_fatal in the reference, :388-390);
+ *     (frame, string_id, om_id) is in the mask -> MASKED, no record (:399; not an error);
+ *     time' = time + time_shift, one binary64 addition (:334; without a table the shift is +0.0, which turns -0.0 into +0.0).
+ * The kept records come out ascending in the integer key (frame, DOM rank, tkey, identifier): frames in ascending frame ID, DOMs
+ * in ascending (string_id signed, om_id) -- OMKey::operator< with PMT 0 --, and b = bits(time'), tkey = b ^ (b >> 63 ? ~0 :
+ * 1 << 63), a total order on bit patterns (-0.0 before +0.0, negative NaNs before -inf, positive NaNs after +inf; nothing depends
+ * on < of doubles).  Records with equal keys are byte-identical, so the output is a function of the input as a multiset: the same
+ * bytes from run to run, whatever the schedule, and the same bytes from the kernels and the host twin.  The series table has one
+ * entry per non-empty (frame, DOM) in the same order; its entries partition the records.
+ * The reference adds the shift to the photon's time before the conversion, in the photon's precision; here it is added once, after
+ * the arrival time correction, in binary64.  Hit merging (MergeHits) and the particle-ID map are not part of this. */
+typedef struct {                        /* one entry of the particle cache: the frame the particle belongs to and its time shift */
+    uint32_t identifier;                /* strictly increasing over the table (CLSIMHIP_ERR_ARGUMENT otherwise) */
+    uint32_t frame;                     /* the caller's frame ID, any value */
+    double time_shift;
+} clsimhip_mcpe_particle;               /* 16 bytes */
+typedef struct {                        /* one module of one frame's ignoreModules; entries that name a frame or a DOM the bunch */
+    uint32_t frame;                     /* never meets are ignored */
+    int16_t string_id;
+    uint16_t om_id;
+} clsimhip_mcpe_mask;                   /* 8 bytes */
+typedef struct {
+    uint32_t frame;
+    int16_t string_id;
+    uint16_t om_id;
+    uint32_t first, count;              /* records [first, first + count) */
+} clsimhip_mcpe_series;                 /* 16 bytes */
+typedef char clsimhip_mcpe_is_16_bytes[sizeof(clsimhip_mcpe) == 16 ? 1 : -1];
+typedef char clsimhip_mcpe_particle_is_16_bytes[sizeof(clsimhip_mcpe_particle) == 16 ? 1 : -1];
+typedef char clsimhip_mcpe_series_is_16_bytes[sizeof(clsimhip_mcpe_series) == 16 ? 1 : -1];
+typedef char clsimhip_mcpe_mask_is_8_bytes[sizeof(clsimhip_mcpe_mask) == 8 ? 1 : -1];
+#define CLSIMHIP_SERIES_UNKNOWN_PARTICLE 0      /* index into the series counters */
+#define CLSIMHIP_SERIES_MASKED 1
+#define CLSIMHIP_SERIES_UNKNOWN_DOM 2
+/* The host twin: the definition with std::sort on the key, for callers without a GPU and for the tests.  `g` supplies the DOM
+ * list.  particles = NULL, n_particles = 0: no table -- every identifier belongs to frame 0 with shift 0.  out and series hold n
+ * entries each; counters[3] (may be NULL) receives the three counts.  CLSIMHIP_ERR_CONFIG when frames x DOMs >= 2^32. */
+int clsimhip_mcpe_series_host(const clsimhip_mcpe_generator *g, const clsimhip_mcpe *mcpes, size_t n, const clsimhip_mcpe_particle *particles,
+                              size_t n_particles, const clsimhip_mcpe_mask *masked, size_t n_masked, clsimhip_mcpe *out,
+                              clsimhip_mcpe_series *series, size_t *n_kept, size_t *n_series, uint64_t counters[3]);
+/* bytes of device memory the kernels need beside their input and output, for up to `capacity` records and a bunch with this table
+ * and mask */
+size_t clsimhip_mcpe_series_workspace_bytes(size_t capacity, size_t n_particles, size_t n_masked);
+/* The kernels, on MCPEs that live in HBM (pairs with clsimhip_mcpe_convert_device: d_mcpes and d_count = its d_counters, whose
+ * first word counts past the capacity): min(*d_count, capacity) records of d_mcpes.  d_out and d_series: `capacity` entries each,
+ * d_workspace: clsimhip_mcpe_series_workspace_bytes(capacity, n_particles, n_masked) bytes, all 16-byte aligned; d_counts: five
+ * uint32 -- records kept, series, then the three counters.  The particle table and the mask are host memory: they are checked and
+ * copied before the call returns (which may wait for the previous call's copy, nothing else); the kernels are asynchronous on
+ * hip_stream (NULL = default stream) and nothing else waits for the device. */
+int clsimhip_mcpe_series_device(clsimhip_mcpe_generator *g, int device, const void *d_mcpes, const void *d_count, size_t capacity,
+                                const clsimhip_mcpe_particle *particles, size_t n_particles, const clsimhip_mcpe_mask *masked, size_t n_masked,
+                                void *d_out, void *d_series, void *d_counts, void *d_workspace, size_t workspace_bytes, void *hip_stream);
+/* The stage behind every bunch's MCPE kernel, on the bunch's stream.  Before Initialize() only (CLSIMHIP_ERR_STATE after);
+ * Compile() refuses it without an MCPE generator (CLSIMHIP_ERR_CONFIG).  on = 0 (the default): nothing changes anywhere.
+ * With it on, clsimhip_get_result_mcpes returns the sorted records, and a bunch with UNKNOWN_PARTICLE (or UNKNOWN_DOM) > 0 fails
+ * as a bunch with one of the MCPE generator's four conditions does, with the count in the text. */
+int clsimhip_set_mcpe_series(clsimhip_converter *c, int on);
+/* clsimhip_enqueue_steps with the bunch's particle table and mask, which are checked and copied in the caller's thread
+ * (CLSIMHIP_ERR_ARGUMENT / CLSIMHIP_ERR_CONFIG as above; CLSIMHIP_ERR_STATE without clsimhip_set_mcpe_series).  A bunch enqueued
+ * with clsimhip_enqueue_steps has no table: one frame, 0. */
+int clsimhip_enqueue_steps_with_particles(clsimhip_converter *c, const clsimhip_step *steps, size_t n, uint32_t identifier,
+                                          const clsimhip_mcpe_particle *particles, size_t n_particles, const clsimhip_mcpe_mask *masked,
+                                          size_t n_masked);
+/* Records and series table of the result `photons` belongs to, valid until clsimhip_release_result(c, photons); n_masked (may be
+ * NULL) receives the MASKED count.  Pointers are NULL where there is nothing.  CLSIMHIP_ERR_STATE without clsimhip_set_mcpe_series. */
+int clsimhip_get_result_mcpe_series(clsimhip_converter *c, const clsimhip_photon *photons, const clsimhip_mcpe **mcpes, size_t *n,
+                                    const clsimhip_mcpe_series **series, size_t *n_series, uint64_t *n_masked);
+
 #ifdef __cplusplus
 }
 #endif

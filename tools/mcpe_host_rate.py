@@ -3,6 +3,10 @@
 No GPU: the committed photon records of tests/golden/verbatim_cl_*.npz, repeated to `--records` records, best of `--repeats`.
 
     python tools/mcpe_host_rate.py [--records 2000000] [--repeats 5]
+
+--series N: the MCPE series' host twin instead (clsimhip_mcpe_series_host: lookup, mask, shift, sort, series table), in MCPEs per
+second, on N synthetic MCPEs at IceCube's 5160 DOMs dealt to 1000 particles in 10 frames; --device adds the device stage's time
+for the same input (HIP events around clsimhip_mcpe_series_device, best of --repeats; needs a GPU).
 """
 import argparse
 import ctypes as C
@@ -19,11 +23,59 @@ from clsim_amd import converter as CV           # noqa: E402
 from tests import mcpe_common as M              # noqa: E402
 
 
+def series_rate(args):
+    n = args.series
+    rng = np.random.default_rng(1)
+    s, d = np.meshgrid(np.arange(1, 87), np.arange(1, 61), indexing="ij")
+    s, d = s.reshape(-1).astype(np.int32), d.reshape(-1).astype(np.uint32)
+    gen = M.make_generator([M.acceptance_table()], s, d, np.zeros(len(s), dtype=np.int32))
+    m = np.zeros(n, dtype=CV.MCPE_DTYPE)
+    dom = rng.integers(0, len(s), n)
+    m["stringID"], m["omID"], m["id"], m["time"] = s[dom], d[dom], rng.integers(0, 1000, n), rng.uniform(0.0, 1.0e4, n)
+    p = np.zeros(1000, dtype=CV.MCPE_PARTICLE_DTYPE)
+    p["id"], p["frame"], p["timeShift"] = np.arange(1000), np.arange(1000) % 10, rng.uniform(0.0, 1.0e6, 1000)
+    masked = np.zeros(20, dtype=CV.MCPE_MASK_DTYPE)
+    masked["frame"], masked["stringID"], masked["omID"] = np.arange(20) % 10, 40, 30
+    best = float("inf")
+    for _ in range(args.repeats):
+        t0 = time.perf_counter()
+        records, series, counters = gen.MakeSeriesHost(m, p, masked)
+        best = min(best, time.perf_counter() - t0)
+    line = {"mcpes": n, "kept": len(records), "series": len(series), "host_seconds": best, "host_mcpes_per_s": n / best, "threads": 1}
+    if args.device:
+        import torch
+        dev = torch.device("cuda", 0)
+        d_in = torch.from_numpy(m.view(np.uint8).reshape(-1, 16).copy()).to(dev)
+        d_cnt = torch.tensor([n], dtype=torch.int32, device=dev)
+        d_out, d_series = torch.zeros((n, 16), dtype=torch.uint8, device=dev), torch.zeros((n, 16), dtype=torch.uint8, device=dev)
+        d_counts = torch.zeros(5, dtype=torch.int32, device=dev)
+        ws = CV.MCPEGenerator.SeriesWorkspaceBytes(n, len(p), len(masked))
+        d_ws = torch.zeros(ws, dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream().cuda_stream
+        times = []
+        for _ in range(args.repeats + 1):
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            gen.MakeSeriesDevice(d_in.data_ptr(), d_cnt.data_ptr(), n, d_out.data_ptr(), d_series.data_ptr(), d_counts.data_ptr(), d_ws.data_ptr(), ws,
+                                 p, masked, stream=stream)
+            stop.record()
+            torch.cuda.synchronize()
+            times.append(start.elapsed_time(stop) * 1e-3)
+        got = d_out.cpu().numpy()[:len(records)].copy().view(CV.MCPE_DTYPE).reshape(-1)
+        assert int(d_counts[0]) == len(records) and got.tobytes() == records.tobytes()
+        line.update(device_seconds=min(times[1:]), device_mcpes_per_s=n / min(times[1:]))
+    print(json.dumps(line))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--records", type=int, default=2000000)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--series", type=int, default=0, metavar="N")
+    ap.add_argument("--device", action="store_true")
     args = ap.parse_args()
+    if args.series:
+        return series_rate(args)
     base = np.concatenate([M.fixture_photons(name) for name in M.FIXTURES if name != "lea_no_pancake"])     # recorded with pancake 5
     ph = np.ascontiguousarray(np.tile(base, -(-args.records // len(base)))[:args.records])
     gen = M.standard_generator()

@@ -1,0 +1,52 @@
+#!/usr/bin/env python3
+"""One full C2 bunch (SPICE-Mie, IC86, 1 048 576 cascade steps of 200 photons) through the converter with the MCPE generator and
+the MCPE series stage, steps dealt to 1000 particles in 10 frames: the run to put under `rocprofv3 --kernel-trace --stats` to see
+the stage's kernels beside the propagation kernel.  Prints the counts and the host-side wall time of the bunch.
+
+    rocprofv3 --kernel-trace --stats -d OUT -- python tools/mcpe_series_profile.py [--steps 1048576] [--no-series]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from clsim_amd import converter as CV           # noqa: E402
+from tests import common                        # noqa: E402
+from tests import mcpe_common as M              # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=1 << 20)
+    ap.add_argument("--no-series", action="store_true")
+    args = ap.parse_args()
+    cfg = common.config("mie")
+    g = cfg["geom"]
+    s, d = np.asarray(g["string_ids"]), np.asarray(g["dom_ids"])
+    gen = M.make_generator([M.acceptance_table()], s, d, np.zeros(len(s), dtype=np.int32))
+    bias = CV.GetIceCubeDOMAcceptance()
+    conv = CV.initializeHIP(0, CV.I3CLSimSimpleGeometry.from_dict(g), cfg["med_p"], bias, common.product_generators(cfg, bias), pancakeFactor=5.0,
+                            stopDetectedPhotons=True, approximateNumberOfWorkItems=args.steps, mcpeGenerator=gen, keepPhotons=False,
+                            mcpeSeries=not args.no_series)
+    steps = common.steps_for(cfg, args.steps, seed=3).copy()
+    steps["id"] = np.arange(len(steps)) % 1000
+    p = np.zeros(1000, dtype=CV.MCPE_PARTICLE_DTYPE)
+    p["id"], p["frame"], p["timeShift"] = np.arange(1000), np.arange(1000) % 10, np.arange(1000) * 1000.0
+    for bunch in range(2):          # the first bunch allocates the pools
+        t0 = time.perf_counter()
+        if args.no_series:
+            conv.EnqueueSteps(steps, bunch)
+        else:
+            conv.EnqueueSteps(steps, bunch, particles=p)
+        r = conv.GetConversionResult()
+        wall = time.perf_counter() - t0
+    print(json.dumps({"steps": len(steps), "photons": int(steps["num"].sum()), "mcpes": len(r.mcpes),
+                      "series": None if r.series is None else len(r.series), "wall_seconds_second_bunch": wall}))
+
+
+if __name__ == "__main__":
+    main()
