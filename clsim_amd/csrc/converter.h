@@ -17,32 +17,9 @@
 #include "hip_resources.h"
 #include "host_model.h"
 #include "kparams.h"
+#include "prop_launch.h"
 
 namespace clsimhip {
-
-hipError_t launch_prop_kernel(const KParams &P, const KVariant &v, hipStream_t stream);
-// pooled scheduling (prop_pool_kernel.hip): same results, propagation without photon histories only
-hipError_t launch_pool_kernel(const KParams &P, const KVariant &v, hipStream_t stream);
-hipError_t launch_pool_keep_kernel(const KParams &P, const KVariant &v, hipStream_t stream);     // prop_pool_keep_kernel.hip: without STOP_PHOTONS_ON_DETECTION
-bool pool_kernel_fits(uint32_t table_words, uint32_t keep_strings, int num_layers);
-size_t pool_kernel_max_steps();     // bunches beyond this many steps do not fit the pooled kernel's pending entries (23-bit step index)
-hipError_t launch_eval_math(int what, const float *xs, const float *ys, uint32_t n, float *out, hipStream_t stream);
-hipError_t launch_check_math(int what, int exp_lo, int exp_hi, uint32_t *result, uint32_t result_cap, hipStream_t stream);
-size_t prop_kernel_lds_bytes(uint32_t table_words);
-int prop_kernel_block_size();
-hipError_t launch_generate_flasher_steps(const clsimhip_flasher_config &cfg, const clsimhip_flasher_request *d_requests, const void *d_plan,
-                                         uint32_t n_requests, uint64_t total, uint64_t seed, const float *d_profiles, void *d_out,
-                                         hipStream_t stream);
-hipError_t launch_generate_steps(const clsimhip_step_request *d_requests, const uint64_t *d_first_step, uint32_t n_requests,
-                                 uint64_t total_real, uint64_t total_padded, uint64_t seed, void *d_out, hipStream_t stream);
-hipError_t launch_tab_kernel(const KParams &P, const KVariant &v, hipStream_t stream);
-hipError_t launch_eval_function(const KParams &P, int lengths_kind, bool has_tilt, bool fast, int what, int layer, const float4 *in, uint32_t n, float4 *out,
-                                hipStream_t stream);
-hipError_t launch_eval_random(const KParams &P, bool fast, int what, int generator, uint64_t *x, const uint32_t *a, uint32_t n_streams, uint32_t draws,
-                              float *out, hipStream_t stream);
-hipError_t launch_keep_kernel(const KParams &P, const KVariant &v, hipStream_t stream);     // prop_keep_kernel.hip: without STOP_PHOTONS_ON_DETECTION
-size_t prop_kernel_max_lanes();
-size_t prop_kernel_lds_budget();
 
 class McpeGenerator;            // mcpe.h
 struct alignas(16) SeriesParticle16 { uint8_t bytes[16]; };     // 16-byte aligned storage for a bunch's table and mask (mcpe_series.h)

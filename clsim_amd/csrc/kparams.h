@@ -68,7 +68,7 @@ struct KParams {
     int32_t k_wait;                     // ... or trips the first of them has waited (whichever comes first)
     int32_t k_aim;                      // segment_misses_string is asked when at most this many lanes of the wave reach a string's cylinder
     int32_t slices;                     // a step is handed out in this many slices (1 = whole steps)
-    // pooled kernel (prop_pool_kernel.hip): entries of a wave's ring of ready photons, and how many lanes must be
+    // pooled kernel (prop_pool_kernel.hip.h): entries of a wave's ring of ready photons, and how many lanes must be
     // without a photon before the wave services them; k_new is its creation batch there (0 = automatic everywhere)
     int32_t pool_ready, k_pop;
     int32_t chip_share;                 // launch geometry only: this launch may fill 1/chip_share of the chip (0, 1: all of it)
@@ -192,7 +192,7 @@ struct KParams {
     uint32_t tab_tiled, tab_tile_stride[3];     // strides of b0 >> e0, b1, b2 >> e2 (b3 >> e3 has stride 8)
     uint32_t tab_tile_bits[3];                  // e0, e2, e3: a sector holds 2^e0 x 2^e2 x 2^e3 bins of axes 0, 2, 3 (e0 + e2 + e3 = 3)
     // (round 6) the standard table: spherical axes, folded azimuth, square-root axes 0 and 3, identity axes 1 and 2, tiled 4 x 2 x 1, no squared
-    // weights -- the four-axis kernel then runs the sampler specialised for it (prop_kernel.hip: sample_bin<..., STD>); set by tabulator.cpp
+    // weights -- the four-axis kernel then runs the sampler specialised for it (prop_kernel.hip.h: sample_bin<..., STD>); set by tabulator.cpp
     uint32_t tab_std;
     float tab_max0, tab_max3, tab_min_inv_groupvel, tab_tan_thetac, tab_volume_step;
     int32_t ang_n;                      // getAngularAcceptance polynomial (coefficients in the LDS image)
@@ -239,7 +239,7 @@ struct KVariant {
     // launch tuning (clsimhip_set_tuning / clsimhip_tabulator_set_tuning; 0 / false = automatic).  Never part of a result.
     int grid = 0;                   // workgroups of the propagation launch ("grid")
     bool generic_only = false;      // the generic instantiation also where Compile() found every proof ("generic_kernels")
-    bool tab_fast = false;          // table maker: the FAST instantiation (measured slower, prop_kernel.hip: launch_tab_kernel) ("fast_kernels")
+    bool tab_fast = false;          // table maker: the FAST instantiation (measured slower, prop_tab_kernel.hip: launch_tab_kernel) ("fast_kernels")
     KLaunched *launched = nullptr;  // where the launcher reports the instantiation it took (host memory of the caller; may be null)
 };
 

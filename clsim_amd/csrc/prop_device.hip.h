@@ -1,5 +1,5 @@
-// Device functions of the photon propagator, shared by the kernels in prop_kernel.hip (classic register-resident
-// scheduling, TABULATE variants) and prop_pool_kernel.hip (per-wave photon pools): the arithmetic of
+// Device functions of the photon propagator, shared by the kernels in prop_kernel.hip.h (classic register-resident
+// scheduling, TABULATE variants) and prop_pool_kernel.hip.h (per-wave photon pools): the arithmetic of
 //   resources/kernels/propagation_kernel.c.cl:73-404, 546-696, sparse_collision_kernel.c.cl:27-587,
 //   mwcrng_kernel.cl:12-28 and the generated medium / spectrum / geometry functions,
 // each function citing the lines it restates.  Scheduling lives in the kernels; nothing here depends on it.
@@ -134,6 +134,24 @@ DM int clamp_index(int v, int hi)
     int r;
     asm("v_med3_i32 %0, %1, 0, %2" : "=v"(r) : "v"(v), "s"(hi));
     return r;
+}
+// Axis::GetIndexCode (Axes.cxx:69-90, Axis.cxx:45-60): clamp(convert_int_sat_rtn(t), -1, n) + 1 for t = scale * inverse(x) - offset.
+// axis_bin_generic_ spells the saturating floor conversion out (NaN -> 0, beyond the int range -> its ends); axis_bin_ is the same
+// function in four instructions -- v_cvt_flr_i32_f32 floors and saturates by itself -- which
+// clsimhip_check_math_exhaustive(19) compares on ALL 2^32 bit patterns on the device (tests/test_detmath_gpu.py).
+DM uint32_t axis_bin_generic_(float t, int nbins)
+{
+    const float f = __builtin_floorf(t);
+    const int b = (f != f) ? 0 : ((f >= 2147483648.0f) ? 2147483647 : ((f < -2147483648.0f) ? (-2147483647 - 1) : (int)f));
+    return (uint32_t)(clampi(b, -1, nbins) + 1);
+}
+DM uint32_t axis_bin_(float t, int nbins)
+{
+    int b, r;
+    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(b) : "v"(t));
+    b = (t != t) ? 0 : b;                                               // (the instruction does not send NaN to 0: measured)
+    asm("v_med3_i32 %0, %1, -1, %2" : "=v"(r) : "v"(b), "s"(nbins));
+    return (uint32_t)(r + 1);
 }
 
 struct Vec3 { float x, y, z; };

@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "prop_device.hip.h"
+#include "prop_launch.h"
 #include "../../include/clsimhip.h"
 
 namespace clsimhip {
@@ -100,20 +101,15 @@ hipError_t launch_eval_function(const KParams &P, int lengths_kind, bool has_til
     const size_t lds = (size_t)P.table_words * 4;
     const dim3 grid((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024), block(256);
     if (lds > 160u * 1024u) return hipErrorInvalidValue;
-    // (an image beyond 64 KB -- a detector of several hundred strings -- needs the attribute, like the propagation kernels' launch_variant)
-#define BIG(kernel) \
-    if (lds > 64u * 1024u) { const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); if (e != hipSuccess) return e; }
-#define GO(m) \
-    if (fast) { BIG((eval_function_kernel<m, true>)) hipLaunchKernelGGL((eval_function_kernel<m, true>), grid, block, lds, stream, P, what, layer, (int)has_tilt, in, n, out); } \
-    else { BIG((eval_function_kernel<m, false>)) hipLaunchKernelGGL((eval_function_kernel<m, false>), grid, block, lds, stream, P, what, layer, (int)has_tilt, in, n, out); }
-    switch (lengths_kind) {
-    case CLSIMHIP_LENGTHS_CONSTANT: GO(CLSIMHIP_LENGTHS_CONSTANT) break;
-    case CLSIMHIP_LENGTHS_ICECUBE: GO(CLSIMHIP_LENGTHS_ICECUBE) break;
-    case CLSIMHIP_LENGTHS_TABLE: GO(CLSIMHIP_LENGTHS_TABLE) break;
-    default: return hipErrorInvalidValue;
-    }
-#undef GO
-    return hipGetLastError();
+    return dispatch_lengths(lengths_kind, [&](auto med) {
+        return dispatch_fast(fast, [&](auto fast_tag) {
+            const auto kernel = &eval_function_kernel<med(), fast_tag()>;
+            // (an image beyond 64 KB -- a detector of several hundred strings -- needs the attribute, like the propagation kernels' launch_variant)
+            if (const hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(kernel), lds)) return e;
+            hipLaunchKernelGGL(kernel, grid, block, lds, stream, P, what, layer, (int)has_tilt, in, n, out);
+            return hipGetLastError();
+        });
+    });
 }
 
 hipError_t launch_eval_random(const KParams &P, bool fast, int what, int generator, uint64_t *x, const uint32_t *a, uint32_t n_streams, uint32_t draws,
@@ -123,10 +119,12 @@ hipError_t launch_eval_random(const KParams &P, bool fast, int what, int generat
     const size_t lds = (size_t)P.table_words * 4;
     const dim3 grid((n_streams + 255) / 256 < 1024 ? (n_streams + 255) / 256 : 1024), block(256);
     if (lds > 160u * 1024u) return hipErrorInvalidValue;
-    if (fast) { BIG((eval_random_kernel<true>)) hipLaunchKernelGGL((eval_random_kernel<true>), grid, block, lds, stream, P, what, generator, x, a, n_streams, draws, out); }
-    else { BIG((eval_random_kernel<false>)) hipLaunchKernelGGL((eval_random_kernel<false>), grid, block, lds, stream, P, what, generator, x, a, n_streams, draws, out); }
-    return hipGetLastError();
-#undef BIG
+    return dispatch_fast(fast, [&](auto fast_tag) {
+        const auto kernel = &eval_random_kernel<fast_tag()>;
+        if (const hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(kernel), lds)) return e;
+        hipLaunchKernelGGL(kernel, grid, block, lds, stream, P, what, generator, x, a, n_streams, draws, out);
+        return hipGetLastError();
+    });
 }
 
 } // namespace clsimhip

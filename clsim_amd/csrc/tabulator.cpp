@@ -336,7 +336,7 @@ void Tabulator::bin_content_double(double *out, size_t n, bool squared)
         hip_check(hipMemcpy(out, squared ? d_sq_bins_.get() : d_bins_.get(), n * sizeof(double), hipMemcpyDeviceToHost), "download table");
         return;
     }
-    // the device's tiled order -> the reference's (sample_bin in prop_kernel.hip forms the same index)
+    // the device's tiled order -> the reference's (sample_bin in prop_kernel.hip.h forms the same index)
     std::vector<double> device(n_device_bins_);
     hip_check(hipMemcpy(device.data(), squared ? d_sq_bins_.get() : d_bins_.get(), n_device_bins_ * sizeof(double), hipMemcpyDeviceToHost), "download table");
     size_t at = 0;

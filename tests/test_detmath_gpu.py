@@ -120,7 +120,7 @@ def test_range_restricted_operations_equal_the_ieee_ones_on_every_input(what, ex
 
 
 def test_axis_bin_conversion_equals_the_spelled_out_one_on_every_bit_pattern():
-    """The table maker's axis_bin_ (prop_kernel.hip: v_cvt_flr_i32_f32 + v_med3_i32) against the generic saturating floor
+    """The table maker's axis_bin_ (prop_device.hip.h: v_cvt_flr_i32_f32 + v_med3_i32) against the generic saturating floor
     conversion and clamp of Axis::GetIndexCode (Axis.cxx:45-60): all 2^32 bit patterns -- NaNs, infinities, denormals,
     both signs -- x five bin counts."""
     bad, first = check_exhaustive(19, 0, 0)

@@ -22,7 +22,8 @@ def test_every_experiment_patch_applies():
 
 def test_kernel_sources_hold_no_experiment_switch_and_no_instrumentation_ifdef():
     src = os.path.join(ROOT, "clsim_amd", "csrc")
-    for name in ("prop_kernel.hip", "prop_pool_kernel.hip", "prop_device.hip.h", "detmath.hip.h", "steps_kernel.hip"):
+    for name in ("prop_kernel.hip.h", "prop_pool_kernel.hip.h", "prop_kernel.hip", "prop_keep_kernel.hip", "prop_tab_kernel.hip", "prop_pool_kernel.hip",
+                 "prop_pool_keep_kernel.hip", "prop_aux_kernels.hip", "prop_device.hip.h", "detmath.hip.h", "steps_kernel.hip"):
         text = open(os.path.join(src, name)).read()
         assert "CLSIMHIP_EXP_" not in text, name
         for m in re.finditer(r"^\s*#\s*if(?:def|ndef)?\s+(.*)$", text, re.M):

@@ -15,7 +15,7 @@ CASES = [(key, mode) for key in KM.KEYS for mode in KM.MODES]
 
 def test_the_matrix_has_every_key_of_the_dispatchers_once():
     assert len(KM.KEYS) == len(set(KM.KEYS)) == 24 and len(KM.TAB_KEYS) == 12 and len(CASES) == 48
-    # the launchers' switch: key = 8 * lengths + 4 * tilt + 2 * aniso + flasher (prop_kernel.hip: launch_prop_kernel)
+    # the launchers' dispatch over lengths x tilt x aniso x flasher, numbered key = 8 * lengths + 4 * tilt + 2 * aniso + flasher (prop_launch.h: dispatch_variant)
     assert sorted(8 * KM.LENGTHS.index(l) + 4 * t + 2 * a + f for l, t, a, f in KM.KEYS) == list(range(24))
     assert KM.LENGTHS == _lib.LENGTHS_KINDS and KM.NO_FAST_KEYS <= set(KM.KEYS)
 

@@ -1,4 +1,4 @@
-"""GPU parity of the pooled propagation kernel (clsim_amd/csrc/prop_pool_kernel.hip, CLSIMHIP_KERNEL=pool): same bar as
+"""GPU parity of the pooled propagation kernel (clsim_amd/csrc/prop_pool_kernel.hip.h, CLSIMHIP_KERNEL=pool): same bar as
 tests/test_parity_gpu.py -- the sorted multiset of 80-byte photon records and the RNG state words left behind are
 BIT-IDENTICAL to the CPU oracle's -- for every ring size, service threshold and creation batch, and equal to the classic
 kernel's output on bunches too large for the oracle."""

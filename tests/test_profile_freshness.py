@@ -11,6 +11,8 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNEL_FILES = ["clsim_amd/csrc/prop_kernel.hip", "clsim_amd/csrc/prop_pool_kernel.hip", "clsim_amd/csrc/prop_tab_kernel.hip",
+                "clsim_amd/csrc/prop_kernel.hip.h", "clsim_amd/csrc/prop_pool_kernel.hip.h", "clsim_amd/csrc/prop_aux_kernels.hip",
+                "clsim_amd/csrc/prop_launch.h",
                 "clsim_amd/csrc/prop_keep_kernel.hip", "clsim_amd/csrc/prop_pool_keep_kernel.hip",
                 "clsim_amd/csrc/prop_device.hip.h", "clsim_amd/csrc/detmath.hip.h", "clsim_amd/csrc/kparams.h", "clsim_amd/csrc/Makefile"]
 

@@ -159,7 +159,7 @@ def test_fast_table_instantiations_match_the_oracle_too(kind, ice):
                                                            ("spherical_small", "lea", 0.5, False)])
 def test_standard_table_sampler_matches_the_oracle(kind, ice, step_length, standard):
     """round 6: a table of the reference's default shape (spherical, folded azimuth, square-root distance and time axes, no squared weights:
-    python/tablemaker/tabulator.py:621-641) runs the sampler specialised for it (prop_kernel.hip: sample_bin<..., STD>); with
+    python/tablemaker/tabulator.py:621-641) runs the sampler specialised for it (prop_kernel.hip.h: sample_bin<..., STD>); with
     clsimhip_tabulator_set_tuning("standard_sampler", 0) the generic one.  Both against the oracle, same bar as every other table."""
     check_table_against_the_oracle(kind, ice, step_length, squared=False, standard_sampler=standard)
 
@@ -239,7 +239,7 @@ def check_product_table(cfg, kind, okind, o, p, tb, steps, streams, xo, ref7, st
     for bunch in range(2):
         tab.EnqueueSteps(steps, ref7)
         if launch_key is not None:
-            # the instantiation the launch took: FAST only when asked for AND proven (prop_kernel.hip: launch_tab_kernel)
+            # the instantiation the launch took: FAST only when asked for AND proven (prop_tab_kernel.hip: launch_tab_kernel)
             want = dict(family="tab5" if len(o) > 4 else "tab4", lengths=launch_key[0], tilt=launch_key[1], aniso=launch_key[2], flasher=True,
                         fast=bool(fast_kernels) and int(tab.GetTable("fast_variant")[0]) == 1)
             assert tab.GetLastLaunch() == want, (tab.GetLastLaunch(), want)

@@ -9,7 +9,7 @@ set -e
 cd "$(dirname "$0")/../clsim_amd/csrc"
 name=$1; shift
 if [ -n "$PATCH" ]; then (cd ../.. && git apply "$PATCH") || exit 1; fi
-if [ -n "$POOL_ONLY" ]; then touch prop_pool_kernel.hip; else touch prop_pool_kernel.hip prop_kernel.hip; fi
+if [ -n "$POOL_ONLY" ]; then touch prop_pool_kernel.hip.h; else touch prop_pool_kernel.hip.h prop_kernel.hip.h prop_aux_kernels.hip; fi
 touch converter.cpp tabulator.cpp feeder.cpp
 make -j8 DEVELOPER=1 EXTRA="$*" 2>&1 | grep -E "error|warning: (variable|unused)" || true
 mkdir -p ../../build_variants
@@ -18,5 +18,5 @@ echo "built build_variants/$name.so with: $*"
 # leave the default build behind, not the variant
 if [ -n "$PATCH" ]; then (cd ../.. && git apply -R "$PATCH"); fi
 touch converter.cpp tabulator.cpp feeder.cpp
-if [ -n "$POOL_ONLY" ]; then touch prop_pool_kernel.hip; else touch prop_pool_kernel.hip prop_kernel.hip; fi
+if [ -n "$POOL_ONLY" ]; then touch prop_pool_kernel.hip.h; else touch prop_pool_kernel.hip.h prop_kernel.hip.h prop_aux_kernels.hip; fi
 make -j8 2>&1 | grep -E "error" || true

@@ -2,7 +2,7 @@
 """Basic blocks of one kernel with their instruction counts and the source lines most of their instructions come from.
 ANALYSIS TOOL (no GPU needed).
 
-  cd clsim_amd/csrc && hipcc <the Makefile's flags for the file> --cuda-device-only -gline-tables-only -S -o /tmp/pool_g.s prop_pool_kernel.hip
+  cd clsim_amd/csrc && hipcc <the Makefile's flags for the file> --cuda-device-only -gline-tables-only -S -o /tmp/pool_g.s prop_pool_kernel.hip      (the kernel's lines are in prop_pool_kernel.hip.h)
   tools/isa_basic_blocks.py /tmp/pool_g.s '_ZN8clsimhip16prop_pool_kernelILi1ELb1ELb0ELb0ELb1EEEvNS_7KParamsE'
 
 Columns: label, vector ALU, scalar (incl. branches), other (LDS / memory / waitcnt), branch targets, the three source lines

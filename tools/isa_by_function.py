@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Static instruction counts of one kernel, by the source function each instruction was inlined from.
 
-  hipcc ... --cuda-device-only -gline-tables-only -S -o pool_g.s prop_pool_kernel.hip
+  hipcc ... --cuda-device-only -gline-tables-only -S -o pool_g.s prop_pool_kernel.hip      (the kernel's lines are in prop_pool_kernel.hip.h)
   tools/isa_by_function.py pool_g.s '_ZN8clsimhip16prop_pool_kernelILi1ELb1ELb0ELb0ELb1EEEvNS_7KParamsE'
 
 Columns: vector ALU, scalar ALU (incl. exec-mask work), branches, s_waitcnt, s_nop, scalar loads, LDS, vector memory.
