@@ -128,6 +128,8 @@ SYMBOLS = [
     "clsimhip_mcpe_convert_host", "clsimhip_mcpe_convert_device", "clsimhip_set_mcpe_generator", "clsimhip_get_result_mcpes",
     "clsimhip_mcpe_series_host", "clsimhip_mcpe_series_workspace_bytes", "clsimhip_mcpe_series_device", "clsimhip_set_mcpe_series",
     "clsimhip_enqueue_steps_with_particles", "clsimhip_get_result_mcpe_series",
+    "clsimhip_pmt_generator_create", "clsimhip_pmt_generator_destroy", "clsimhip_pmt_generator_last_error",
+    "clsimhip_pmt_convert_host", "clsimhip_pmt_convert_device", "clsimhip_set_pmt_generator", "clsimhip_get_result_pmt_hits",
 ]
 
 # clsimhip_get_last_launch: CLSIMHIP_FAMILY_* and CLSIMHIP_LENGTHS_* by name
@@ -298,6 +300,13 @@ def load():
         "clsimhip_set_mcpe_series": (i32, [vp, i32]),
         "clsimhip_enqueue_steps_with_particles": (i32, [vp, vp, sz, u32, vp, sz, vp, sz]),
         "clsimhip_get_result_mcpe_series": (i32, [vp, vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(u64)]),
+        "clsimhip_pmt_generator_create": (i32, [C.POINTER(Function), sz, vp, sz, vp, sz, vp, sz, u64, C.POINTER(vp)]),
+        "clsimhip_pmt_generator_destroy": (None, [vp]),
+        "clsimhip_pmt_generator_last_error": (C.c_char_p, [vp]),
+        "clsimhip_pmt_convert_host": (i32, [vp, vp, sz, vp, sz, C.POINTER(sz), vp]),
+        "clsimhip_pmt_convert_device": (i32, [vp, i32, vp, vp, sz, vp, sz, vp, vp]),
+        "clsimhip_set_pmt_generator": (i32, [vp, vp, i32]),
+        "clsimhip_get_result_pmt_hits": (i32, [vp, vp, C.POINTER(vp), C.POINTER(sz)]),
         "clsimhip_tabulator_write_fits_file": (i32, [vp, C.c_char_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double), sz]),
     }
     for name in SYMBOLS:

@@ -426,14 +426,70 @@ class MCPEGenerator:
                                                      int(workspace_bytes), C.c_void_p(stream)))
 
 
+# Multi-PMT hit generator (include/clsimhip.h): clsimhip_pmt_type, clsimhip_pmt, clsimhip_pmt_module and clsimhip_pmt_hit
+PMT_TYPE_DTYPE = np.dtype([("sphereRadius", "<f8"), ("firstPMT", "<i4"), ("numPMTs", "<i4"), ("glassGelSurvival", "<i4"), ("reserved", "<i4")])
+PMT_DTYPE = np.dtype([("axis", "<f8", (3,)), ("position", "<f8", (3,)), ("radius", "<f8"), ("collectionEfficiency", "<f8"),
+                      ("quantumEfficiency", "<i4"), ("angularAcceptance", "<i4")])
+PMT_MODULE_DTYPE = np.dtype([("stringID", "<i4"), ("omID", "<u4"), ("type", "<i4"), ("reserved", "<i4"), ("rotation", "<f8", (9,))])
+PMT_HIT_DTYPE = np.dtype([("id", "<u4"), ("stringID", "<i2"), ("omID", "<u2"), ("pmt", "<u4"), ("reserved", "<u4"), ("time", "<f8")])
+PMT_CONDITIONS = ("unknown_module", "probability_above_one", "off_surface")
+
+
+class PMTHitGenerator:
+    """Detected photons -> hits on the PMTs of segmented modules (clsimhip_pmt_generator): FindHitPMT and the per-photon body of
+    I3PhotonToMCHitConverterForMultiPMT::DAQ (private/clsim/dom/I3PhotonToMCHitConverterForMultiPMT.cxx:111-227, 297-382) as a
+    function of the record and a seed.
+
+    functions: up to 64 I3CLSimFunctionFromTable (equal spacing) / I3CLSimFunctionConstant, named by index; types (PMT_TYPE_DTYPE):
+    sphere radius, the type's PMTs in `pmts` and its glass / gel survival; pmts (PMT_DTYPE): axis, position, radius, collection
+    efficiency, quantum efficiency over the wavelength and angular acceptance factor over the cosine of the hit angle; modules
+    (PMT_MODULE_DTYPE): type and rotation (row-major, module frame -> detector frame) of every (string ID, OM ID).  Give it to
+    initializeHIP(..., pmtHitGenerator=...) to run on the GPU behind the propagator, or call ConvertHost / ConvertDevice on records."""
+
+    def __init__(self, functions, types, pmts, modules, seed=0):
+        self._lib = _lib.load()
+        self._h = C.c_void_p()
+        self._keep = list(functions)
+        descs = (_lib.Function * max(len(self._keep), 1))(*[f._desc() for f in self._keep])
+        types = np.ascontiguousarray(types, dtype=PMT_TYPE_DTYPE)
+        pmts = np.ascontiguousarray(pmts, dtype=PMT_DTYPE)
+        modules = np.ascontiguousarray(modules, dtype=PMT_MODULE_DTYPE)
+        _check(self._lib.clsimhip_pmt_generator_create(descs, len(self._keep), types.ctypes.data_as(C.c_void_p), len(types),
+                                                       pmts.ctypes.data_as(C.c_void_p), len(pmts), modules.ctypes.data_as(C.c_void_p), len(modules),
+                                                       int(seed), C.byref(self._h)))
+
+    def __del__(self):
+        try:
+            if self._h:
+                self._lib.clsimhip_pmt_generator_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def ConvertHost(self, photons):
+        """(hits, counters): the host twin, in input order; counters = {condition: count} (PMT_CONDITIONS)"""
+        photons = np.ascontiguousarray(photons, dtype=PHOTON_DTYPE)
+        out = np.zeros(len(photons), dtype=PMT_HIT_DTYPE)
+        n, counters = C.c_size_t(), np.zeros(3, dtype=np.uint64)
+        _check(self._lib.clsimhip_pmt_convert_host(self._h, photons.ctypes.data_as(C.c_void_p), len(photons), out.ctypes.data_as(C.c_void_p),
+                                                   len(out), C.byref(n), counters.ctypes.data_as(C.c_void_p)))
+        return out[:n.value], dict(zip(PMT_CONDITIONS, (int(c) for c in counters)))
+
+    def ConvertDevice(self, d_photons, d_hit_count, capacity, d_hits, hit_capacity, d_counters, device=0, stream=0):
+        """the kernel on device-resident records (addresses); d_counters: four uint32, [0] hits made, [1..3] PMT_CONDITIONS"""
+        _check(self._lib.clsimhip_pmt_convert_device(self._h, int(device), C.c_void_p(d_photons), C.c_void_p(d_hit_count), int(capacity),
+                                                     C.c_void_p(d_hits), int(hit_capacity), C.c_void_p(d_counters), C.c_void_p(stream)))
+
+
 class ConversionResult(tuple):
     """What GetConversionResult / GetConversionResultInPlace return: the tuple (identifier, photons[, histories]) / (identifier,
     photons, release), with the bunch's MCPEs (MCPE_DTYPE) as attribute `mcpes` when the converter has an MCPE generator (None
     otherwise).  With the MCPE series stage `mcpes` are the sorted records, `series` their series table (MCPE_SERIES_DTYPE) and
-    `masked` the bunch's MASKED count."""
+    `masked` the bunch's MASKED count.  With a PMT hit generator `pmt_hits` holds the bunch's hits (PMT_HIT_DTYPE)."""
     mcpes = None
     series = None
     masked = None
+    pmt_hits = None
 
 
 class I3CLSimStepToPhotonConverterHIP:
@@ -446,6 +502,7 @@ class I3CLSimStepToPhotonConverterHIP:
         self._history_entries = 0
         self._mcpe = None
         self._series = False
+        self._pmt = None
 
     def __del__(self):
         try:
@@ -496,6 +553,11 @@ class I3CLSimStepToPhotonConverterHIP:
         the device (the client module's two switches, frame->photons / frame->hits)"""
         self._call("clsimhip_set_mcpe_generator", generator._h if generator is not None else None, int(bool(keepPhotons)))
         self._mcpe = generator
+    def SetPMTHitGenerator(self, generator, keepPhotons=True):
+        """generator: a PMTHitGenerator or None (off); keepPhotons as for SetMCPEGenerator.  Before Initialize() only; Compile()
+        refuses it beside an MCPE generator."""
+        self._call("clsimhip_set_pmt_generator", generator._h if generator is not None else None, int(bool(keepPhotons)))
+        self._pmt = generator
     def SetMCPESeries(self, on=True):
         """the sorting stage behind the MCPE generator: every result's MCPEs come back as per-frame, per-DOM time-sorted series
         (result attributes `mcpes`, `series`, `masked`).  Before Initialize() only; Compile() refuses it without a generator."""
@@ -555,6 +617,21 @@ class I3CLSimStepToPhotonConverterHIP:
             C.memmove(mcpes.ctypes.data, mp.value, mn.value * 16)
         return mcpes
 
+    def _result_pmt_hits(self, ptr):
+        """copy of the PMT hits of the result `ptr` belongs to (None without a PMT hit generator)"""
+        if self._pmt is None:
+            return None
+        hp, hn = C.c_void_p(), C.c_size_t()
+        self._call("clsimhip_get_result_pmt_hits", ptr, C.byref(hp), C.byref(hn))
+        hits = np.zeros(hn.value, dtype=PMT_HIT_DTYPE)
+        if hn.value:
+            C.memmove(hits.ctypes.data, hp.value, hn.value * 24)
+        return hits
+
+    def _has_handle(self):
+        """a result without photon records still has a handle to release when a hit maker is attached"""
+        return self._mcpe is not None or self._pmt is not None
+
     def GetConversionResult(self, with_histories=False, out=None):
         """ConversionResult_t (I3CLSimStepToPhotonConverter.h:70-90): (identifier, photons), plus with
         with_histories=True the photonHistories as a list of [k_i, 4] arrays (k_i = min(numScatters_i,
@@ -589,11 +666,13 @@ class I3CLSimStepToPhotonConverterHIP:
                 if with_histories and self._history_entries:
                     histories = []
             mcpes = self._result_mcpes(ptr)
+            pmt_hits = self._result_pmt_hits(ptr)
         finally:
-            if n.value or self._mcpe is not None:
+            if n.value or self._has_handle():
                 self._call("clsimhip_release_result", ptr)
         result = ConversionResult((ident.value, photons, histories) if with_histories else (ident.value, photons))
         self._attach_mcpes(result, mcpes)
+        result.pmt_hits = pmt_hits
         return result
 
     def GetConversionResultInPlace(self):
@@ -605,12 +684,13 @@ class I3CLSimStepToPhotonConverterHIP:
         self._call("clsimhip_get_conversion_result", C.byref(ident), C.byref(ptr), C.byref(n))
         try:
             mcpes = self._result_mcpes(ptr)
+            pmt_hits = self._result_pmt_hits(ptr)
         except Exception:
-            if n.value or self._mcpe is not None:
+            if n.value or self._has_handle():
                 self._call("clsimhip_release_result", ptr)
             raise
         if not n.value:
-            if self._mcpe is not None:          # (the handle of a result without photon records)
+            if self._has_handle():              # (the handle of a result without photon records)
                 self._call("clsimhip_release_result", ptr)
             result = ConversionResult((ident.value, np.zeros(0, dtype=PHOTON_DTYPE), (lambda: None)))
         else:
@@ -619,6 +699,7 @@ class I3CLSimStepToPhotonConverterHIP:
             view.flags.writeable = False
             result = ConversionResult((ident.value, view, (lambda: self._call("clsimhip_release_result", ptr))))
         self._attach_mcpes(result, mcpes)
+        result.pmt_hits = pmt_hits
         return result
 
     def _attach_mcpes(self, result, mcpes):
@@ -769,11 +850,12 @@ def initializeHIP(device, geometry, medium, wavelengthGenerationBias, wavelength
                   enableDoubleBuffering=False, doublePrecision=False, stopDetectedPhotons=True, saveAllPhotons=False,
                   saveAllPhotonsPrescale=0.01, fixedNumberOfAbsorptionLengths=float("nan"), pancakeFactor=1.0,
                   photonHistoryEntries=0, limitWorkgroupSize=0, approximateNumberOfWorkItems=262144,
-                  seed=12345, streams=None, tuning=None, mcpeGenerator=None, keepPhotons=True, mcpeSeries=False):
+                  seed=12345, streams=None, tuning=None, mcpeGenerator=None, keepPhotons=True, mcpeSeries=False, pmtHitGenerator=None):
     """Canonical configuration sequence, I3CLSimModuleHelper::initializeOpenCL
     (ModuleHelper.cxx:303-372).  tuning: {key: value} for clsimhip_set_tuning, applied before Compile().
     mcpeGenerator: an MCPEGenerator that turns every bunch's photons into MCPEs on the GPU (result attribute `mcpes`);
-    keepPhotons=False then leaves the photon records on the device; mcpeSeries=True sorts them into per-frame, per-DOM series."""
+    keepPhotons=False then leaves the photon records on the device; mcpeSeries=True sorts them into per-frame, per-DOM series.
+    pmtHitGenerator: a PMTHitGenerator instead, for modules with several PMTs (result attribute `pmt_hits`; keepPhotons as above)."""
     conv = I3CLSimStepToPhotonConverterHIP(device)
     for key, value in (tuning or {}).items():
         conv.SetTuning(key, value)
@@ -793,6 +875,8 @@ def initializeHIP(device, geometry, medium, wavelengthGenerationBias, wavelength
         conv.SetMCPEGenerator(mcpeGenerator, keepPhotons)
     if mcpeSeries:
         conv.SetMCPESeries(True)
+    if pmtHitGenerator is not None:
+        conv.SetPMTHitGenerator(pmtHitGenerator, keepPhotons)
     conv.Compile()
     max_wg = conv.GetMaxWorkgroupSize()
     if limitWorkgroupSize:

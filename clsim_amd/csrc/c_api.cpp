@@ -13,12 +13,14 @@
 #include "step_store.h"
 #include "flasher.h"
 #include "mcpe.h"
+#include "pmt_hits.h"
 
 using namespace clsimhip;
 
 struct clsimhip_converter { Converter impl; explicit clsimhip_converter(int dev) : impl(dev) {} };
 struct clsimhip_medium { MediumData data; };
 struct clsimhip_mcpe_generator { std::shared_ptr<McpeGenerator> impl; };
+struct clsimhip_pmt_generator { std::shared_ptr<PmtHitGenerator> impl; };
 struct clsimhip_tabulator {
     std::unique_ptr<Tabulator> impl;
 };
@@ -1017,6 +1019,46 @@ int clsimhip_get_result_mcpe_series(clsimhip_converter *c, const clsimhip_photon
                                     const clsimhip_mcpe_series **series, size_t *n_series, uint64_t *n_masked)
 {
     return guarded(c, [&] { need(c, "converter"); c->impl.result_mcpe_series(photons, mcpes, n, series, n_series, n_masked); });
+}
+
+// ---- Multi-PMT hit generator (pmt_hits.h) ----
+int clsimhip_pmt_generator_create(const clsimhip_function *functions, size_t n_functions, const clsimhip_pmt_type *types, size_t n_types,
+                                  const clsimhip_pmt *pmts, size_t n_pmts, const clsimhip_pmt_module *modules, size_t n_modules,
+                                  uint64_t seed, clsimhip_pmt_generator **out)
+{
+    return guarded(nullptr, [&] {
+        need(functions, "functions"); need(types, "types"); need(pmts, "pmts"); need(out, "out");
+        std::vector<FunctionData> fs;
+        for (size_t k = 0; k < n_functions; ++k) fs.push_back(function_from(functions + k));
+        *out = new clsimhip_pmt_generator{std::make_shared<PmtHitGenerator>(fs, types, n_types, pmts, n_pmts, modules, n_modules, seed)};
+    });
+}
+void clsimhip_pmt_generator_destroy(clsimhip_pmt_generator *g) { delete g; }
+const char *clsimhip_pmt_generator_last_error(const clsimhip_pmt_generator *g) { (void)g; return g_last_error.c_str(); }
+int clsimhip_pmt_convert_host(const clsimhip_pmt_generator *g, const clsimhip_photon *photons, size_t n, clsimhip_pmt_hit *out,
+                              size_t capacity, size_t *n_out, uint64_t counters[3])
+{
+    return guarded(nullptr, [&] {
+        need(g, "generator");
+        if (counters) std::memset(counters, 0, 3 * sizeof(uint64_t));
+        g->impl->convert_host(photons, n, out, capacity, n_out, counters);
+    });
+}
+int clsimhip_pmt_convert_device(clsimhip_pmt_generator *g, int device, const void *d_photons, const void *d_hit_count, size_t capacity,
+                                void *d_hits, size_t hit_capacity, void *d_counters, void *hip_stream)
+{
+    return guarded(nullptr, [&] {
+        need(g, "generator");
+        g->impl->convert_device(device, d_photons, d_hit_count, capacity, d_hits, hit_capacity, d_counters, static_cast<hipStream_t>(hip_stream));
+    });
+}
+int clsimhip_set_pmt_generator(clsimhip_converter *c, clsimhip_pmt_generator *g, int keep_photons)
+{
+    return guarded(c, [&] { need(c, "converter"); c->impl.set_pmt_generator(g ? g->impl : std::shared_ptr<PmtHitGenerator>(), keep_photons != 0); });
+}
+int clsimhip_get_result_pmt_hits(clsimhip_converter *c, const clsimhip_photon *photons, const clsimhip_pmt_hit **hits, size_t *n)
+{
+    return guarded(c, [&] { need(c, "converter"); c->impl.result_pmt_hits(photons, hits, n); });
 }
 
 } // extern "C"

@@ -5,6 +5,7 @@
 // is on the GPU while the previous one is downloaded and converted.
 #include "converter.h"
 #include "mcpe.h"
+#include "pmt_hits.h"
 
 #include <chrono>
 #include <cmath>
@@ -156,6 +157,7 @@ void Converter::release_device()
     result_pool_.reset();
     mcpe_pool_.reset();
     series_pool_.reset();
+    pmt_pool_.reset();
     bunch_pool_.reset();
 }
 
@@ -222,6 +224,14 @@ void Converter::set_mcpe_generator(std::shared_ptr<McpeGenerator> g, bool keep_p
     keep_photons_ = keep_photons;
 }
 
+void Converter::set_pmt_generator(std::shared_ptr<PmtHitGenerator> g, bool keep_photons)
+{
+    guard();
+    compiled_ = false;
+    pmt_ = std::move(g);
+    pmt_keep_photons_ = keep_photons;
+}
+
 void Converter::set_workgroup_size(size_t v)
 {
     guard();
@@ -281,6 +291,28 @@ void Converter::compile()
         // records of a converter with another pancake factor sit at another radius: every one of them would be OFF_SURFACE
         if (mcpe_->pancake() != pancake_)
             throw Error(CLSIMHIP_ERR_CONFIG, "MCPE generator: made for DOM pancake factor " + std::to_string(mcpe_->pancake()) + ", the converter's is " + std::to_string(pancake_));
+    }
+    if (pmt_) {
+        if (mcpe_) throw Error(CLSIMHIP_ERR_CONFIG, "a converter takes an MCPE generator or a PMT hit generator, not both");
+        if (series_) throw Error(CLSIMHIP_ERR_CONFIG, "MCPE series are not made from PMT hits (clsimhip_set_mcpe_series with a PMT hit generator)");
+        // as for the MCPE generator: every DOM's pair must fit the records and must have a module (log_fatal per module in the
+        // reference, I3PhotonToMCHitConverterForMultiPMT.cxx:281-287)
+        for (size_t i = 0; i < geometry_.string_ids.size(); ++i) {
+            const int32_t sid = geometry_.string_ids[i];
+            const uint32_t did = geometry_.dom_ids[i];
+            if (sid < -32768 || sid > 32767 || did > 65535u)
+                throw Error(CLSIMHIP_ERR_CONFIG, "PMT hit generator: string ID " + std::to_string(sid) + " / OM ID " + std::to_string(did) + " does not fit the photon record");
+            if (!pmt_->has_module(sid, did))
+                throw Error(CLSIMHIP_ERR_CONFIG, "No module configured for OMKey(" + std::to_string(sid) + "," + std::to_string(did) + ")");
+        }
+        // records sit at the geometry's (oversized) OM radius, flattened by the pancake factor: a type made for another radius would
+        // find every record OFF_SURFACE and its discs in the wrong places
+        const double recorded_at = geometry_.om_radius / pancake_;
+        for (double radius : pmt_->used_sphere_radii())
+            if (!(std::fabs(radius - recorded_at) <= 0.03))
+                throw Error(CLSIMHIP_ERR_CONFIG, "PMT hit generator: a module type's sphere radius is " + std::to_string(radius) + " m, photons are recorded at " +
+                                                     std::to_string(recorded_at) + " m");
+        if (history_entries_ && !pmt_keep_photons_) throw Error(CLSIMHIP_ERR_CONFIG, "photon histories need keep_photons");
     }
     tables_ = compile_tables(medium_, geometry_, generators_, bias_, pancake_, table_tuning_);
     if (!std::isnan(fixed_abs_lengths_)) {                      // OpenCL.cxx:425-431
@@ -458,6 +490,12 @@ void Converter::setup_device_buffers(DeviceState &D)
             sl.d_mcpes.alloc(max_output_photons_, "MCPEs");
             sl.d_mcpe_counters.alloc(8, "MCPE counters");
             sl.h_mcpe_counters.alloc(8, "pinned MCPE counters");
+        }
+        if (pmt_) {
+            if (!D.id_strings) throw Error(CLSIMHIP_ERR_CONFIG, "PMT hit generator: the geometry has no DOM");
+            sl.d_pmt_hits.alloc(max_output_photons_, "PMT hits");
+            sl.d_pmt_counters.alloc(4, "PMT hit counters");
+            sl.h_pmt_counters.alloc(4, "pinned PMT hit counters");
         }
         if (series_) {
             sl.series_workspace_bytes = mcpe_series_workspace_bytes(max_output_photons_, 0, 0);
@@ -640,6 +678,11 @@ void Converter::submit(Slot &s, Job &job)
                                       s.d_series.get(), s.d_series_counts.get(), s.d_series_workspace.get(), s.series_workspace_bytes, stream);
         hip_check(hipMemcpyAsync(s.h_series_counts.get(), s.d_series_counts.get(), 20, hipMemcpyDeviceToHost, stream), "download MCPE series counts");
     }
+    if (pmt_) {
+        // where the MCPE stage would run: behind assemble_hits_kernel on the bunch's stream, outside the start / stop pair
+        pmt_->convert_device(device_, s.d_photons.get(), s.d_hit_count.get(), max_output_photons_, s.d_pmt_hits.get(), max_output_photons_, s.d_pmt_counters.get(), stream);
+        hip_check(hipMemcpyAsync(s.h_pmt_counters.get(), s.d_pmt_counters.get(), 16, hipMemcpyDeviceToHost, stream), "download PMT hit counters");
+    }
     hip_check(hipEventRecord(s.counted.get(), stream), "event");
 }
 
@@ -684,8 +727,18 @@ void Converter::finish(Slot &s, std::chrono::steady_clock::time_point &last_done
         n_mcpes = std::min(sc[0], max_output_photons_);
         n_series = std::min(sc[1], n_mcpes);
     }
+    uint32_t n_pmt_hits = 0;
+    if (pmt_) {
+        const uint32_t *pc = s.h_pmt_counters.get();       // hits, UNKNOWN_MODULE, PROBABILITY_ABOVE_ONE, OFF_SURFACE
+        if ((pc[1] | pc[2]) != 0u)                          // log_fatal in the reference (I3PhotonToMCHitConverterForMultiPMT.cxx:283, 349)
+            throw Error(CLSIMHIP_ERR_DEVICE, "PMT hit generator, bunch " + std::to_string(s.id) + ": " + std::to_string(pc[1]) + " photons at a module it does not have, " +
+                                                 std::to_string(pc[2]) + " with hit probability above 1");
+        if (pc[3] != 0u)                                    // log_warn in the reference (:140-145)
+            std::fprintf(stderr, "clsimhip: PMT hit generator, bunch %u: %u photons are not within 3 cm of their module's sphere\n", s.id, pc[3]);
+        n_pmt_hits = std::min(pc[0], max_output_photons_);
+    }
     const uint32_t detected = hits;
-    if (mcpe_ && !keep_photons_) hits = 0;              // the records stay on the device
+    if (!carries_photons()) hits = 0;                   // the records stay on the device
     Result r;
     r.count = hits;
     std::unique_ptr<std::vector<clsimhip_photon>> photons;
@@ -730,6 +783,18 @@ void Converter::finish(Slot &s, std::chrono::steady_clock::time_point &last_done
         r.series_count = n_series;
         if (series_) r.masked = s.h_series_counts.get()[3];
         if (!hits) r.handle.reset(new clsimhip_photon());
+    }
+    if (pmt_) {
+        r.pmt_count = n_pmt_hits;
+        if (n_pmt_hits) {
+            r.pmt_pinned = pmt_pool_.take(n_pmt_hits, result_capacity(n_pmt_hits, s.result_min_records), device_);
+            clsimhip_pmt_hit *to = r.pmt_pinned.get();
+            if (!to) { r.pmt_hits.reset(new std::vector<clsimhip_pmt_hit>(n_pmt_hits)); to = r.pmt_hits->data(); }
+            hip_check(hipMemcpyAsync(to, s.d_pmt_hits.get(), static_cast<size_t>(n_pmt_hits) * sizeof(clsimhip_pmt_hit), hipMemcpyDeviceToHost, copy_stream),
+                      "download PMT hits");
+            hip_check(hipStreamSynchronize(copy_stream), "download PMT hits");
+        }
+        if (!hits && !r.handle) r.handle.reset(new clsimhip_photon());
     }
     std::unique_ptr<std::vector<float>> histories;
     if (hits && history_entries_) {
@@ -871,6 +936,20 @@ void Converter::result_mcpes(const clsimhip_photon *photons, const clsimhip_mcpe
     if (it == handed_out_.end()) throw Error(CLSIMHIP_ERR_ARGUMENT, "not a result handed out by GetConversionResult (or already released)");
     *n = it->second.mcpe_count;
     if (it->second.mcpe_count) *mcpes = it->second.mcpe_data();
+}
+
+void Converter::result_pmt_hits(const clsimhip_photon *photons, const clsimhip_pmt_hit **hits, size_t *n)
+{
+    need_init();
+    if (!hits || !n) throw Error(CLSIMHIP_ERR_ARGUMENT, "output pointers are (null)");
+    *hits = nullptr;
+    *n = 0;
+    if (!pmt_) return;
+    std::lock_guard<std::mutex> lk(results_mutex_);
+    auto it = handed_out_.find(photons);
+    if (it == handed_out_.end()) throw Error(CLSIMHIP_ERR_ARGUMENT, "not a result handed out by GetConversionResult (or already released)");
+    *n = it->second.pmt_count;
+    if (it->second.pmt_count) *hits = it->second.pmt_data();
 }
 
 void Converter::result_mcpe_series(const clsimhip_photon *photons, const clsimhip_mcpe **mcpes, size_t *n, const clsimhip_mcpe_series **series, size_t *n_series,

@@ -22,6 +22,7 @@
 namespace clsimhip {
 
 class McpeGenerator;            // mcpe.h
+class PmtHitGenerator;          // pmt_hits.h
 struct alignas(16) SeriesParticle16 { uint8_t bytes[16]; };     // 16-byte aligned storage for a bunch's table and mask (mcpe_series.h)
 
 // RCCL gather of detected photons (comm.cpp)
@@ -280,6 +281,8 @@ public:
     void set_mcpe_generator(std::shared_ptr<McpeGenerator> g, bool keep_photons);
     // clsimhip_set_mcpe_series: the sorting stage behind the hit maker (mcpe_series.h); needs a generator (Compile() checks)
     void set_mcpe_series(bool on) { guard(); compiled_ = false; series_ = on; }
+    // clsimhip_set_pmt_generator: the multi-PMT hit maker runs behind every bunch's propagation (null: off)
+    void set_pmt_generator(std::shared_ptr<PmtHitGenerator> g, bool keep_photons);
 
     void compile();
     void initialize(uint64_t seed);
@@ -298,6 +301,7 @@ public:
     void result_mcpes(const clsimhip_photon *photons, const clsimhip_mcpe **mcpes, size_t *n);
     void result_mcpe_series(const clsimhip_photon *photons, const clsimhip_mcpe **mcpes, size_t *n, const clsimhip_mcpe_series **series, size_t *n_series,
                             uint64_t *n_masked);
+    void result_pmt_hits(const clsimhip_photon *photons, const clsimhip_pmt_hit **hits, size_t *n);
     void release_result(const clsimhip_photon *photons);
     size_t queue_size() const;
     bool more_photons_available() const;
@@ -333,6 +337,7 @@ private:
     using PhotonPool = PinnedPool<clsimhip_photon>;
     using McpePool = PinnedPool<clsimhip_mcpe>;
     using SeriesPool = PinnedPool<clsimhip_mcpe_series>;
+    using PmtHitPool = PinnedPool<clsimhip_pmt_hit>;
     using BlobPool = PinnedPool<uint8_t>;
     // A bunch on its way to the worker: the caller's steps are copied ONCE, in the caller's thread, into a page-locked buffer of the
     // step pool, which the worker uploads from (round 5; before, a vector here and a second copy into the slot's staging buffer on
@@ -366,6 +371,11 @@ private:
         uint64_t masked = 0;
         std::unique_ptr<std::vector<clsimhip_mcpe_series>> series;
         const clsimhip_mcpe_series *series_data() const { return series_pinned ? series_pinned.get() : (series ? series->data() : nullptr); }
+        // with a PMT hit generator: the bunch's hits, kept as the MCPEs are (and `handle` for a result without photon records)
+        PmtHitPool::Lease pmt_pinned;
+        size_t pmt_count = 0;
+        std::unique_ptr<std::vector<clsimhip_pmt_hit>> pmt_hits;
+        const clsimhip_pmt_hit *pmt_data() const { return pmt_pinned ? pmt_pinned.get() : (pmt_hits ? pmt_hits->data() : nullptr); }
     };
 
     void guard() const { if (initialized_) throw Error(CLSIMHIP_ERR_STATE, "I3CLSimStepToPhotonConverterHIP already initialized!"); }
@@ -394,6 +404,9 @@ private:
     std::shared_ptr<McpeGenerator> mcpe_;       // null: no MCPEs are made (the default)
     bool keep_photons_ = true;
     bool series_ = false;                       // the MCPE series stage runs behind the hit maker
+    std::shared_ptr<PmtHitGenerator> pmt_;      // null: no PMT hits are made (the default)
+    bool pmt_keep_photons_ = true;
+    bool carries_photons() const { return !(mcpe_ && !keep_photons_) && !(pmt_ && !pmt_keep_photons_); }
 
     std::atomic<bool> compiled_{false}, initialized_{false};    // (atomic: set_tuning() reads them from any thread)
     CompiledTables tables_;
@@ -407,6 +420,7 @@ private:
     PhotonPool result_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
     McpePool mcpe_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
     SeriesPool series_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
+    PmtHitPool pmt_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
     // particle tables and masks of the bunches on their way (input queue depth + one per slot + the one being filled)
     BlobPool bunch_pool_{PinnedPoolPolicy{8, size_t{1} << 28, nullptr}};
     size_t result_capacity(size_t records, size_t min_records) const;
@@ -431,6 +445,9 @@ private:
         DeviceBuffer<clsimhip_mcpe> d_mcpes;    // with an MCPE generator: max_output_photons_ records, five counters (mcpe.h)
         DeviceBuffer<uint32_t> d_mcpe_counters;
         PinnedBuffer<uint32_t> h_mcpe_counters;
+        DeviceBuffer<clsimhip_pmt_hit> d_pmt_hits;  // with a PMT hit generator: max_output_photons_ records, four counters (pmt_hits.h)
+        DeviceBuffer<uint32_t> d_pmt_counters;
+        PinnedBuffer<uint32_t> h_pmt_counters;
         // with the MCPE series stage: its workspace (grown when a bunch's table needs it), sorted records, series table, five counts
         DeviceBuffer<uint8_t> d_series_workspace;
         size_t series_workspace_bytes = 0;

@@ -227,6 +227,14 @@ public:
             lastMCPEs_.assign(m, m + nm);
             if (!n) check(clsimhip_release_result(handle_, p));     // the handle of a result without photon records
         }
+        lastPMTHits_.clear();
+        if (pmtHitGenerator_) {     // (likewise: GetLastPMTHits())
+            const clsimhip_pmt_hit *h = nullptr;
+            size_t nh = 0;
+            check(clsimhip_get_result_pmt_hits(handle_, p, &h, &nh));
+            lastPMTHits_.assign(h, h + nh);
+            if (!n) check(clsimhip_release_result(handle_, p));
+        }
         if (n) {
             std::memcpy(static_cast<void *>(r.photons->data()), p, n * sizeof(clsimhip_photon));
             // I3CLSimPhotonHistory (public/clsim/I3CLSimPhotonHistory.h): per photon the recorded scatter points
@@ -261,6 +269,8 @@ public:
         std::shared_ptr<const void> hold;
         const clsimhip_mcpe *mcpes = nullptr;       // with an MCPE generator: the bunch's MCPEs, valid as long as `photons`
         std::size_t numMCPEs = 0;
+        const clsimhip_pmt_hit *pmtHits = nullptr;  // with a PMT hit generator: the bunch's hits, valid as long as `photons`
+        std::size_t numPMTHits = 0;
         const I3CLSimPhoton *begin() const { return photons; }
         const I3CLSimPhoton *end() const { return photons + size; }
     };
@@ -271,6 +281,7 @@ public:
         check(clsimhip_get_conversion_result(handle_, &v.identifier, &p, &v.size));
         v.photons = reinterpret_cast<const I3CLSimPhoton *>(p);
         if (mcpeGenerator_) check(clsimhip_get_result_mcpes(handle_, p, &v.mcpes, &v.numMCPEs));
+        if (pmtHitGenerator_) check(clsimhip_get_result_pmt_hits(handle_, p, &v.pmtHits, &v.numPMTHits));
         if (p) {
             std::shared_ptr<clsimhip_converter> keep = owner_;
             v.hold = std::shared_ptr<const void>(static_cast<const void *>(p), [keep](const void *q) { (void)clsimhip_release_result(keep.get(), static_cast<const clsimhip_photon *>(q)); });
@@ -342,6 +353,17 @@ public:
     // with SetMCPESeries(true) in the order of the series
     const std::vector<clsimhip_mcpe> &GetLastMCPEs() const { return lastMCPEs_; }
 
+    // ---- Multi-PMT hit generator (include/clsimhip.h, "Multi-PMT hit generator": what I3PhotonToMCHitConverterForMultiPMT does with the
+    // photons of a frame, on the GPU behind the propagator).  Before Initialize(); nullptr switches it off; not beside an MCPE
+    // generator (Compile() refuses).  The generator object stays the caller's (the converter shares it). ----
+    void SetPMTHitGenerator(clsimhip_pmt_generator *generator, bool keepPhotons = true)
+    {
+        check(clsimhip_set_pmt_generator(handle_, generator, keepPhotons ? 1 : 0));
+        pmtHitGenerator_ = generator != nullptr;
+    }
+    // the hits of the bunch the last GetConversionResult() returned, in no particular order
+    const std::vector<clsimhip_pmt_hit> &GetLastPMTHits() const { return lastPMTHits_; }
+
     // ---- MCPE series (include/clsimhip.h, "MCPE series"): what replaces the client module's AddPhotonsToFrames loop and the per-DOM
     // time sort.  Before Initialize(); needs a generator.  A bunch is enqueued with its particle table (strictly increasing in
     // identifier) and its frames' ignored modules; its result's MCPEs come back per frame, per DOM in OMKey order, in time order. ----
@@ -393,6 +415,8 @@ private:
     bool mcpeSeries_ = false;
     std::vector<clsimhip_mcpe_series> lastSeries_;
     uint64_t lastMasked_ = 0;
+    bool pmtHitGenerator_ = false;
+    std::vector<clsimhip_pmt_hit> lastPMTHits_;
 #ifdef CLSIMHIP_WITH_ICETRAY
     I3RandomServicePtr randomService_;
 #endif

@@ -859,6 +859,96 @@ int clsimhip_enqueue_steps_with_particles(clsimhip_converter *c, const clsimhip_
 int clsimhip_get_result_mcpe_series(clsimhip_converter *c, const clsimhip_photon *photons, const clsimhip_mcpe **mcpes, size_t *n,
                                     const clsimhip_mcpe_series **series, size_t *n_series, uint64_t *n_masked);
 
+/* ---- Multi-PMT hit generator: detected photons -> hits on the PMTs of segmented modules ---------------------------------
+ * The hit maker for modules that carry several PMTs (KM3NeT-style spheres): FindHitPMT and the per-photon body of
+ * I3PhotonToMCHitConverterForMultiPMT::DAQ (private/clsim/dom/I3PhotonToMCHitConverterForMultiPMT.cxx:111-227, 297-382).  A pure
+ * function of one delivered photon record (position relative to the module centre, string and OM IDs), a fixed configuration and
+ * a 64-bit seed.  Per record, in this order:
+ *     no module for the record's (string ID, OM ID) -> UNKNOWN_MODULE, no hit;
+ *     direction d from the record's angles as the MCPE generator makes it; position . d > 0 (the photon is leaving) -> no hit;
+ *     |position| not within 3 cm of the sphere radius of the module's type -> counted as OFF_SURFACE, and the record GOES ON (the
+ *     reference only warns);
+ *     every PMT of the type in index order, axis n and centre a rotated into the module's orientation: skipped when d . n >= 1e-8,
+ *     when mu = ((a - position) . n) / (d . n) < 0, or when position + mu d is further from a than the PMT's radius; of several
+ *     intersections the one with the smallest mu (a later one replaces an earlier one only if its mu is smaller); none -> no hit;
+ *     c = -(n . d) <= 0 -> no hit (the reference's hit_angle >= 90 degrees, stated on the cosine);
+ *     P = weight; P *= G_type(wavelength); P *= Q_pmt(wavelength) x collection efficiency; P *= A_pmt(c) / c;
+ *     P > 1 -> PROBABILITY_ABOVE_ONE, no hit; a hit when P > u, u as for the MCPE generator (the record's hash and the seed);
+ *     hit = {identifier, string ID, OM ID, PMT index within its type, time = the photon's time} (the reference computes a travel
+ *     time inside the module and then stores the photon's own).
+ * G (glass / gel survival), Q (quantum efficiency) and A (angular acceptance factor, tabulated over c = cos of the hit angle) are
+ * clsimhip_functions of kinds TABLE and CONSTANT.  The path length the reference hands to the glass / gel survival is NOT modelled
+ * (it needs an exponential the reference does not define).  Binary64 + - x / in one fixed order, as for the MCPE generator: the HIP
+ * kernel and the host twin give the same bits. */
+typedef struct {
+    double sphere_radius;               /* of the module's sphere [m]: the radius photons are recorded at */
+    int32_t first_pmt, n_pmts;          /* its PMTs in the `pmts` array (1 ... 64); a hit's `pmt` counts from first_pmt */
+    int32_t glass_gel_survival;         /* G: index into `functions`, over the wavelength */
+    int32_t reserved;
+} clsimhip_pmt_type;                    /* 24 bytes */
+typedef struct {
+    double axis[3];                     /* unit to 1e-6, module frame: the direction the PMT looks in */
+    double position[3];                 /* centre of its disc [m], module frame; inside the sphere */
+    double radius;                      /* of the disc [m] */
+    double collection_efficiency;
+    int32_t quantum_efficiency;         /* Q: index into `functions`, over the wavelength */
+    int32_t angular_acceptance;         /* A: index into `functions`, over c */
+} clsimhip_pmt;                         /* 72 bytes */
+typedef struct {
+    int32_t string_id;
+    uint32_t om_id;
+    int32_t type;                       /* index into `types` */
+    int32_t reserved;
+    double rotation[9];                 /* row-major, module frame -> detector frame (I3Orientation is outside the reference) */
+} clsimhip_pmt_module;                  /* 88 bytes */
+typedef struct {
+    uint32_t identifier;                /* the photon's (I3MCHit::SetParticleID is the caller's, keyed by it) */
+    int16_t string_id;
+    uint16_t om_id;
+    uint32_t pmt;                       /* PMT number within the module's type (the key of I3MCHitSeriesMultiOM) */
+    uint32_t reserved;                  /* 0 */
+    double time;
+} clsimhip_pmt_hit;                     /* 24 bytes */
+typedef char clsimhip_pmt_hit_is_24_bytes[sizeof(clsimhip_pmt_hit) == 24 ? 1 : -1];
+typedef char clsimhip_pmt_is_72_bytes[sizeof(clsimhip_pmt) == 72 ? 1 : -1];
+typedef char clsimhip_pmt_module_is_88_bytes[sizeof(clsimhip_pmt_module) == 88 ? 1 : -1];
+#define CLSIMHIP_PMT_UNKNOWN_MODULE 0           /* index into the condition counters */
+#define CLSIMHIP_PMT_PROBABILITY_ABOVE_ONE 1
+#define CLSIMHIP_PMT_OFF_SURFACE 2
+typedef struct clsimhip_pmt_generator clsimhip_pmt_generator;
+/* At most 64 functions (3072 table values together), 8 types, 64 PMTs per type, 2^24 modules.  CLSIMHIP_ERR_CONFIG for: a limit
+ * exceeded; a function of another kind than TABLE / CONSTANT; a rotation that changes the squared length of a unit vector (its
+ * three columns, and every PMT axis and position of the module's type) by more than 1e-6; a PMT axis that is not unit to 1e-6; a
+ * PMT whose position lies outside its type's sphere; a module whose type index names no type; a (string ID, OM ID) pair given
+ * twice; IDs that do not fit the photon record.  Host only: no GPU is touched. */
+int clsimhip_pmt_generator_create(const clsimhip_function *functions, size_t n_functions, const clsimhip_pmt_type *types, size_t n_types,
+                                  const clsimhip_pmt *pmts, size_t n_pmts, const clsimhip_pmt_module *modules, size_t n_modules,
+                                  uint64_t seed, clsimhip_pmt_generator **out);
+/* a converter the generator was given to keeps it alive until the converter is destroyed */
+void clsimhip_pmt_generator_destroy(clsimhip_pmt_generator *g);
+const char *clsimhip_pmt_generator_last_error(const clsimhip_pmt_generator *g);
+/* The host twin: the definition, for callers without a GPU and for the tests.  Keeps the input order.  *n_out = hits made (may
+ * exceed `capacity`: only the first `capacity` are stored); counters[3] (may be NULL) receives the three condition counts. */
+int clsimhip_pmt_convert_host(const clsimhip_pmt_generator *g, const clsimhip_photon *photons, size_t n, clsimhip_pmt_hit *out,
+                              size_t capacity, size_t *n_out, uint64_t counters[3]);
+/* The kernel, on records that live in HBM: min(*d_hit_count, capacity) records of d_photons (16-byte aligned).  d_hits: 8-byte
+ * aligned.  d_counters: four uint32, zeroed by this call; [0] counts the hits and keeps counting past hit_capacity (only the first
+ * hit_capacity are stored), [1] UNKNOWN_MODULE, [2] PROBABILITY_ABOVE_ONE, [3] OFF_SURFACE.  Output order is unspecified.
+ * Asynchronous on hip_stream (NULL = default stream). */
+int clsimhip_pmt_convert_device(clsimhip_pmt_generator *g, int device, const void *d_photons, const void *d_hit_count, size_t capacity,
+                                void *d_hits, size_t hit_capacity, void *d_counters, void *hip_stream);
+/* Attach the generator to a converter: the kernel then runs on every bunch's stream behind the propagation kernels, over the
+ * records the bunch stored.  Before Initialize() only (CLSIMHIP_ERR_STATE after); g = NULL switches it off (the default: no launch
+ * and no byte changes anywhere).  keep_photons as for clsimhip_set_mcpe_generator.  Compile() then refuses (CLSIMHIP_ERR_CONFIG):
+ * an MCPE generator beside it; clsimhip_set_mcpe_series (series per PMT are not made); a geometry DOM without a module or whose
+ * IDs do not fit the record; a type in use whose sphere radius differs by more than 3 cm from the radius the converter records
+ * photons at (the geometry's OM radius / the pancake factor); photon histories together with keep_photons = 0.
+ * A bunch with UNKNOWN_MODULE or PROBABILITY_ABOVE_ONE > 0 fails as a bunch with one of the MCPE generator's conditions does, with
+ * the counts in the text; OFF_SURFACE is reported on stderr and is not fatal. */
+int clsimhip_set_pmt_generator(clsimhip_converter *c, clsimhip_pmt_generator *g, int keep_photons);
+/* Hits of the result `photons` belongs to; valid until clsimhip_release_result(c, photons).  *hits is NULL when there are none. */
+int clsimhip_get_result_pmt_hits(clsimhip_converter *c, const clsimhip_photon *photons, const clsimhip_pmt_hit **hits, size_t *n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,9 @@ No GPU: the committed photon records of tests/golden/verbatim_cl_*.npz, repeated
 --series N: the MCPE series' host twin instead (clsimhip_mcpe_series_host: lookup, mask, shift, sort, series table), in MCPEs per
 second, on N synthetic MCPEs at IceCube's 5160 DOMs dealt to 1000 particles in 10 frames; --device adds the device stage's time
 for the same input (HIP events around clsimhip_mcpe_series_device, best of --repeats; needs a GPU).
+
+--pmt: the multi-PMT hit generator's host twin instead (clsimhip_pmt_convert_host) on the same records, against the 31-PMT layout
+of tests/pmt_common.py, in photon records per second.
 """
 import argparse
 import ctypes as C
@@ -73,11 +76,23 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--series", type=int, default=0, metavar="N")
     ap.add_argument("--device", action="store_true")
+    ap.add_argument("--pmt", action="store_true")
     args = ap.parse_args()
     if args.series:
         return series_rate(args)
     base = np.concatenate([M.fixture_photons(name) for name in M.FIXTURES if name != "lea_no_pancake"])     # recorded with pancake 5
     ph = np.ascontiguousarray(np.tile(base, -(-args.records // len(base)))[:args.records])
+    if args.pmt:
+        from tests import pmt_common as PC
+        gen = PC.make_generator(*PC.configuration("identity", PC.sphere_radius_of("mie")))
+        best = float("inf")
+        for _ in range(args.repeats):
+            t0 = time.perf_counter()
+            hits, counters = gen.ConvertHost(ph)
+            best = min(best, time.perf_counter() - t0)
+            assert not any(counters.values())
+        print(json.dumps({"records": len(ph), "pmt_hits": len(hits), "pmts_per_module": 31, "seconds": best, "records_per_s": len(ph) / best, "threads": 1}))
+        return
     gen = M.standard_generator()
     out = np.zeros(len(ph), dtype=CV.MCPE_DTYPE)
     n, counters = C.c_size_t(), np.zeros(4, dtype=np.uint64)
