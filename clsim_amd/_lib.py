@@ -128,6 +128,8 @@ SYMBOLS = [
     "clsimhip_mcpe_convert_host", "clsimhip_mcpe_convert_device", "clsimhip_set_mcpe_generator", "clsimhip_get_result_mcpes",
     "clsimhip_mcpe_series_host", "clsimhip_mcpe_series_workspace_bytes", "clsimhip_mcpe_series_device", "clsimhip_set_mcpe_series",
     "clsimhip_enqueue_steps_with_particles", "clsimhip_get_result_mcpe_series",
+    "clsimhip_mcpe_merge_host", "clsimhip_mcpe_merge_workspace_bytes", "clsimhip_mcpe_merge_device", "clsimhip_set_mcpe_merging",
+    "clsimhip_get_result_mcpe_merged",
     "clsimhip_pmt_generator_create", "clsimhip_pmt_generator_destroy", "clsimhip_pmt_generator_last_error",
     "clsimhip_pmt_convert_host", "clsimhip_pmt_convert_device", "clsimhip_set_pmt_generator", "clsimhip_get_result_pmt_hits",
 ]
@@ -300,6 +302,11 @@ def load():
         "clsimhip_set_mcpe_series": (i32, [vp, i32]),
         "clsimhip_enqueue_steps_with_particles": (i32, [vp, vp, sz, u32, vp, sz, vp, sz]),
         "clsimhip_get_result_mcpe_series": (i32, [vp, vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(u64)]),
+        "clsimhip_mcpe_merge_host": (i32, [vp, sz, vp, sz, C.c_double, vp, vp, vp, vp, C.POINTER(sz), C.POINTER(sz)]),
+        "clsimhip_mcpe_merge_workspace_bytes": (sz, [sz]),
+        "clsimhip_mcpe_merge_device": (i32, [vp, i32, vp, vp, vp, sz, C.c_double, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "clsimhip_set_mcpe_merging": (i32, [vp, i32, C.c_double]),
+        "clsimhip_get_result_mcpe_merged": (i32, [vp, vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(vp)]),
         "clsimhip_pmt_generator_create": (i32, [C.POINTER(Function), sz, vp, sz, vp, sz, vp, sz, u64, C.POINTER(vp)]),
         "clsimhip_pmt_generator_destroy": (None, [vp]),
         "clsimhip_pmt_generator_last_error": (C.c_char_p, [vp]),

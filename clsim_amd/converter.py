@@ -331,6 +331,10 @@ MCPE_PARTICLE_DTYPE = np.dtype([("id", "<u4"), ("frame", "<u4"), ("timeShift", "
 MCPE_MASK_DTYPE = np.dtype([("frame", "<u4"), ("stringID", "<i2"), ("omID", "<u2")])
 MCPE_SERIES_DTYPE = np.dtype([("frame", "<u4"), ("stringID", "<i2"), ("omID", "<u2"), ("first", "<u4"), ("count", "<u4")])
 MCPE_SERIES_COUNTERS = ("unknown_particle", "masked", "unknown_dom")
+# MCPE merging (include/clsimhip.h): one merged record, one entry of the flattened particle-ID map, one series' entries of it
+MCPE_MERGED_DTYPE = np.dtype([("npe", "<u4"), ("stringID", "<i2"), ("omID", "<u2"), ("time", "<f8")])
+MCPE_PARENT_DTYPE = np.dtype([("id", "<u4"), ("index", "<u4")])
+MCPE_PARENT_RANGE_DTYPE = np.dtype([("first", "<u4"), ("count", "<u4")])
 
 
 def _series_inputs(particles, masked):
@@ -425,6 +429,38 @@ class MCPEGenerator:
                                                      C.c_void_p(d_out), C.c_void_p(d_series), C.c_void_p(d_counts), C.c_void_p(d_workspace),
                                                      int(workspace_bytes), C.c_void_p(stream)))
 
+    @staticmethod
+    def MergeHost(records, series, window):
+        """(merged, merged_series, parents, parent_ranges): the host twin of the MCPE merging stage on the output of the series stage.
+        records: MCPE_DTYPE, series: MCPE_SERIES_DTYPE (they partition the records), window: 0 <= window < inf.  merged:
+        MCPE_MERGED_DTYPE, one per group; merged_series: the series table over the merged records; parents: MCPE_PARENT_DTYPE, the
+        distinct (id, group within the series) pairs ascending in (series, id, index); parent_ranges: MCPE_PARENT_RANGE_DTYPE, one
+        per series."""
+        records = np.ascontiguousarray(records, dtype=MCPE_DTYPE)
+        series = np.ascontiguousarray(series, dtype=MCPE_SERIES_DTYPE)
+        merged, parents = np.zeros(len(records), dtype=MCPE_MERGED_DTYPE), np.zeros(len(records), dtype=MCPE_PARENT_DTYPE)
+        out_series, ranges = np.zeros(len(series), dtype=MCPE_SERIES_DTYPE), np.zeros(len(series), dtype=MCPE_PARENT_RANGE_DTYPE)
+        n_merged, n_parents = C.c_size_t(), C.c_size_t()
+        _check(_lib.load().clsimhip_mcpe_merge_host(records.ctypes.data_as(C.c_void_p), len(records), series.ctypes.data_as(C.c_void_p), len(series),
+                                                    float(window), merged.ctypes.data_as(C.c_void_p), out_series.ctypes.data_as(C.c_void_p),
+                                                    parents.ctypes.data_as(C.c_void_p), ranges.ctypes.data_as(C.c_void_p), C.byref(n_merged),
+                                                    C.byref(n_parents)))
+        return merged[:n_merged.value], out_series, parents[:n_parents.value], ranges
+
+    @staticmethod
+    def MergeWorkspaceBytes(capacity):
+        return int(_lib.load().clsimhip_mcpe_merge_workspace_bytes(int(capacity)))
+
+    def MergeDevice(self, d_records, d_series, d_series_counts, capacity, window, d_merged, d_merged_series, d_parents, d_ranges, d_counts,
+                    d_workspace, workspace_bytes, device=0, stream=0):
+        """the kernels on device-resident series (addresses; pairs with MakeSeriesDevice: its d_out, d_series and d_counts); the four
+        outputs hold `capacity` entries each, d_counts: two uint32 (merged records, parent entries), d_workspace:
+        MergeWorkspaceBytes(capacity) bytes"""
+        _check(self._lib.clsimhip_mcpe_merge_device(self._h, int(device), C.c_void_p(d_records), C.c_void_p(d_series), C.c_void_p(d_series_counts),
+                                                    int(capacity), float(window), C.c_void_p(d_merged), C.c_void_p(d_merged_series),
+                                                    C.c_void_p(d_parents), C.c_void_p(d_ranges), C.c_void_p(d_counts), C.c_void_p(d_workspace),
+                                                    int(workspace_bytes), C.c_void_p(stream)))
+
 
 # Multi-PMT hit generator (include/clsimhip.h): clsimhip_pmt_type, clsimhip_pmt, clsimhip_pmt_module and clsimhip_pmt_hit
 PMT_TYPE_DTYPE = np.dtype([("sphereRadius", "<f8"), ("firstPMT", "<i4"), ("numPMTs", "<i4"), ("glassGelSurvival", "<i4"), ("reserved", "<i4")])
@@ -485,10 +521,15 @@ class ConversionResult(tuple):
     """What GetConversionResult / GetConversionResultInPlace return: the tuple (identifier, photons[, histories]) / (identifier,
     photons, release), with the bunch's MCPEs (MCPE_DTYPE) as attribute `mcpes` when the converter has an MCPE generator (None
     otherwise).  With the MCPE series stage `mcpes` are the sorted records, `series` their series table (MCPE_SERIES_DTYPE) and
-    `masked` the bunch's MASKED count.  With a PMT hit generator `pmt_hits` holds the bunch's hits (PMT_HIT_DTYPE)."""
+    `masked` the bunch's MASKED count; with the MCPE merging stage `merged` (MCPE_MERGED_DTYPE), `merged_series`, `parents`
+    (MCPE_PARENT_DTYPE) and `parent_ranges` (MCPE_PARENT_RANGE_DTYPE) beside them.  With a PMT hit generator `pmt_hits` holds the bunch's hits (PMT_HIT_DTYPE)."""
     mcpes = None
     series = None
     masked = None
+    merged = None
+    merged_series = None
+    parents = None
+    parent_ranges = None
     pmt_hits = None
 
 
@@ -502,6 +543,7 @@ class I3CLSimStepToPhotonConverterHIP:
         self._history_entries = 0
         self._mcpe = None
         self._series = False
+        self._merging = False
         self._pmt = None
 
     def __del__(self):
@@ -563,6 +605,12 @@ class I3CLSimStepToPhotonConverterHIP:
         (result attributes `mcpes`, `series`, `masked`).  Before Initialize() only; Compile() refuses it without a generator."""
         self._call("clsimhip_set_mcpe_series", int(bool(on)))
         self._series = bool(on)
+    def SetMCPEMerging(self, window, on=True):
+        """the merging stage behind the series stage: records of a series within `window` of their group's opener become one merged
+        record (result attributes `merged`, `merged_series`, `parents`, `parent_ranges`; `mcpes` and `series` stay the unmerged
+        ones).  Before Initialize() only; Compile() refuses it without SetMCPESeries."""
+        self._call("clsimhip_set_mcpe_merging", int(bool(on)), float(window))
+        self._merging = bool(on)
     def SetWorkgroupSize(self, v): self._call("clsimhip_set_workgroup_size", int(v))
     def SetMaxNumWorkitems(self, v): self._call("clsimhip_set_max_num_workitems", int(v))
 
@@ -609,6 +657,8 @@ class I3CLSimStepToPhotonConverterHIP:
                 C.memmove(mcpes.ctypes.data, mp.value, mn.value * 16)
             if sn.value:
                 C.memmove(series.ctypes.data, sp.value, sn.value * 16)
+            if self._merging:
+                return mcpes, series, int(masked.value), self._result_merged(ptr)
             return mcpes, series, int(masked.value)
         mp, mn = C.c_void_p(), C.c_size_t()
         self._call("clsimhip_get_result_mcpes", ptr, C.byref(mp), C.byref(mn))
@@ -616,6 +666,19 @@ class I3CLSimStepToPhotonConverterHIP:
         if mn.value:
             C.memmove(mcpes.ctypes.data, mp.value, mn.value * 16)
         return mcpes
+
+    def _result_merged(self, ptr):
+        """copies of (merged records, merged series table, parents, parent ranges) of the result `ptr` belongs to"""
+        gp, gn, sp, sn, pp, pn, rp = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_size_t(), C.c_void_p()
+        self._call("clsimhip_get_result_mcpe_merged", ptr, C.byref(gp), C.byref(gn), C.byref(sp), C.byref(sn), C.byref(pp), C.byref(pn), C.byref(rp))
+        out = []
+        for address, count, dtype in ((gp, gn.value, MCPE_MERGED_DTYPE), (sp, sn.value, MCPE_SERIES_DTYPE), (pp, pn.value, MCPE_PARENT_DTYPE),
+                                      (rp, sn.value, MCPE_PARENT_RANGE_DTYPE)):
+            array = np.zeros(count, dtype=dtype)
+            if count:
+                C.memmove(array.ctypes.data, address.value, count * dtype.itemsize)
+            out.append(array)
+        return tuple(out)
 
     def _result_pmt_hits(self, ptr):
         """copy of the PMT hits of the result `ptr` belongs to (None without a PMT hit generator)"""
@@ -704,7 +767,9 @@ class I3CLSimStepToPhotonConverterHIP:
 
     def _attach_mcpes(self, result, mcpes):
         if self._series and mcpes is not None:
-            result.mcpes, result.series, result.masked = mcpes
+            result.mcpes, result.series, result.masked = mcpes[:3]
+            if self._merging:
+                result.merged, result.merged_series, result.parents, result.parent_ranges = mcpes[3]
         else:
             result.mcpes = mcpes
 
@@ -850,11 +915,12 @@ def initializeHIP(device, geometry, medium, wavelengthGenerationBias, wavelength
                   enableDoubleBuffering=False, doublePrecision=False, stopDetectedPhotons=True, saveAllPhotons=False,
                   saveAllPhotonsPrescale=0.01, fixedNumberOfAbsorptionLengths=float("nan"), pancakeFactor=1.0,
                   photonHistoryEntries=0, limitWorkgroupSize=0, approximateNumberOfWorkItems=262144,
-                  seed=12345, streams=None, tuning=None, mcpeGenerator=None, keepPhotons=True, mcpeSeries=False, pmtHitGenerator=None):
+                  seed=12345, streams=None, tuning=None, mcpeGenerator=None, keepPhotons=True, mcpeSeries=False, pmtHitGenerator=None, mcpeMergeWindow=None):
     """Canonical configuration sequence, I3CLSimModuleHelper::initializeOpenCL
     (ModuleHelper.cxx:303-372).  tuning: {key: value} for clsimhip_set_tuning, applied before Compile().
     mcpeGenerator: an MCPEGenerator that turns every bunch's photons into MCPEs on the GPU (result attribute `mcpes`);
-    keepPhotons=False then leaves the photon records on the device; mcpeSeries=True sorts them into per-frame, per-DOM series.
+    keepPhotons=False then leaves the photon records on the device; mcpeSeries=True sorts them into per-frame, per-DOM series;
+    mcpeMergeWindow=w then merges the records of a series within w of their group's opener (SetMCPEMerging).
     pmtHitGenerator: a PMTHitGenerator instead, for modules with several PMTs (result attribute `pmt_hits`; keepPhotons as above)."""
     conv = I3CLSimStepToPhotonConverterHIP(device)
     for key, value in (tuning or {}).items():
@@ -875,6 +941,8 @@ def initializeHIP(device, geometry, medium, wavelengthGenerationBias, wavelength
         conv.SetMCPEGenerator(mcpeGenerator, keepPhotons)
     if mcpeSeries:
         conv.SetMCPESeries(True)
+    if mcpeMergeWindow is not None:
+        conv.SetMCPEMerging(mcpeMergeWindow)
     if pmtHitGenerator is not None:
         conv.SetPMTHitGenerator(pmtHitGenerator, keepPhotons)
     conv.Compile()

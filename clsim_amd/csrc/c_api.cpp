@@ -13,6 +13,7 @@
 #include "step_store.h"
 #include "flasher.h"
 #include "mcpe.h"
+#include "mcpe_merge.h"
 #include "pmt_hits.h"
 
 using namespace clsimhip;
@@ -1019,6 +1020,38 @@ int clsimhip_get_result_mcpe_series(clsimhip_converter *c, const clsimhip_photon
                                     const clsimhip_mcpe_series **series, size_t *n_series, uint64_t *n_masked)
 {
     return guarded(c, [&] { need(c, "converter"); c->impl.result_mcpe_series(photons, mcpes, n, series, n_series, n_masked); });
+}
+
+// ---- MCPE merging (mcpe_merge.h) ----
+int clsimhip_mcpe_merge_host(const clsimhip_mcpe *records, size_t n, const clsimhip_mcpe_series *series, size_t n_series, double window,
+                             clsimhip_mcpe_merged *out_merged, clsimhip_mcpe_series *out_series, clsimhip_mcpe_parent *out_parents,
+                             clsimhip_mcpe_parent_range *out_ranges, size_t *n_merged, size_t *n_parents)
+{
+    return guarded(nullptr, [&] { mcpe_merge_host(records, n, series, n_series, window, out_merged, out_series, out_parents, out_ranges, n_merged, n_parents); });
+}
+size_t clsimhip_mcpe_merge_workspace_bytes(size_t capacity)
+{
+    return mcpe_merge_workspace_bytes(capacity);
+}
+int clsimhip_mcpe_merge_device(clsimhip_mcpe_generator *g, int device, const void *d_records, const void *d_series,
+                               const void *d_series_counts, size_t capacity, double window, void *d_merged, void *d_merged_series,
+                               void *d_parents, void *d_ranges, void *d_counts, void *d_workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return guarded(nullptr, [&] {
+        need(g, "generator");
+        mcpe_merge_device(device, d_records, d_series, d_series_counts, capacity, window, d_merged, d_merged_series, d_parents, d_ranges, d_counts,
+                          d_workspace, workspace_bytes, static_cast<hipStream_t>(hip_stream));
+    });
+}
+int clsimhip_set_mcpe_merging(clsimhip_converter *c, int on, double window)
+{
+    return guarded(c, [&] { need(c, "converter"); c->impl.set_mcpe_merging(on != 0, window); });
+}
+int clsimhip_get_result_mcpe_merged(clsimhip_converter *c, const clsimhip_photon *photons, const clsimhip_mcpe_merged **merged,
+                                    size_t *n_merged, const clsimhip_mcpe_series **series, size_t *n_series,
+                                    const clsimhip_mcpe_parent **parents, size_t *n_parents, const clsimhip_mcpe_parent_range **ranges)
+{
+    return guarded(c, [&] { need(c, "converter"); c->impl.result_mcpe_merged(photons, merged, n_merged, series, n_series, parents, n_parents, ranges); });
 }
 
 // ---- Multi-PMT hit generator (pmt_hits.h) ----

@@ -5,6 +5,7 @@
 // is on the GPU while the previous one is downloaded and converted.
 #include "converter.h"
 #include "mcpe.h"
+#include "mcpe_merge.h"
 #include "pmt_hits.h"
 
 #include <chrono>
@@ -157,6 +158,7 @@ void Converter::release_device()
     result_pool_.reset();
     mcpe_pool_.reset();
     series_pool_.reset();
+    merge_pool_.reset();
     pmt_pool_.reset();
     bunch_pool_.reset();
 }
@@ -276,6 +278,7 @@ void Converter::compile()
     }
 #endif
     if (series_ && !mcpe_) throw Error(CLSIMHIP_ERR_CONFIG, "MCPE series need an MCPE generator (clsimhip_set_mcpe_generator)");
+    if (merging_ && !series_) throw Error(CLSIMHIP_ERR_CONFIG, "MCPE merging needs the MCPE series stage (clsimhip_set_mcpe_series)");
     if (mcpe_) {
         // the generator reads IDs from the records: every DOM's pair must fit them (the host conversion reports such IDs only when a
         // photon carries them, OpenCL.cxx:1577-1586) and must have a class (log_fatal per photon in the reference, :628-630)
@@ -505,6 +508,16 @@ void Converter::setup_device_buffers(DeviceState &D)
             sl.d_series_counts.alloc(8, "MCPE series counts");
             sl.h_series_counts.alloc(8, "pinned MCPE series counts");
         }
+        if (merging_) {
+            sl.merge_workspace_bytes = mcpe_merge_workspace_bytes(max_output_photons_);
+            sl.d_merge_workspace.alloc(sl.merge_workspace_bytes, "MCPE merging workspace");
+            sl.d_merged.alloc(max_output_photons_, "merged MCPEs");
+            sl.d_merged_series.alloc(max_output_photons_, "merged MCPE series table");
+            sl.d_parents.alloc(max_output_photons_, "MCPE parents");
+            sl.d_ranges.alloc(max_output_photons_, "MCPE parent ranges");
+            sl.d_merge_counts.alloc(4, "MCPE merging counts");
+            sl.h_merge_counts.alloc(4, "pinned MCPE merging counts");
+        }
         sl.start.create("hipEventCreate");
         sl.stop.create("hipEventCreate");
         sl.counted.create_untimed("hipEventCreate");
@@ -678,6 +691,13 @@ void Converter::submit(Slot &s, Job &job)
                                       s.d_series.get(), s.d_series_counts.get(), s.d_series_workspace.get(), s.series_workspace_bytes, stream);
         hip_check(hipMemcpyAsync(s.h_series_counts.get(), s.d_series_counts.get(), 20, hipMemcpyDeviceToHost, stream), "download MCPE series counts");
     }
+    if (merging_) {
+        // behind the series stage on the same stream, over the records and the table it left; reads its sizes from the stage's counts
+        mcpe_merge_device(device_, s.d_sorted.get(), s.d_series.get(), s.d_series_counts.get(), max_output_photons_, merge_window_, s.d_merged.get(),
+                          s.d_merged_series.get(), s.d_parents.get(), s.d_ranges.get(), s.d_merge_counts.get(), s.d_merge_workspace.get(),
+                          s.merge_workspace_bytes, stream);
+        hip_check(hipMemcpyAsync(s.h_merge_counts.get(), s.d_merge_counts.get(), 8, hipMemcpyDeviceToHost, stream), "download MCPE merging counts");
+    }
     if (pmt_) {
         // where the MCPE stage would run: behind assemble_hits_kernel on the bunch's stream, outside the start / stop pair
         pmt_->convert_device(device_, s.d_photons.get(), s.d_hit_count.get(), max_output_photons_, s.d_pmt_hits.get(), max_output_photons_, s.d_pmt_counters.get(), stream);
@@ -777,6 +797,22 @@ void Converter::finish(Slot &s, std::chrono::steady_clock::time_point &last_done
                 if (!table) { r.series.reset(new std::vector<clsimhip_mcpe_series>(n_series)); table = r.series->data(); }
                 hip_check(hipMemcpyAsync(table, s.d_series.get(), static_cast<size_t>(n_series) * sizeof(clsimhip_mcpe_series), hipMemcpyDeviceToHost, copy_stream),
                           "download MCPE series table");
+            }
+            if (merging_ && n_series) {
+                const uint32_t n_merged = std::min(s.h_merge_counts.get()[0], n_mcpes), n_parents = std::min(s.h_merge_counts.get()[1], n_mcpes);
+                const size_t at_series = static_cast<size_t>(n_merged) * sizeof(clsimhip_mcpe_merged);
+                const size_t at_parents = at_series + static_cast<size_t>(n_series) * sizeof(clsimhip_mcpe_series);
+                const size_t at_ranges = at_parents + static_cast<size_t>(n_parents) * sizeof(clsimhip_mcpe_parent);
+                const size_t bytes = at_ranges + static_cast<size_t>(n_series) * sizeof(clsimhip_mcpe_parent_range);
+                r.merge_pinned = merge_pool_.take(bytes, (bytes + bytes / 4 + 4095) / 4096 * 4096, device_);
+                uint8_t *blob = r.merge_pinned.get();
+                if (!blob) { r.merge_blob.reset(new std::vector<uint64_t>(bytes / 8)); blob = reinterpret_cast<uint8_t *>(r.merge_blob->data()); }
+                hip_check(hipMemcpyAsync(blob, s.d_merged.get(), at_series, hipMemcpyDeviceToHost, copy_stream), "download merged MCPEs");
+                hip_check(hipMemcpyAsync(blob + at_series, s.d_merged_series.get(), at_parents - at_series, hipMemcpyDeviceToHost, copy_stream), "download merged MCPE series table");
+                hip_check(hipMemcpyAsync(blob + at_parents, s.d_parents.get(), at_ranges - at_parents, hipMemcpyDeviceToHost, copy_stream), "download MCPE parents");
+                hip_check(hipMemcpyAsync(blob + at_ranges, s.d_ranges.get(), bytes - at_ranges, hipMemcpyDeviceToHost, copy_stream), "download MCPE parent ranges");
+                r.merged_count = n_merged;
+                r.parent_count = n_parents;
             }
             hip_check(hipStreamSynchronize(copy_stream), "download MCPEs");
         }
@@ -968,6 +1004,39 @@ void Converter::result_mcpe_series(const clsimhip_photon *photons, const clsimhi
     if (it->second.mcpe_count) *mcpes = it->second.mcpe_data();
     if (it->second.series_count) *series = it->second.series_data();
     if (n_masked) *n_masked = it->second.masked;
+}
+
+void Converter::set_mcpe_merging(bool on, double window)
+{
+    guard();
+    if (on && !merge_window_ok(window)) throw Error(CLSIMHIP_ERR_ARGUMENT, "MCPE merging: the window must be a number with 0 <= window < +inf");
+    compiled_ = false;
+    merging_ = on;
+    merge_window_ = on ? window : 0.;
+}
+
+void Converter::result_mcpe_merged(const clsimhip_photon *photons, const clsimhip_mcpe_merged **merged, size_t *n_merged, const clsimhip_mcpe_series **series,
+                                   size_t *n_series, const clsimhip_mcpe_parent **parents, size_t *n_parents, const clsimhip_mcpe_parent_range **ranges)
+{
+    need_init();
+    if (!merged || !n_merged || !series || !n_series || !parents || !n_parents || !ranges) throw Error(CLSIMHIP_ERR_ARGUMENT, "output pointers are (null)");
+    if (!merging_) throw Error(CLSIMHIP_ERR_STATE, "the MCPE merging stage is off (clsimhip_set_mcpe_merging)");
+    *merged = nullptr; *series = nullptr; *parents = nullptr; *ranges = nullptr;
+    *n_merged = 0; *n_series = 0; *n_parents = 0;
+    std::lock_guard<std::mutex> lk(results_mutex_);
+    auto it = handed_out_.find(photons);
+    if (it == handed_out_.end()) throw Error(CLSIMHIP_ERR_ARGUMENT, "not a result handed out by GetConversionResult (or already released)");
+    const Result &r = it->second;
+    const uint8_t *blob = r.merge_data();
+    if (!blob) return;
+    const size_t at_series = r.merged_count * sizeof(clsimhip_mcpe_merged);
+    const size_t at_parents = at_series + r.series_count * sizeof(clsimhip_mcpe_series);
+    const size_t at_ranges = at_parents + r.parent_count * sizeof(clsimhip_mcpe_parent);
+    *n_merged = r.merged_count; *n_series = r.series_count; *n_parents = r.parent_count;
+    *merged = reinterpret_cast<const clsimhip_mcpe_merged *>(blob);
+    *series = reinterpret_cast<const clsimhip_mcpe_series *>(blob + at_series);
+    *parents = reinterpret_cast<const clsimhip_mcpe_parent *>(blob + at_parents);
+    *ranges = reinterpret_cast<const clsimhip_mcpe_parent_range *>(blob + at_ranges);
 }
 
 void Converter::release_result(const clsimhip_photon *photons)

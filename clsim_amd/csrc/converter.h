@@ -281,6 +281,8 @@ public:
     void set_mcpe_generator(std::shared_ptr<McpeGenerator> g, bool keep_photons);
     // clsimhip_set_mcpe_series: the sorting stage behind the hit maker (mcpe_series.h); needs a generator (Compile() checks)
     void set_mcpe_series(bool on) { guard(); compiled_ = false; series_ = on; }
+    // clsimhip_set_mcpe_merging: the merging stage behind the series stage (mcpe_merge.h); needs the series stage (Compile() checks)
+    void set_mcpe_merging(bool on, double window);
     // clsimhip_set_pmt_generator: the multi-PMT hit maker runs behind every bunch's propagation (null: off)
     void set_pmt_generator(std::shared_ptr<PmtHitGenerator> g, bool keep_photons);
 
@@ -301,6 +303,8 @@ public:
     void result_mcpes(const clsimhip_photon *photons, const clsimhip_mcpe **mcpes, size_t *n);
     void result_mcpe_series(const clsimhip_photon *photons, const clsimhip_mcpe **mcpes, size_t *n, const clsimhip_mcpe_series **series, size_t *n_series,
                             uint64_t *n_masked);
+    void result_mcpe_merged(const clsimhip_photon *photons, const clsimhip_mcpe_merged **merged, size_t *n_merged, const clsimhip_mcpe_series **series,
+                            size_t *n_series, const clsimhip_mcpe_parent **parents, size_t *n_parents, const clsimhip_mcpe_parent_range **ranges);
     void result_pmt_hits(const clsimhip_photon *photons, const clsimhip_pmt_hit **hits, size_t *n);
     void release_result(const clsimhip_photon *photons);
     size_t queue_size() const;
@@ -371,6 +375,12 @@ private:
         uint64_t masked = 0;
         std::unique_ptr<std::vector<clsimhip_mcpe_series>> series;
         const clsimhip_mcpe_series *series_data() const { return series_pinned ? series_pinned.get() : (series ? series->data() : nullptr); }
+        // with the MCPE merging stage: merged records, merged series table, parent table and its ranges, one behind the other (every
+        // one starts at a multiple of 8 bytes) in a page-locked buffer of the merge pool or (pool exhausted) a vector
+        BlobPool::Lease merge_pinned;
+        std::unique_ptr<std::vector<uint64_t>> merge_blob;
+        size_t merged_count = 0, parent_count = 0;
+        const uint8_t *merge_data() const { return merge_pinned ? merge_pinned.get() : (merge_blob ? reinterpret_cast<const uint8_t *>(merge_blob->data()) : nullptr); }
         // with a PMT hit generator: the bunch's hits, kept as the MCPEs are (and `handle` for a result without photon records)
         PmtHitPool::Lease pmt_pinned;
         size_t pmt_count = 0;
@@ -404,6 +414,8 @@ private:
     std::shared_ptr<McpeGenerator> mcpe_;       // null: no MCPEs are made (the default)
     bool keep_photons_ = true;
     bool series_ = false;                       // the MCPE series stage runs behind the hit maker
+    bool merging_ = false;                      // the MCPE merging stage runs behind the series stage
+    double merge_window_ = 0.;
     std::shared_ptr<PmtHitGenerator> pmt_;      // null: no PMT hits are made (the default)
     bool pmt_keep_photons_ = true;
     bool carries_photons() const { return !(mcpe_ && !keep_photons_) && !(pmt_ && !pmt_keep_photons_); }
@@ -420,6 +432,7 @@ private:
     PhotonPool result_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
     McpePool mcpe_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
     SeriesPool series_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
+    BlobPool merge_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
     PmtHitPool pmt_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
     // particle tables and masks of the bunches on their way (input queue depth + one per slot + the one being filled)
     BlobPool bunch_pool_{PinnedPoolPolicy{8, size_t{1} << 28, nullptr}};
@@ -455,6 +468,15 @@ private:
         DeviceBuffer<clsimhip_mcpe_series> d_series;
         DeviceBuffer<uint32_t> d_series_counts;
         PinnedBuffer<uint32_t> h_series_counts;
+        // with the MCPE merging stage: its workspace, merged records, merged series table, parents, ranges, two counts
+        DeviceBuffer<uint8_t> d_merge_workspace;
+        size_t merge_workspace_bytes = 0;
+        DeviceBuffer<clsimhip_mcpe_merged> d_merged;
+        DeviceBuffer<clsimhip_mcpe_series> d_merged_series;
+        DeviceBuffer<clsimhip_mcpe_parent> d_parents;
+        DeviceBuffer<clsimhip_mcpe_parent_range> d_ranges;
+        DeviceBuffer<uint32_t> d_merge_counts;
+        PinnedBuffer<uint32_t> h_merge_counts;
         BlobPool::Lease bunch_lease;            // the pool buffer the slot's table upload reads; back to the pool when the slot is used again
         PinnedBuffer<uint8_t> h_bunch;          // pinned staging (for a job that came without a pool buffer)
         size_t h_bunch_bytes = 0;

@@ -145,4 +145,11 @@ struct SeriesDeviceArgs {
 // all kernels of the stage, asynchronous on `stream`
 hipError_t launch_mcpe_series(const SeriesDeviceArgs &A, hipStream_t stream);
 
+// Two pieces of the stage the MCPE merging stage (mcpe_merge.h) uses on keys of its own, with header, histogram, tile_counts, keys
+// and capacity of A filled in: header[SH_KEPT] keys in keys[0] and their 16 x 256 digit histogram -> the plan and all live passes
+// (the sorted keys are in keys[header[SH_FINAL]]); one count per tile of header[SH_KEPT] keys in tile_counts -> their exclusive
+// scan, the total in header[SH_SERIES].
+void launch_series_sort(const SeriesDeviceArgs &A, hipStream_t stream);
+void launch_series_tile_scan(const SeriesDeviceArgs &A, hipStream_t stream);
+
 } // namespace clsimhip

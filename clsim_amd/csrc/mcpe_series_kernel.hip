@@ -311,6 +311,30 @@ __global__ void __launch_bounds__(256) series_close_kernel(const SeriesDeviceArg
 
 } // namespace
 
+namespace {
+uint32_t tiles_of(uint32_t capacity)
+{
+    const uint32_t tiles = (uint32_t)(((uint64_t)capacity + kSeriesTile - 1u) / kSeriesTile);
+    return tiles == 0u ? 1u : tiles;
+}
+} // namespace
+
+void launch_series_sort(const SeriesDeviceArgs &A, hipStream_t stream)
+{
+    const uint32_t tiles = tiles_of(A.capacity);
+    hipLaunchKernelGGL(series_plan_kernel, dim3(1), dim3(64), 0, stream, A);
+    for (uint32_t pass = 0; pass < 16u; ++pass) {
+        hipLaunchKernelGGL(series_count_kernel, dim3(tiles), dim3(256), 0, stream, A, pass);
+        hipLaunchKernelGGL(series_scan_kernel, dim3(1), dim3(1024), 0, stream, A, pass);
+        hipLaunchKernelGGL(series_scatter_kernel, dim3(tiles), dim3(256), 0, stream, A, pass);
+    }
+}
+
+void launch_series_tile_scan(const SeriesDeviceArgs &A, hipStream_t stream)
+{
+    hipLaunchKernelGGL(series_scan_kernel, dim3(1), dim3(1024), 0, stream, A, 16u);
+}
+
 hipError_t launch_mcpe_series(const SeriesDeviceArgs &A, hipStream_t stream)
 {
     hipError_t e = hipMemsetAsync(A.header, 0, (kSeriesHeaderWords + 16u * 256u) * sizeof(uint32_t), stream);     // header and histogram lie together
@@ -318,17 +342,11 @@ hipError_t launch_mcpe_series(const SeriesDeviceArgs &A, hipStream_t stream)
     uint32_t lanes = (A.capacity + 255u) / 256u;
     if (A.capacity > 0xffffff00u || lanes > 1024u) lanes = 1024u;
     if (lanes == 0u) lanes = 1u;
-    uint32_t tiles = (uint32_t)(((uint64_t)A.capacity + kSeriesTile - 1u) / kSeriesTile);
-    if (tiles == 0u) tiles = 1u;
+    const uint32_t tiles = tiles_of(A.capacity);
     hipLaunchKernelGGL(series_key_kernel, dim3(lanes), dim3(256), 0, stream, A);
-    hipLaunchKernelGGL(series_plan_kernel, dim3(1), dim3(64), 0, stream, A);
-    for (uint32_t pass = 0; pass < 16u; ++pass) {
-        hipLaunchKernelGGL(series_count_kernel, dim3(tiles), dim3(256), 0, stream, A, pass);
-        hipLaunchKernelGGL(series_scan_kernel, dim3(1), dim3(1024), 0, stream, A, pass);
-        hipLaunchKernelGGL(series_scatter_kernel, dim3(tiles), dim3(256), 0, stream, A, pass);
-    }
+    launch_series_sort(A, stream);
     hipLaunchKernelGGL(series_heads_kernel, dim3(tiles), dim3(256), 0, stream, A);
-    hipLaunchKernelGGL(series_scan_kernel, dim3(1), dim3(1024), 0, stream, A, 16u);
+    launch_series_tile_scan(A, stream);
     hipLaunchKernelGGL(series_emit_kernel, dim3(tiles), dim3(256), 0, stream, A);
     hipLaunchKernelGGL(series_close_kernel, dim3(lanes), dim3(256), 0, stream, A);
     return hipGetLastError();

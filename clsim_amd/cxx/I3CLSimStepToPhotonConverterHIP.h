@@ -213,6 +213,7 @@ public:
         r.photons = I3CLSimPhotonSeriesPtr(new I3CLSimPhotonSeries(n));
         lastMCPEs_.clear();
         lastSeries_.clear();
+        lastMerged_.clear(); lastMergedSeries_.clear(); lastParents_.clear(); lastParentRanges_.clear();
         lastMasked_ = 0;
         if (mcpeGenerator_) {       // (ConversionResult_t has no place for them: GetLastMCPEs())
             const clsimhip_mcpe *m = nullptr;
@@ -222,6 +223,17 @@ public:
                 size_t ns = 0;
                 check(clsimhip_get_result_mcpe_series(handle_, p, &m, &nm, &s, &ns, &lastMasked_));
                 lastSeries_.assign(s, s + ns);
+                if (mcpeMerging_) {
+                    const clsimhip_mcpe_merged *g = nullptr;
+                    const clsimhip_mcpe_parent *q = nullptr;
+                    const clsimhip_mcpe_parent_range *ranges = nullptr;
+                    size_t ng = 0, nq = 0;
+                    check(clsimhip_get_result_mcpe_merged(handle_, p, &g, &ng, &s, &ns, &q, &nq, &ranges));
+                    lastMerged_.assign(g, g + ng);
+                    lastMergedSeries_.assign(s, s + ns);
+                    lastParents_.assign(q, q + nq);
+                    lastParentRanges_.assign(ranges, ranges + ns);
+                }
             } else
                 check(clsimhip_get_result_mcpes(handle_, p, &m, &nm));
             lastMCPEs_.assign(m, m + nm);
@@ -395,6 +407,44 @@ public:
         return frames;
     }
 
+    // ---- MCPE merging (include/clsimhip.h, "MCPE merging"): what stands where the client module's MCHitMerging::MCPEStream and
+    // extractMCPEsWithPIDInfo() do -- this project's own rule, unpinned against the reference.  Before Initialize(); needs
+    // SetMCPESeries.  GetLastMCPEs() / GetLastMCPESeries() stay the unmerged series. ----
+    void SetMCPEMerging(double window, bool on = true)
+    {
+        check(clsimhip_set_mcpe_merging(handle_, on ? 1 : 0, window));
+        mcpeMerging_ = on;
+    }
+    // the flat views of the last result: merged records, their series table (the entries of GetLastMCPESeries(), over the merged
+    // records), the parent table and one range of it per series
+    const std::vector<clsimhip_mcpe_merged> &GetLastMergedMCPEs() const { return lastMerged_; }
+    const std::vector<clsimhip_mcpe_series> &GetLastMergedMCPESeries() const { return lastMergedSeries_; }
+    const std::vector<clsimhip_mcpe_parent> &GetLastMCPEParents() const { return lastParents_; }
+    const std::vector<clsimhip_mcpe_parent_range> &GetLastMCPEParentRanges() const { return lastParentRanges_; }
+    // ... and as the frames receive them: frame -> (string ID, OM ID) -> merged MCPEs (an I3MCPESeriesMap per frame), and
+    // frame -> (string ID, OM ID) -> identifier -> indices into that DOM's merged MCPEs, ascending (an I3ParticleIDMap per frame)
+    typedef std::map<std::pair<int, unsigned>, std::vector<clsimhip_mcpe_merged> > MergedMCPESeriesMap;
+    typedef std::map<std::pair<int, unsigned>, std::map<uint32_t, std::vector<uint32_t> > > ParticleIDMap;
+    std::map<uint32_t, MergedMCPESeriesMap> GetLastMergedMCPESeriesMaps() const
+    {
+        std::map<uint32_t, MergedMCPESeriesMap> frames;
+        for (const clsimhip_mcpe_series &s : lastMergedSeries_)
+            frames[s.frame][std::make_pair(static_cast<int>(s.string_id), static_cast<unsigned>(s.om_id))]
+                .assign(lastMerged_.begin() + s.first, lastMerged_.begin() + s.first + s.count);
+        return frames;
+    }
+    std::map<uint32_t, ParticleIDMap> GetLastParticleIDMaps() const
+    {
+        std::map<uint32_t, ParticleIDMap> frames;
+        for (size_t k = 0; k < lastMergedSeries_.size(); ++k) {
+            const clsimhip_mcpe_series &s = lastMergedSeries_[k];
+            std::map<uint32_t, std::vector<uint32_t> > &dom = frames[s.frame][std::make_pair(static_cast<int>(s.string_id), static_cast<unsigned>(s.om_id))];
+            for (uint32_t i = lastParentRanges_[k].first; i < lastParentRanges_[k].first + lastParentRanges_[k].count; ++i)
+                dom[lastParents_[i].identifier].push_back(lastParents_[i].index);
+        }
+        return frames;
+    }
+
 private:
     void check(int rc) const
     {
@@ -415,6 +465,11 @@ private:
     bool mcpeSeries_ = false;
     std::vector<clsimhip_mcpe_series> lastSeries_;
     uint64_t lastMasked_ = 0;
+    bool mcpeMerging_ = false;
+    std::vector<clsimhip_mcpe_merged> lastMerged_;
+    std::vector<clsimhip_mcpe_series> lastMergedSeries_;
+    std::vector<clsimhip_mcpe_parent> lastParents_;
+    std::vector<clsimhip_mcpe_parent_range> lastParentRanges_;
     bool pmtHitGenerator_ = false;
     std::vector<clsimhip_pmt_hit> lastPMTHits_;
 #ifdef CLSIMHIP_WITH_ICETRAY

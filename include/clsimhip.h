@@ -801,7 +801,8 @@ int clsimhip_get_result_mcpes(clsimhip_converter *c, const clsimhip_photon *phot
  * bytes from run to run, whatever the schedule, and the same bytes from the kernels and the host twin.  The series table has one
  * entry per non-empty (frame, DOM) in the same order; its entries partition the records.
  * The reference adds the shift to the photon's time before the conversion, in the photon's precision; here it is added once, after
- * the arrival time correction, in binary64.  Hit merging (MergeHits) and the particle-ID map are not part of this. */
+ * the arrival time correction, in binary64.  Hit merging and the particle-ID map are the next stage ("MCPE merging"
+ * below). */
 typedef struct {                        /* one entry of the particle cache: the frame the particle belongs to and its time shift */
     uint32_t identifier;                /* strictly increasing over the table (CLSIMHIP_ERR_ARGUMENT otherwise) */
     uint32_t frame;                     /* the caller's frame ID, any value */
@@ -858,6 +859,75 @@ int clsimhip_enqueue_steps_with_particles(clsimhip_converter *c, const clsimhip_
  * NULL) receives the MASKED count.  Pointers are NULL where there is nothing.  CLSIMHIP_ERR_STATE without clsimhip_set_mcpe_series. */
 int clsimhip_get_result_mcpe_series(clsimhip_converter *c, const clsimhip_photon *photons, const clsimhip_mcpe **mcpes, size_t *n,
                                     const clsimhip_mcpe_series **series, size_t *n_series, uint64_t *n_masked);
+
+/* ---- MCPE merging: the records of a series within a time window become one, with the particle-ID map ----------------------
+ * The reference never commits the unmerged series: I3CLSimClientModule pushes every MCPE through MCHitMerging::MCPEStream
+ * (public/clsim/I3CLSimClientModule.h:193-194, private/clsim/I3CLSimClientModule.cxx:430) and at frame end puts
+ * extractMCPEsWithPIDInfo()'s two objects into the frame (:710-719): the merged I3MCPESeriesMap (npe >= 1, the particle taken out
+ * of the record) and <name>ParticleIDMap (per DOM and per particle, the indices of the merged MCPEs the particle contributed to);
+ * the older module does the same behind its time sort (dom/I3PhotonToMCPEConverter.cxx:524-533).  The stream class lies outside
+ * the reference (sim-services) and its result depends on insertion order, which no two runs repeat.  THE RULE BELOW IS THIS
+ * PROJECT'S OWN DEFINITION, UNPINNED AGAINST THE REFERENCE; it exists once, compiled for the host twin and for the kernels.
+ * Input: the output of the series stage -- records ascending in (frame, DOM rank, tkey, identifier), partitioned by the series
+ * table.  Parameter: window, a binary64 with 0 <= window < +inf (anything else: CLSIMHIP_ERR_ARGUMENT; there is no default, the
+ * reference's value lives outside the reference).  Per series, the records in order; a record OPENS A GROUP when
+ *     it is the first record of its series, or
+ *     its time is not finite, or
+ *     the opener of the current group has a time that is not finite, or
+ *     time - T > window, T the time of the record that opened the current group: one binary64 subtraction and one >, the rounded
+ *     difference decides;
+ * otherwise it joins the current group.  Groups never span series; particles do not matter for grouping.
+ * One merged record per group: time = the opener's time, npe = the number of records in the group.  The merged series table has
+ * the same entries in the same order as the input table; first and count refer to merged records.  The parent table is the
+ * flattened I3ParticleIDMap: one entry per distinct (identifier, group) of a series, `index` = the group's position within its
+ * series' merged records, ascending in (series, identifier, index); the parallel range table has one entry per series.
+ * All outputs are functions of the input arrays: the same bytes from run to run, and from the kernels and the host twin.
+ * fl(t - T) is monotone in t, so within the finite part of a series "the first record with t - T > window" is a well-defined
+ * cut; the sum of npe is the number of input records; consecutive finite openers of a series differ by more than window; every
+ * group spans at most window. */
+typedef struct {
+    uint32_t npe;
+    int16_t string_id;
+    uint16_t om_id;
+    double time;
+} clsimhip_mcpe_merged;                 /* 16 bytes */
+typedef struct {
+    uint32_t identifier;
+    uint32_t index;                     /* of the merged record, within its series */
+} clsimhip_mcpe_parent;                 /* 8 bytes */
+typedef struct {
+    uint32_t first, count;              /* parent entries [first, first + count) of one series */
+} clsimhip_mcpe_parent_range;           /* 8 bytes */
+typedef char clsimhip_mcpe_merged_is_16_bytes[sizeof(clsimhip_mcpe_merged) == 16 ? 1 : -1];
+typedef char clsimhip_mcpe_parent_is_8_bytes[sizeof(clsimhip_mcpe_parent) == 8 ? 1 : -1];
+typedef char clsimhip_mcpe_parent_range_is_8_bytes[sizeof(clsimhip_mcpe_parent_range) == 8 ? 1 : -1];
+/* The host twin: a sequential walk, std::sort and std::unique for the parents.  Host only, no GPU is touched.  series must
+ * partition the n records in order (CLSIMHIP_ERR_ARGUMENT otherwise).  out_merged and out_parents hold n entries each, out_series
+ * and out_ranges n_series. */
+int clsimhip_mcpe_merge_host(const clsimhip_mcpe *records, size_t n, const clsimhip_mcpe_series *series, size_t n_series, double window,
+                             clsimhip_mcpe_merged *out_merged, clsimhip_mcpe_series *out_series, clsimhip_mcpe_parent *out_parents,
+                             clsimhip_mcpe_parent_range *out_ranges, size_t *n_merged, size_t *n_parents);
+/* bytes of device memory the kernels need beside their input and output, for up to `capacity` records */
+size_t clsimhip_mcpe_merge_workspace_bytes(size_t capacity);
+/* The kernels, on series that live in HBM (pairs with clsimhip_mcpe_series_device: d_records = its d_out, d_series and
+ * d_series_counts = its d_series and d_counts): min(d_series_counts[0], capacity) records, min(d_series_counts[1], capacity)
+ * series.  d_merged, d_merged_series, d_parents and d_ranges: `capacity` entries each, 8-byte aligned; d_counts: two uint32 --
+ * merged records, parent entries; d_workspace: clsimhip_mcpe_merge_workspace_bytes(capacity) bytes, 16-byte aligned.
+ * g: the generator whose series these are (it must be there; the stage itself needs nothing from it).  Asynchronous on hip_stream
+ * (NULL = default stream); nothing waits for the device.  Errors are CLSIMHIP_ERR_ARGUMENT. */
+int clsimhip_mcpe_merge_device(clsimhip_mcpe_generator *g, int device, const void *d_records, const void *d_series,
+                               const void *d_series_counts, size_t capacity, double window, void *d_merged, void *d_merged_series,
+                               void *d_parents, void *d_ranges, void *d_counts, void *d_workspace, size_t workspace_bytes, void *hip_stream);
+/* The stage behind every bunch's series stage, on the bunch's stream.  Before Initialize() only (CLSIMHIP_ERR_STATE after);
+ * Compile() refuses it without clsimhip_set_mcpe_series (CLSIMHIP_ERR_CONFIG).  on = 0 (the default): no launch, no byte changes
+ * anywhere. */
+int clsimhip_set_mcpe_merging(clsimhip_converter *c, int on, double window);
+/* Merged records, merged series table, parent table and its ranges (n_series entries) of the result `photons` belongs to, valid
+ * until clsimhip_release_result(c, photons); pointers are NULL where there is nothing.  clsimhip_get_result_mcpe_series keeps
+ * returning the unmerged series of the same bunch.  CLSIMHIP_ERR_STATE without clsimhip_set_mcpe_merging. */
+int clsimhip_get_result_mcpe_merged(clsimhip_converter *c, const clsimhip_photon *photons, const clsimhip_mcpe_merged **merged,
+                                    size_t *n_merged, const clsimhip_mcpe_series **series, size_t *n_series,
+                                    const clsimhip_mcpe_parent **parents, size_t *n_parents, const clsimhip_mcpe_parent_range **ranges);
 
 /* ---- Multi-PMT hit generator: detected photons -> hits on the PMTs of segmented modules ---------------------------------
  * The hit maker for modules that carry several PMTs (KM3NeT-style spheres): FindHitPMT and the per-photon body of

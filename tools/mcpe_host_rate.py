@@ -8,6 +8,10 @@ No GPU: the committed photon records of tests/golden/verbatim_cl_*.npz, repeated
 second, on N synthetic MCPEs at IceCube's 5160 DOMs dealt to 1000 particles in 10 frames; --device adds the device stage's time
 for the same input (HIP events around clsimhip_mcpe_series_device, best of --repeats; needs a GPU).
 
+--merge: the MCPE merging host twin instead (clsimhip_mcpe_merge_host), in records per second, on one DOM with 130 000 records of 7
+particles as a long chain of groups (window 5 ns) and as one group, and on 300 000 synthetic records in 420 series (window 2 ns);
+--device adds the device stage's time for the same inputs (HIP events around clsimhip_mcpe_merge_device; needs a GPU).
+
 --pmt: the multi-PMT hit generator's host twin instead (clsimhip_pmt_convert_host) on the same records, against the 31-PMT layout
 of tests/pmt_common.py, in photon records per second.
 """
@@ -70,6 +74,49 @@ def series_rate(args):
     print(json.dumps(line))
 
 
+def merge_rate(args):
+    from tests import mcpe_merge_common as MM
+    from tests import mcpe_series_common as S
+    gen = S.synthetic_generator()
+    dom = MM.series_of(gen, MM.one_dom(130000, seed=3))
+    m = S.synthetic_mcpes(300000, seed=9, n_identifiers=3000)
+    many = gen.MakeSeriesHost(m, S.particle_table(m["id"], frames=(50, 10, 40, 20, 30)))[:2]
+    for name, (records, series), window in (("one_dom_long_chain", dom, 5.0), ("one_dom_one_group", dom, 2e6), ("synthetic_300000", many, 2.0)):
+        best = float("inf")
+        for _ in range(args.repeats):
+            t0 = time.perf_counter()
+            want = CV.MCPEGenerator.MergeHost(records, series, window)
+            best = min(best, time.perf_counter() - t0)
+        n = len(records)
+        line = {"input": name, "records": n, "series": len(series), "window": window, "merged": len(want[0]), "parents": len(want[2]),
+                "host_seconds": best, "host_records_per_s": n / best, "threads": 1}
+        if args.device:
+            import torch
+            dev = torch.device("cuda", 0)
+            d_records = torch.from_numpy(records.view(np.uint8).copy()).to(dev)
+            d_series = torch.zeros(n * 16, dtype=torch.uint8, device=dev)
+            d_series[:len(series) * 16] = torch.from_numpy(series.view(np.uint8).copy()).to(dev)
+            d_series_counts = torch.tensor([n, len(series), 0, 0, 0], dtype=torch.int32, device=dev)
+            outs = [torch.zeros(n * size, dtype=torch.uint8, device=dev) for size in (16, 16, 8, 8)]
+            d_counts = torch.zeros(2, dtype=torch.int32, device=dev)
+            ws = CV.MCPEGenerator.MergeWorkspaceBytes(n)
+            d_ws = torch.zeros(ws, dtype=torch.uint8, device=dev)
+            stream = torch.cuda.current_stream().cuda_stream
+            times = []
+            for _ in range(args.repeats + 1):
+                start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                start.record()
+                gen.MergeDevice(d_records.data_ptr(), d_series.data_ptr(), d_series_counts.data_ptr(), n, window, outs[0].data_ptr(), outs[1].data_ptr(),
+                                outs[2].data_ptr(), outs[3].data_ptr(), d_counts.data_ptr(), d_ws.data_ptr(), ws, stream=stream)
+                stop.record()
+                torch.cuda.synchronize()
+                times.append(start.elapsed_time(stop) * 1e-3)
+            assert [int(c) for c in d_counts.cpu()] == [len(want[0]), len(want[2])]
+            assert outs[0].cpu().numpy()[:len(want[0]) * 16].tobytes() == want[0].tobytes() and outs[2].cpu().numpy()[:len(want[2]) * 8].tobytes() == want[2].tobytes()
+            line.update(device_seconds=min(times[1:]), device_records_per_s=n / min(times[1:]))
+        print(json.dumps(line))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--records", type=int, default=2000000)
@@ -77,7 +124,10 @@ def main():
     ap.add_argument("--series", type=int, default=0, metavar="N")
     ap.add_argument("--device", action="store_true")
     ap.add_argument("--pmt", action="store_true")
+    ap.add_argument("--merge", action="store_true")
     args = ap.parse_args()
+    if args.merge:
+        return merge_rate(args)
     if args.series:
         return series_rate(args)
     base = np.concatenate([M.fixture_photons(name) for name in M.FIXTURES if name != "lea_no_pancake"])     # recorded with pancake 5

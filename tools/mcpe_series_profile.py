@@ -3,7 +3,9 @@
 the MCPE series stage, steps dealt to 1000 particles in 10 frames: the run to put under `rocprofv3 --kernel-trace --stats` to see
 the stage's kernels beside the propagation kernel.  Prints the counts and the host-side wall time of the bunch.
 
-    rocprofv3 --kernel-trace --stats -d OUT -- python tools/mcpe_series_profile.py [--steps 1048576] [--no-series]
+    rocprofv3 --kernel-trace --stats -d OUT -- python tools/mcpe_series_profile.py [--steps 1048576] [--no-series] [--merge-window NS]
+
+--merge-window NS: the MCPE merging stage behind the series stage, with that window.
 """
 import argparse
 import json
@@ -23,6 +25,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=1 << 20)
     ap.add_argument("--no-series", action="store_true")
+    ap.add_argument("--merge-window", type=float, default=None, metavar="NS")
     args = ap.parse_args()
     cfg = common.config("mie")
     g = cfg["geom"]
@@ -31,7 +34,7 @@ def main():
     bias = CV.GetIceCubeDOMAcceptance()
     conv = CV.initializeHIP(0, CV.I3CLSimSimpleGeometry.from_dict(g), cfg["med_p"], bias, common.product_generators(cfg, bias), pancakeFactor=5.0,
                             stopDetectedPhotons=True, approximateNumberOfWorkItems=args.steps, mcpeGenerator=gen, keepPhotons=False,
-                            mcpeSeries=not args.no_series)
+                            mcpeSeries=not args.no_series, mcpeMergeWindow=args.merge_window)
     steps = common.steps_for(cfg, args.steps, seed=3).copy()
     steps["id"] = np.arange(len(steps)) % 1000
     p = np.zeros(1000, dtype=CV.MCPE_PARTICLE_DTYPE)
@@ -45,7 +48,8 @@ def main():
         r = conv.GetConversionResult()
         wall = time.perf_counter() - t0
     print(json.dumps({"steps": len(steps), "photons": int(steps["num"].sum()), "mcpes": len(r.mcpes),
-                      "series": None if r.series is None else len(r.series), "wall_seconds_second_bunch": wall}))
+                      "series": None if r.series is None else len(r.series),
+                      "merged": None if r.merged is None else len(r.merged), "parents": None if r.parents is None else len(r.parents), "wall_seconds_second_bunch": wall}))
 
 
 if __name__ == "__main__":
