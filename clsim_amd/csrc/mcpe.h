@@ -60,7 +60,19 @@ struct McpeParams {
     uint32_t capacity, out_capacity;
 };
 
+// The Cephes branch's quadrant count as an int32, for EVERY float: what gfx950's conversion instruction gives for dm::sincos_cephes_'s
+// (int32_t)k -- it saturates, and a NaN gives 0.  (The C++ conversion is undefined outside int32, and x86-64 yields INT32_MIN there.)
+inline int32_t mcpe_quadrant_host(float k)
+{
+    if (k != k) return 0;
+    if (k >= 2147483648.0f) return INT32_MAX;
+    if (k <= -2147483648.0f) return INT32_MIN;
+    return (int32_t)k;
+}
+
 // ---- dm::sincos_ on the host: the same operations on the same constants (detmath.hip.h: sincos_2pi_with_, sincos_cephes_) ----
+// Total: an angle beyond the int32 quadrant range (|x| from about 3.37e9, infinities, NaNs) takes the saturated count above.  There
+// the reduced argument is meaningless (huge, or a NaN for an infinite or NaN angle); the results are what the operations give.
 inline void mcpe_sincos_host(float x, float &s, float &c)
 {
     if (x >= 0.0f && x <= dm::SINCOS_2PI_MAX) {
@@ -93,11 +105,11 @@ inline void mcpe_sincos_host(float x, float &s, float &c)
     pc = pc * (z * z);
     pc = __builtin_fmaf(-0.5f, z, pc);
     pc = pc + 1.0f;
-    const int32_t q = (int32_t)k;
-    const float a = (q & 1) ? pc : ps;
-    const float b = (q & 1) ? ps : pc;
-    s = (q & 2) ? -a : a;
-    c = ((q + 1) & 2) ? -b : b;
+    const uint32_t q = (uint32_t)mcpe_quadrant_host(k);                 // (unsigned: q + 1 wraps at INT32_MAX, as the device's add does)
+    const float a = (q & 1u) ? pc : ps;
+    const float b = (q & 1u) ? ps : pc;
+    s = (q & 2u) ? -a : a;
+    c = ((q + 1u) & 2u) ? -b : b;
 }
 
 MCPE_HD void mcpe_sincos(float x, float &s, float &c)
@@ -194,7 +206,11 @@ MCPE_HD int mcpe_make(const McpeParams &P, Values values, const uint32_t *w, cls
     out.identifier = w[10];
     out.string_id = (int16_t)(w[11] & 0xffffu);
     out.om_id = (uint16_t)(w[11] >> 16);
-    out.time = (double)mcpe_f(w[3]) + dot * P.time_factor / (double)mcpe_f(w[18]);
+    double time = (double)mcpe_f(w[3]) + dot * P.time_factor / (double)mcpe_f(w[18]);
+    // a NaN time has ONE bit pattern: which of two NaN operands an addition passes on is the target's (and the compiler's) business --
+    // measured: x86-64 and gfx950 differ there, while both generate 0xfff8000000000000 -- and the series stage orders records by the time's bits
+    if (time != time) time = __builtin_bit_cast(double, (uint64_t)0x7ff8000000000000ull);
+    out.time = time;
     return MCPE_ACCEPTED;
 }
 

@@ -134,7 +134,7 @@ MCPE_HD int pmt_make(const PmtHitParams &P, Values values, Pmts pmts, const uint
     return PMT_ACCEPTED;
 }
 
-// bytes of LDS a launch with these parameters asks for (the function values, then the PMT tables)
+// bytes of LDS a launch with these parameters asks for (the PMT tables, then the function values: pmt_hits_kernel's layout)
 inline size_t pmt_hits_lds_bytes(const PmtHitParams &P) { return (size_t)P.num_values * sizeof(double) + (size_t)P.num_pmts * sizeof(PmtEntry); }
 
 // pmt_hits_kernel.hip: P.values / P.pmts / P.module_table / P.modules in device memory; asynchronous on `stream`

@@ -737,7 +737,16 @@ int clsimhip_tabulator_get_last_launch(const clsimhip_tabulator *t, int out[6]);
  *     u = (h >> 11) 2^-53, h = seed folded with splitmix64 over the record's ten 64-bit words;
  *     time = photon time + (-position . direction) (1 - pancake / oversize) / group velocity.
  * All of it is binary64 + - x / in one fixed order (the two sin / cos pairs of the direction: the library's deterministic single
- * precision ones), so the HIP kernel and the host twin give the same bits.  The reference draws u from an I3RandomService in
+ * precision ones), so the HIP kernel and the host twin give the same bits -- for every 80-byte pattern, physical or not:
+ *     angles: any float.  Outside [0, 2 pi] the sin / cos pair reduces by multiples of pi / 2 with a quadrant count held in an int32;
+ *     where the count does not fit (|angle| from about 3.37e9, infinities) it saturates to INT32_MAX / INT32_MIN, for a NaN it is 0
+ *     (what gfx950's conversion gives; the twin says so explicitly).  Such a direction is meaningless but defined: finite garbage for a
+ *     huge angle, NaNs for an infinite or NaN angle, and a NaN -direction z clamps to 1;
+ *     comparisons with a NaN are false: a NaN weight, acceptance or P passes both P > 1 and P <= u and yields an MCPE, a NaN r^2 is
+ *     OFF_SURFACE, a NaN wavelength reads the table's last bin; float32 denormals are kept (nothing is flushed);
+ *     time: the formula's value, infinities included; a NaN, however it came about (a NaN photon time or group velocity, 0 / 0 from
+ *     a zero group velocity with pancake = oversize, inf - inf), is stored as the one pattern 0x7ff8000000000000.
+ * The reference draws u from an I3RandomService in
  * arrival order, which no two runs repeat; keying the draw on the record makes the result independent of the schedule and
  * takes nothing from the propagator's RNG streams.  The four named conditions are log_fatal in the reference. */
 typedef struct {                        /* I3MCPE(particle, npe = 1, time); the particle's major / minor ID and time shift are */
@@ -949,7 +958,10 @@ int clsimhip_get_result_mcpe_merged(clsimhip_converter *c, const clsimhip_photon
  * G (glass / gel survival), Q (quantum efficiency) and A (angular acceptance factor, tabulated over c = cos of the hit angle) are
  * clsimhip_functions of kinds TABLE and CONSTANT.  The path length the reference hands to the glass / gel survival is NOT modelled
  * (it needs an exponential the reference does not define).  Binary64 + - x / in one fixed order, as for the MCPE generator: the HIP
- * kernel and the host twin give the same bits. */
+ * kernel and the host twin give the same bits, for every 80-byte pattern.  Angles of any size, infinite or NaN: as for the MCPE
+ * generator.  Comparisons with a NaN are false, so a NaN direction skips no PMT and ends on the type's last one (a NaN path length is
+ * replaced by any later intersection), and a NaN weight or P yields a hit.  The hit's time is the record's binary32 time widened:
+ * infinities stay, a NaN keeps its sign and payload and is made quiet. */
 typedef struct {
     double sphere_radius;               /* of the module's sphere [m]: the radius photons are recorded at */
     int32_t first_pmt, n_pmts;          /* its PMTs in the `pmts` array (1 ... 64); a hit's `pmt` counts from first_pmt */

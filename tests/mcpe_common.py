@@ -88,7 +88,8 @@ def numpy_mcpes(photons, tables, class_of, coefficients, pancake, seed=SEED, dom
     st, ct = capi.eval_math(2, ph["theta"]).astype(np.float64), capi.eval_math(3, ph["theta"]).astype(np.float64)
     sp, cp = capi.eval_math(2, ph["phi"]).astype(np.float64), capi.eval_math(3, ph["phi"]).astype(np.float64)
     dx, dy, dz = st * cp, st * sp, ct
-    c = np.maximum(-1.0, np.minimum(1.0, -dz))
+    c = np.where(-dz < 1.0, -dz, 1.0)                   # (c < 1 ? c : 1, then c > -1 ? c : -1: a NaN gives 1, which np.minimum would pass on)
+    c = np.where(c > -1.0, c, -1.0)
     k = np.asarray(class_of(ph["stringID"], ph["omID"]), dtype=np.int64)
     counters["unknown_dom"] = int((alive & (k < 0)).sum())
     alive &= k >= 0
@@ -125,6 +126,7 @@ def numpy_mcpes(photons, tables, class_of, coefficients, pancake, seed=SEED, dom
     accepted = alive & ~(P <= u)
     dot = (-x) * dx + (-y) * dy + (-z) * dz
     time = ph["t"].astype(np.float64) + dot * (1.0 - pancake / oversize) / ph["groupVelocity"].astype(np.float64)
+    time = np.where(np.isnan(time), np.uint64(0x7ff8000000000000).view(np.float64), time)       # a NaN time has one bit pattern
     out = np.zeros(int(accepted.sum()), dtype=CV.MCPE_DTYPE)
     out["id"], out["stringID"], out["omID"], out["time"] = ph["id"][accepted], ph["stringID"][accepted], ph["omID"][accepted], time[accepted]
     return out, counters, P[alive], accepted[alive]
