@@ -8,7 +8,8 @@ import ctypes as C
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("CLSIMHIP_LIB", os.path.join(HERE, "libclsimhip.so"))
+DEFAULT_LIB_PATH = os.path.join(HERE, "libclsimhip.so")
+LIB_PATH = os.environ.get("CLSIMHIP_LIB", DEFAULT_LIB_PATH)
 
 OK, ERR_ARGUMENT, ERR_STATE, ERR_CONFIG, ERR_DEVICE, ERR_IO = 0, -1, -2, -3, -4, -5
 REFINDEX_ICECUBE, REFINDEX_TABLE, REFINDEX_DISPERSION = 0, 1, 2       # include/clsimhip.h: CLSIMHIP_REFINDEX_*
@@ -107,7 +108,7 @@ SYMBOLS = [
     "clsimhip_eval_math", "clsimhip_check_math_exhaustive", "clsimhip_version",
     "clsimhip_eval_device_function", "clsimhip_eval_device_random", "clsimhip_get_option",
     "clsimhip_set_tuning", "clsimhip_get_tuning", "clsimhip_tabulator_set_tuning",
-    "clsimhip_get_last_launch", "clsimhip_tabulator_get_last_launch",
+    "clsimhip_get_last_launch", "clsimhip_tabulator_get_last_launch", "clsimhip_baked_info", "clsimhip_baked_compile", "clsimhip_baked_set_compiler_library",
     "clsimhip_count_generated_steps", "clsimhip_generate_steps_device", "clsimhip_generate_steps",
     "clsimhip_ppc_create", "clsimhip_ppc_destroy", "clsimhip_ppc_photons_per_meter", "clsimhip_ppc_enqueue", "clsimhip_shower_parameters",
     "clsimhip_flasher_correction_factor", "clsimhip_flasher_enqueue",
@@ -240,6 +241,9 @@ def load():
         "clsimhip_get_tuning": (i32, [vp, C.c_char_p, C.POINTER(C.c_longlong)]),
         "clsimhip_tabulator_set_tuning": (i32, [vp, C.c_char_p, C.c_longlong]),
         "clsimhip_get_last_launch": (i32, [vp, C.POINTER(C.c_int)]),
+        "clsimhip_baked_set_compiler_library": (i32, [C.c_char_p]),
+        "clsimhip_baked_info": (i32, [vp, C.POINTER(C.c_int), C.c_char_p, C.c_char_p, C.c_size_t]),
+        "clsimhip_baked_compile": (i32, [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_double), C.c_char_p, C.c_size_t]),
         "clsimhip_tabulator_get_last_launch": (i32, [vp, C.POINTER(C.c_int)]),
         "clsimhip_eval_device_function": (i32, [vp, i32, i32, i32, vp, sz, vp]),
         "clsimhip_eval_device_random": (i32, [vp, i32, i32, i32, vp, vp, sz, sz, vp]),
@@ -317,7 +321,15 @@ def load():
         "clsimhip_tabulator_write_fits_file": (i32, [vp, C.c_char_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double), sz]),
     }
     for name in SYMBOLS:
+        # (A/B measurements load an older build through CLSIMHIP_LIB: it may lack the entries of the run-time compiled kernel, which
+        # bench.py does not call)
+        if name in ("clsimhip_baked_info", "clsimhip_baked_compile", "clsimhip_baked_set_compiler_library") and LIB_PATH != DEFAULT_LIB_PATH and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.restype, fn.argtypes = sig[name]
+    # The library reads no environment variable for its run-time compiler: CLSIMHIP_HIPRTC_LIBRARY is read here, as
+    # CLSIMHIP_LIB is, and handed in through the C ABI before anything is compiled.
+    if os.environ.get("CLSIMHIP_HIPRTC_LIBRARY") and hasattr(lib, "clsimhip_baked_set_compiler_library"):
+        lib.clsimhip_baked_set_compiler_library(os.fsencode(os.environ["CLSIMHIP_HIPRTC_LIBRARY"]))
     _lib = lib
     return lib

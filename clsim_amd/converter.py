@@ -875,6 +875,24 @@ class I3CLSimStepToPhotonConverterHIP:
         self._call("clsimhip_get_last_launch", out)
         return _lib.launched_dict(out)
 
+    BAKED_STATES = {0: "unused", 1: "baked", 2: "fallback"}
+
+    def GetBakedInfo(self):
+        """clsimhip_baked_info: {state: 'unused' | 'baked' | 'fallback', key, why} of the last launch that asked for the pooled kernel
+        compiled for this configuration (tuning "baked_kernel")"""
+        state, key, why = C.c_int(), C.create_string_buffer(33), C.create_string_buffer(4096)
+        self._call("clsimhip_baked_info", C.byref(state), key, why, len(why))
+        return {"state": self.BAKED_STATES[state.value], "key": key.value.decode(), "why": why.value.decode(errors="replace")}
+
+    def CompileBakedKernel(self, arch="gfx950", flags=None, code_path=None):
+        """clsimhip_baked_compile (after Compile(), no GPU needed): {compiled, key, seconds, why}; the code object goes to code_path"""
+        key, why, seconds = C.create_string_buffer(33), C.create_string_buffer(4096), C.c_double()
+        r = self._lib.clsimhip_baked_compile(self._h, arch.encode(), None if flags is None else flags.encode(),
+                                             None if code_path is None else os.fsencode(code_path), key, C.byref(seconds), why, len(why))
+        if r < 0:
+            _check(int(r), self._h)
+        return {"compiled": bool(r), "key": key.value.decode(), "seconds": seconds.value, "why": why.value.decode(errors="replace")}
+
     # ---- the reference's tester classes (private/test/I3CLSim*Tester): single functions evaluated on the device ----
     EVAL = {"lengths": 0, "refraction": 1, "wavelength_bias": 2, "tilt": 3, "abs_len_scaling": 4, "pre_scatter_transform": 5,
             "post_scatter_transform": 6}

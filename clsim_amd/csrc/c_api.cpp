@@ -416,6 +416,39 @@ int clsimhip_kernel_for_bunch(const clsimhip_converter *c, size_t n_steps, int *
 {
     return guarded_const(c, [&] { need(c, "converter"); need(out, "out"); *out = c->impl.pooled_for(n_steps) ? 1 : 0; });
 }
+int clsimhip_baked_compile(const clsimhip_converter *c, const char *arch, const char *flags, const char *code_path, char key[33], double *seconds,
+                           char *why, size_t why_bytes)
+{
+    int compiled = 0;
+    const int status = guarded_const(c, [&] {
+        need(c, "converter"); need(arch, "arch");
+        const BakedResult r = c->impl.baked_compile_probe(arch, flags);
+        if (key) std::snprintf(key, 33, "%s", r.key.c_str());
+        if (seconds) *seconds = r.seconds;
+        if (why && why_bytes) std::snprintf(why, why_bytes, "%s", r.why.c_str());
+        if (r.ok && code_path) {
+            std::FILE *f = std::fopen(code_path, "wb");
+            if (!f || std::fwrite(r.code.data(), 1, r.code.size(), f) != r.code.size()) { if (f) std::fclose(f); throw Error(CLSIMHIP_ERR_ARGUMENT, "cannot write the code object"); }
+            std::fclose(f);
+        }
+        compiled = r.ok ? 1 : 0;
+    });
+    return status != CLSIMHIP_OK ? status : compiled;
+}
+int clsimhip_baked_set_compiler_library(const char *path)
+{
+    return guarded(nullptr, [&] { baked_set_compiler_library(path ? path : ""); });
+}
+int clsimhip_baked_info(const clsimhip_converter *c, int *state, char key[33], char *why, size_t why_bytes)
+{
+    return guarded_const(c, [&] {
+        need(c, "converter");
+        const BakedReport r = c->impl.baked_report();
+        if (state) *state = r.state;
+        if (key) std::snprintf(key, 33, "%s", r.key.c_str());
+        if (why && why_bytes) std::snprintf(why, why_bytes, "%s", r.why.c_str());
+    });
+}
 int clsimhip_get_device(const clsimhip_converter *c, int *out)
 {
     return guarded_const(c, [&] { need(c, "converter"); need(out, "out"); *out = c->impl.device(); });

@@ -37,11 +37,18 @@ hipError_t Converter::launch(const KParams &P, const LaunchTuning &tuning, hipSt
     v.generic_only = tuning.generic_only;
     KLaunched launched;
     v.launched = &launched;
+    // the kernel compiled for this configuration: on the bunches the launcher itself sends to the pooled kernel -- their launches last
+    // long enough for the one-off compilation to vanish in a run; the small bunches of tests take it only where asked to ("baked_kernel" 2)
+    BakedReport baked;
+    if (pooled && tuning.baked_kernel == 2) baked.wanted = 2;
+    else if (pooled && tuning.baked_kernel == 1 && P.n_steps * static_cast<size_t>(concurrent_launches_) >= kPooledKernelMinSteps) baked.wanted = 1;
+    v.baked = &baked;
     const hipError_t err = v.keep_detected ? (pooled ? launch_pool_keep_kernel(P, v, stream) : launch_keep_kernel(P, v, stream))
                                            : (pooled ? launch_pool_kernel(P, v, stream) : launch_prop_kernel(P, v, stream));
     if (launched.family >= 0) {              // (an empty bunch launches nothing: the report of the last real launch stays)
         std::lock_guard<std::mutex> lk(launched_mutex_);
         launched_ = launched;
+        if (baked.state != kBakedUnused) baked_ = baked;
     }
     return err;
 }
@@ -89,6 +96,7 @@ const TuningKey kTuningKeys[] = {
     {"k_aim", -1, 64, LAUNCH_FIELD(k_aim)},
     {"grid", 0, 1 << 20, LAUNCH_FIELD(grid)},
     {"generic_kernels", 0, 1, LAUNCH_FIELD(generic_only)},
+    {"baked_kernel", 0, 2, LAUNCH_FIELD(baked_kernel)},
     {"result_min_records", 1, 1ll << 32, LAUNCH_FIELD(result_min_records)},
     {"string_map_cells", 8, 4096, TABLE_FIELD(string_map_cells)},
     {"dom_map_cells", 4, 512, TABLE_FIELD(dom_map_cells)},
@@ -117,9 +125,23 @@ void Converter::set_tuning(const std::string &key, long long value)
 
 long long Converter::get_tuning(const std::string &key) const
 {
+    if (key == "baked_state") return baked_report().state;       // (read only: kBakedUnused, kBakedActive, kBakedFallback)
     const TuningKey &k = tuning_key(key);
     std::lock_guard<std::mutex> lk(tuning_mutex_);
     return k.get(tuning_, table_tuning_);
+}
+
+BakedResult Converter::baked_compile_probe(const char *arch, const char *flags) const
+{
+    BakedResult r;
+    if (!compiled_) { r.why = "Compile() first"; return r; }
+    const KVariant &v = tables_.variant;
+    LaunchTuning t;
+    {
+        std::lock_guard<std::mutex> lk(tuning_mutex_);
+        t = tuning_;
+    }
+    return baked_compile(tables_.params, BakedVariant{v.lengths, v.tilt, v.aniso, v.flasher, v.fast && !t.generic_only, v.keep_detected}, arch, flags);
 }
 
 void Converter::set_concurrent_device_launches(int k)

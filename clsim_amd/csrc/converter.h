@@ -16,6 +16,7 @@
 
 #include "hip_resources.h"
 #include "host_model.h"
+#include "baked_kernel.h"
 #include "kparams.h"
 #include "prop_launch.h"
 
@@ -244,6 +245,9 @@ struct LaunchTuning {
                                                  // constants); 0 is honoured: never wait / never ask
     int grid = 0;
     bool generic_only = false;                   // "generic_kernels"
+    int baked_kernel = 1;                        // "baked_kernel": the pooled kernel compiled for this configuration (baked_kernel.h): 0 never, 1 for
+                                                 // the bunches the launcher itself sends to the pooled kernel, in the instantiation it was measured to pay
+                                                 // for (prop_pool_kernel.hip.h: kBakedPays); 2 every instantiation, also where it was forced on smaller bunches
     size_t result_min_records = 65536;           // (tests make the result buffers grow with small bunches)
     // derived by Converter::apply_kernel_choice() once initialized
     bool derived = false;
@@ -335,6 +339,10 @@ public:
     bool uses_pooled_kernel() const { need_init(); const LaunchTuning t = tuning_snapshot(); return t.use_pool && t.pool_min_steps == 0; }     // for every bunch size
     // clsimhip_get_last_launch: the instantiation the last launch (worker or device path) dispatched to, every field -1 before the first
     KLaunched last_launch() const { std::lock_guard<std::mutex> lk(launched_mutex_); return launched_; }
+    // clsimhip_baked_info: what the last pooled launch that wanted the run-time compiled kernel got ("baked_state" of clsimhip_get_tuning)
+    BakedReport baked_report() const { std::lock_guard<std::mutex> lk(launched_mutex_); return baked_; }
+    // clsimhip_baked_compile: compiles this configuration's pooled kernel without a device (after Compile()); never throws
+    BakedResult baked_compile_probe(const char *arch, const char *flags) const;
 
 private:
     using StepPool = PinnedPool<clsimhip_step>;
@@ -527,6 +535,7 @@ private:
     hipError_t launch(const KParams &P, const LaunchTuning &tuning, hipStream_t stream) const;
     mutable std::mutex launched_mutex_;          // launched_: the worker (or a device-path caller) writes, any thread reads
     mutable KLaunched launched_;
+    mutable BakedReport baked_;                  // (under launched_mutex_ too)
 
     // worker + queues (in: capacity 5 like queueToOpenCL_, OpenCL.cxx:77)
     std::unique_ptr<BoundedQueue<Job>> in_queue_;

@@ -17,8 +17,10 @@
 // 17 vector instructions in place of 22 and 31.  The propagation kernels read the two tables from the front of their LDS
 // image (prop_device.hip.h: lds_log / lds_sincos_2pi; kMathTableWords), every other kernel from the global copies below.
 #pragma once
+#ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#endif
 
 #include "math_tables.h"
 

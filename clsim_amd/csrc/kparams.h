@@ -12,7 +12,9 @@
 // The reference bakes the same values into the OpenCL source as #defines and
 // __constant arrays (MediumPropertiesSource.cxx:207-389, GeometrySource.cxx:1153-1269).
 #pragma once
+#ifndef __HIPCC_RTC__      // (the run-time compiler brings the fixed-width types itself)
 #include <stdint.h>
+#endif
 
 namespace clsimhip {
 
@@ -49,6 +51,13 @@ static_assert(sizeof(WorkRecord) == 64, "work record");
 static_assert(sizeof(DevStep) == 48, "step record");
 static_assert(sizeof(DevPhoton) == 80, "photon record");
 
+// The run-time compiled pooled kernel (baked_kernel.h) sees a KParams of its own in this place: the members fixed by Compile() as
+// `static constexpr` -- `P->member` reads those as well -- and the others as fields at the offsets they have here.  A member added
+// below is also added to kparams_members.inc.  (The Makefile preprocesses the device headers for that kernel with KPARAMS_BAKED defined as a
+// name the generated source defines in turn.)
+#ifdef KPARAMS_BAKED
+KPARAMS_BAKED
+#else
 struct KParams {
     // ---- buffers ----
     const uint32_t *tables;             // LDS image (table_words words)
@@ -218,12 +227,15 @@ struct KParams {
     // with its own wait in every trip): k_pop | k_search << 8 | k_aim << 16 | k_wait << 24, every field below 256 (the launcher packs them)
     uint32_t k_packed;
 };
+#endif
 
 // The instantiation a launch dispatched to: the template arguments of launch_variant / launch_pool_variant, written by them on the host
 // where the kernel is launched (clsimhip_get_last_launch; family: CLSIMHIP_FAMILY_*, -1 before the first launch)
 struct KLaunched {
     int family = -1, lengths = -1, tilt = -1, aniso = -1, flasher = -1, fast = -1;
 };
+
+struct BakedReport;
 
 // kernel variants (the reference's #ifdef switches, OpenCL.cxx:390-442 and the
 // generated *_IS_CONSTANT / NO_FLASHER hints)
@@ -241,6 +253,7 @@ struct KVariant {
     bool generic_only = false;      // the generic instantiation also where Compile() found every proof ("generic_kernels")
     bool tab_fast = false;          // table maker: the FAST instantiation (measured slower, prop_tab_kernel.hip: launch_tab_kernel) ("fast_kernels")
     KLaunched *launched = nullptr;  // where the launcher reports the instantiation it took (host memory of the caller; may be null)
+    BakedReport *baked = nullptr;   // pooled kernels: asks for the run-time compiled kernel and takes the answer (baked_kernel.h; may be null)
 };
 
 } // namespace clsimhip

@@ -4,7 +4,9 @@
 //   mwcrng_kernel.cl:12-28 and the generated medium / spectrum / geometry functions,
 // each function citing the lines it restates.  Scheduling lives in the kernels; nothing here depends on it.
 #pragma once
+#ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
+#endif
 
 #include "detmath.hip.h"
 #include "../../include/clsimhip.h"
@@ -131,6 +133,11 @@ DM float clampf_ordered(float v, float lo, float hi) { return __builtin_amdgcn_f
 // clampi(v, 0, hi) for a wave-uniform hi >= 0 (a table dimension minus one, in a scalar register)
 DM int clamp_index(int v, int hi)
 {
+#ifdef KPARAMS_BAKED
+    // (run-time compiled kernel: the dimension is a constant, and for constant bounds the compiler forms the median itself, with the
+    // bound as an inline operand where the encoding has room for it -- the "s" constraint would put it back into a scalar register)
+    if (__builtin_constant_p(hi)) return clampi(v, 0, hi);
+#endif
     int r;
     asm("v_med3_i32 %0, %1, 0, %2" : "=v"(r) : "v"(v), "s"(hi));
     return r;
@@ -261,6 +268,18 @@ struct ScatterK {
     float rcp_mix_frac, rcp_mix_frac_rest, rcp_hg_two_g;
     uint32_t div_ok;
 };
+#ifdef KPARAMS_BAKED
+// (run-time compiled kernel: the ten are literals, there is nothing to load)
+DM ScatterK scatter_constants(KP P)
+{
+    ScatterK K;
+    K.mix_frac = P->mix_frac; K.mix_frac_rest = P->mix_frac_rest; K.liu_beta = P->liu_beta; K.hg_g = P->hg_g;
+    K.hg_one_minus_g2 = P->hg_one_minus_g2; K.hg_one_plus_g2 = P->hg_one_plus_g2; K.hg_two_g = P->hg_two_g;
+    K.rcp_mix_frac = P->rcp_mix_frac; K.rcp_mix_frac_rest = P->rcp_mix_frac_rest; K.rcp_hg_two_g = P->rcp_hg_two_g;
+    K.div_ok = P->div_ok;
+    return K;
+}
+#else
 static_assert(offsetof(KParams, hg_two_g) - offsetof(KParams, mix_frac) == 24 && offsetof(KParams, liu_beta) - offsetof(KParams, mix_frac) == 8,
               "mix_frac, mix_frac_rest, liu_beta, hg_g, hg_one_minus_g2, hg_one_plus_g2, hg_two_g are seven consecutive floats");
 static_assert(offsetof(KParams, div_ok) - offsetof(KParams, rcp_tilt_dz) == 20 && offsetof(KParams, rcp_mix_frac) - offsetof(KParams, rcp_tilt_dz) == 8,
@@ -279,6 +298,7 @@ DM ScatterK scatter_constants(KP P)
     K.div_ok = b[5];
     return K;
 }
+#endif
 // HenyeyGreenstein.cxx:69-92
 template <bool FAST = false>
 DM float hg_cos(const ScatterK &K, float u)
@@ -334,7 +354,9 @@ DM float abs_len_corr(KP P, const Vec3 &d)
     return (FAST || (P->div_ok & kFastAniso) != 0u) ? 2.0f * dm::rcp_(x) : 2.0f / x;
 }
 // VectorTransformMatrix.cxx:101-135
-DM void apply_matrix(const __attribute__((address_space(4))) float *m, int renorm, Vec3 &d, bool fast)
+// (M: a pointer to the nine floats in the kernel arguments, or -- run-time compiled kernel, baked_kernel.h -- to the literals themselves)
+template <typename M>
+DM void apply_matrix(M m, int renorm, Vec3 &d, bool fast)
 {
     const float x = (m[0] * d.x) + (m[1] * d.y) + (m[2] * d.z);
     const float y = (m[3] * d.x) + (m[4] * d.y) + (m[5] * d.z);

@@ -14,7 +14,7 @@ hipError_t launch_pool_keep_kernel(const KParams &P, const KVariant &v, hipStrea
     if (P.n_steps > kPoolIndexMask) return hipErrorInvalidValue;          // (a pending entry keeps the step index in 23 bits: Converter::pooled_for() says so first)
     const bool fast = v.fast && !v.generic_only;       // (as launch_pool_kernel)
     return dispatch_variant(v, fast, [&](auto med, auto tilt, auto aniso, auto flasher, auto fast_tag) {
-        return launch_pool_variant<med(), tilt(), aniso(), flasher(), fast_tag(), true>(P, stream, v.grid, v.launched);
+        return launch_pool_variant<med(), tilt(), aniso(), flasher(), fast_tag(), true>(P, stream, v.grid, v.launched, v.baked);
     });
 }
 

@@ -14,7 +14,7 @@ hipError_t launch_pool_kernel(const KParams &P, const KVariant &v, hipStream_t s
     // clsimhip_set_tuning("generic_kernels", 1): the generic instantiation also where Compile() found every proof (tests compare the two)
     const bool fast = v.fast && !v.generic_only;
     return dispatch_variant(v, fast, [&](auto med, auto tilt, auto aniso, auto flasher, auto fast_tag) {
-        return launch_pool_variant<med(), tilt(), aniso(), flasher(), fast_tag(), false>(P, stream, v.grid, v.launched);
+        return launch_pool_variant<med(), tilt(), aniso(), flasher(), fast_tag(), false>(P, stream, v.grid, v.launched, v.baked);
     });
 }
 

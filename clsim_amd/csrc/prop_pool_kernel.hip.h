@@ -24,12 +24,17 @@
 // still created and propagated in sequence from its own stream, whichever lanes carry them.
 //
 // Build: hipcc --offload-arch=gfx950 -ffp-contract=off.
+#ifndef __HIPCC_RTC__      // (the run-time compiled kernel, baked_kernel.h, takes the device side of this file only)
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#endif
 
 #include "prop_device.hip.h"
+#ifndef __HIPCC_RTC__
+#include "baked_kernel.h"
 #include "prop_launch.h"
+#endif
 
 namespace clsimhip {
 
@@ -559,6 +564,7 @@ __global__ void __launch_bounds__(kPoolBlock, kPoolMinWaves) prop_pool_kernel(co
     )
 }
 
+#ifndef __HIPCC_RTC__
 // ring entries per wave that fit beside a table image of `table_words` words (two workgroups per CU share 160 KB; the image is per
 // workgroup, the rest goes to the waves' pools); keep_strings: the detector's strings without STOP_PHOTONS_ON_DETECTION, else 0
 static int pool_ring_that_fits(uint32_t table_words, uint32_t keep_strings)
@@ -570,7 +576,7 @@ static int pool_ring_that_fits(uint32_t table_words, uint32_t keep_strings)
 
 // ---- host side: the launch of one instantiation (launch_pool_kernel, launch_pool_keep_kernel dispatch to it) ----
 template <int MED, bool TILT, bool ANISO, bool FLASHER, bool FAST, bool KEEP>
-static hipError_t launch_pool_variant(const KParams &Pin, hipStream_t stream, int grid_wanted = 0, KLaunched *launched = nullptr)
+static hipError_t launch_pool_variant(const KParams &Pin, hipStream_t stream, int grid_wanted = 0, KLaunched *launched = nullptr, BakedReport *baked = nullptr)
 {
     KParams P = Pin;
     if (launched) *launched = KLaunched{KEEP ? CLSIMHIP_FAMILY_POOL_KEEP : CLSIMHIP_FAMILY_POOL, MED, TILT, ANISO, FLASHER, FAST};      // (as launch_variant)
@@ -650,10 +656,36 @@ static hipError_t launch_pool_variant(const KParams &Pin, hipStream_t stream, in
     }
     hipError_t err = launch_scan_steps(P, stream);
     if (err != hipSuccess) return err;
-    hipLaunchKernelGGL((prop_pool_kernel<MED, TILT, ANISO, FLASHER, FAST, KEEP>), dim3(grid), dim3(kPoolBlock), lds_launch, stream, P);
+    // The same instantiation compiled for this configuration (baked_kernel.h), where the caller asks for it and it can be had: same
+    // kernarg bytes, same grid, same LDS.  Anything that fails on the way -- the launch itself included -- runs the precompiled kernel.
+    // Measured (round 7, profiles/r07/ab_default_line.txt; this kernel against the precompiled one): IceCube lengths + tilt, FAST, no anisotropy,
+    // no flasher +2.6 % (C2), the same without STOP_PHOTONS_ON_DETECTION +2.9 %; with anisotropy -1.2 % (C3), with anisotropy and flasher
+    // -1.4 % (C5): gfx950's three-operand encodings take no 32-bit literal, and the matrices' constants go through registers the kernel
+    // does not have to spare.  Unasked ("baked_kernel" = 1) only the instantiation that gained takes it.
+    constexpr bool kBakedPays = (MED == CLSIMHIP_LENGTHS_ICECUBE) && TILT && !ANISO && !FLASHER && FAST;
+    bool baked_launched = false;
+    if (baked && (baked->wanted == 2 || (baked->wanted == 1 && kBakedPays))) {
+        const BakedVariant bv{MED, TILT, ANISO, FLASHER, FAST, KEEP};
+        std::string why;
+        if (void *function = baked_pool_function(P, bv, &why, &baked->key)) {
+            size_t bytes = sizeof(P);
+            void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &P, HIP_LAUNCH_PARAM_BUFFER_SIZE, &bytes, HIP_LAUNCH_PARAM_END};
+            const hipError_t e = hipModuleLaunchKernel(static_cast<hipFunction_t>(function), grid, 1, 1, kPoolBlock, 1, 1, (unsigned int)lds_launch, stream, nullptr, config);
+            if (e == hipSuccess) baked_launched = true;
+            else {
+                (void)hipGetLastError();
+                why = std::string("launch: ") + hipGetErrorString(e);
+                baked_disable(P, bv, why);
+            }
+        }
+        baked->state = baked_launched ? kBakedActive : kBakedFallback;
+        baked->why = why;
+    }
+    if (!baked_launched) hipLaunchKernelGGL((prop_pool_kernel<MED, TILT, ANISO, FLASHER, FAST, KEEP>), dim3(grid), dim3(kPoolBlock), lds_launch, stream, P);
     err = hipGetLastError();
     if (err != hipSuccess) return err;
     return launch_assemble_hits(P, FLASHER, stream);
 }
+#endif // __HIPCC_RTC__
 
 } // namespace clsimhip

@@ -19,8 +19,10 @@
 #ifndef CLSIMHIP_H
 #define CLSIMHIP_H
 
+#ifndef __HIPCC_RTC__      /* (the device headers include this file for its constants; the run-time compiler has no C library) */
 #include <stddef.h>
 #include <stdint.h>
+#endif
 
 #ifdef __cplusplus
 extern "C" {
@@ -395,6 +397,29 @@ int clsimhip_uses_pooled_kernel(const clsimhip_converter *c, int *out);
 #define CLSIMHIP_FAMILY_TAB4 4      /* table maker, 4 axes                                     */
 #define CLSIMHIP_FAMILY_TAB5 5      /* table maker, 5 axes (impact angle)                      */
 int clsimhip_get_last_launch(const clsimhip_converter *c, int out[6]);
+/* The pooled kernel compiled at run time for this converter's configuration ("baked_kernel" of clsimhip_set_tuning): hiprtc, loaded
+ * with dlopen, compiles the
+ * instantiation the launcher would take, with the values Compile() fixed as literals.  Pointers, sizes and launcher thresholds stay
+ * kernel arguments.  Results are those of the precompiled kernel, bit for bit.
+ * Two more keys of clsimhip_set_tuning / clsimhip_get_tuning belong to it: "baked_kernel" = 0 never; 1 (the default) for the bunches
+ * the launcher itself sends to the pooled kernel, where the instantiation is the one it was measured to pay for (IceCube lengths with
+ * tilt, no anisotropy, no flasher, every proof of Compile() in hand: +2.6 %; with anisotropy or a flasher it lost 1.2 - 1.4 %) -- the
+ * first such launch compiles, synchronously, in about a second; 2 every instantiation, also on smaller bunches on which "kernel"
+ * forced the pooled kernel (tests).  Whatever fails -- no library, a compile error, more than 80
+ * vector registers or scratch in the result, a load or launch error -- runs the precompiled kernel and says so once on stderr.
+ * "baked_state" (read only) is that of the last launch that asked for the kernel: 0 none yet, 1 it ran, 2 the precompiled one ran.
+ * clsimhip_baked_info: state as "baked_state"; key: the module's cache key (32 hexadecimal digits + NUL; over the generated source, the
+ * options, the architecture and the compiler's version); why: the reason of a fallback.  Any pointer may be null.
+ * clsimhip_baked_compile (after Compile(), no GPU needed): compiles for `arch` ("gfx950") with `flags` (null: the library's own) and
+ * writes the code object to code_path (may be null).  Returns 1 = compiled, 0 = not (why says it: the launches would run the
+ * precompiled kernel), negative = a status.
+ * clsimhip_baked_set_compiler_library: the hiprtc to load (null or "": libhiprtc.so.7, libhiprtc.so), and then no other is tried; it
+ * counts until the first compilation of the process.  The library itself reads no environment variable for this; the Python binding
+ * passes on CLSIMHIP_HIPRTC_LIBRARY when it loads the library. */
+int clsimhip_baked_set_compiler_library(const char *path);
+int clsimhip_baked_info(const clsimhip_converter *c, int *state, char key[33], char *why, size_t why_bytes);
+int clsimhip_baked_compile(const clsimhip_converter *c, const char *arch, const char *flags, const char *code_path, char key[33], double *seconds,
+                           char *why, size_t why_bytes);
 /* copies the compiled table `name` (e.g. "geoStringPosX", "aDust400") converted to
  * double into out[0..cap); returns the entry count or a negative status.
  * "kernel_variant" (after Compile, no GPU needed): the key the launchers dispatch on, as Compile() derived it from the
