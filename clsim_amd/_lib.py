@@ -133,6 +133,8 @@ SYMBOLS = [
     "clsimhip_get_result_mcpe_merged",
     "clsimhip_pmt_generator_create", "clsimhip_pmt_generator_destroy", "clsimhip_pmt_generator_last_error",
     "clsimhip_pmt_convert_host", "clsimhip_pmt_convert_device", "clsimhip_set_pmt_generator", "clsimhip_get_result_pmt_hits",
+    "clsimhip_pmt_series_host", "clsimhip_pmt_series_workspace_bytes", "clsimhip_pmt_series_device", "clsimhip_set_pmt_series",
+    "clsimhip_get_result_pmt_series",
 ]
 
 # clsimhip_get_last_launch: CLSIMHIP_FAMILY_* and CLSIMHIP_LENGTHS_* by name
@@ -318,6 +320,11 @@ def load():
         "clsimhip_pmt_convert_device": (i32, [vp, i32, vp, vp, sz, vp, sz, vp, vp]),
         "clsimhip_set_pmt_generator": (i32, [vp, vp, i32]),
         "clsimhip_get_result_pmt_hits": (i32, [vp, vp, C.POINTER(vp), C.POINTER(sz)]),
+        "clsimhip_pmt_series_host": (i32, [vp, vp, sz, vp, sz, vp, sz, vp, vp, C.POINTER(sz), C.POINTER(sz), vp]),
+        "clsimhip_pmt_series_workspace_bytes": (sz, [sz, sz, sz]),
+        "clsimhip_pmt_series_device": (i32, [vp, i32, vp, vp, sz, vp, sz, vp, sz, vp, vp, vp, vp, sz, vp]),
+        "clsimhip_set_pmt_series": (i32, [vp, i32]),
+        "clsimhip_get_result_pmt_series": (i32, [vp, vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(u64)]),
         "clsimhip_tabulator_write_fits_file": (i32, [vp, C.c_char_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double), sz]),
     }
     for name in SYMBOLS:

@@ -469,6 +469,10 @@ PMT_DTYPE = np.dtype([("axis", "<f8", (3,)), ("position", "<f8", (3,)), ("radius
 PMT_MODULE_DTYPE = np.dtype([("stringID", "<i4"), ("omID", "<u4"), ("type", "<i4"), ("reserved", "<i4"), ("rotation", "<f8", (9,))])
 PMT_HIT_DTYPE = np.dtype([("id", "<u4"), ("stringID", "<i2"), ("omID", "<u2"), ("pmt", "<u4"), ("reserved", "<u4"), ("time", "<f8")])
 PMT_CONDITIONS = ("unknown_module", "probability_above_one", "off_surface")
+# PMT series (include/clsimhip.h): one series of the result; the particle table and the mask are the MCPE series'
+PMT_SERIES_DTYPE = np.dtype([("frame", "<u4"), ("stringID", "<i2"), ("omID", "<u2"), ("pmt", "<u4"), ("first", "<u4"), ("count", "<u4"),
+                             ("reserved", "<u4")])
+PMT_SERIES_COUNTERS = ("unknown_particle", "masked", "unknown_channel")
 
 
 class PMTHitGenerator:
@@ -516,13 +520,45 @@ class PMTHitGenerator:
         _check(self._lib.clsimhip_pmt_convert_device(self._h, int(device), C.c_void_p(d_photons), C.c_void_p(d_hit_count), int(capacity),
                                                      C.c_void_p(d_hits), int(hit_capacity), C.c_void_p(d_counters), C.c_void_p(stream)))
 
+    def MakeSeriesHost(self, hits, particles=None, masked=None):
+        """(records, series, counters): the host twin of the PMT series stage.  hits: PMT_HIT_DTYPE; particles: MCPE_PARTICLE_DTYPE,
+        strictly increasing in `id` (None: no table -- one frame, 0, no shift); masked: MCPE_MASK_DTYPE (all PMTs of a module).
+        records: the kept hits with shifted times, ascending in (frame, stringID, omID, pmt, time key, id); series:
+        PMT_SERIES_DTYPE, one entry per non-empty (frame, module, PMT); counters = {name: count} (PMT_SERIES_COUNTERS)"""
+        hits = np.ascontiguousarray(hits, dtype=PMT_HIT_DTYPE)
+        keep, pp, n_p, masked, mp, n_m = _series_inputs(particles, masked)
+        out = np.zeros(len(hits), dtype=PMT_HIT_DTYPE)
+        series = np.zeros(len(hits), dtype=PMT_SERIES_DTYPE)
+        n_kept, n_series, counters = C.c_size_t(), C.c_size_t(), np.zeros(3, dtype=np.uint64)
+        _check(self._lib.clsimhip_pmt_series_host(self._h, hits.ctypes.data_as(C.c_void_p), len(hits), pp, n_p, mp, n_m,
+                                                  out.ctypes.data_as(C.c_void_p), series.ctypes.data_as(C.c_void_p), C.byref(n_kept),
+                                                  C.byref(n_series), counters.ctypes.data_as(C.c_void_p)))
+        return out[:n_kept.value], series[:n_series.value], dict(zip(PMT_SERIES_COUNTERS, (int(c) for c in counters)))
+
+    @staticmethod
+    def SeriesWorkspaceBytes(capacity, n_particles=0, n_masked=0):
+        return int(_lib.load().clsimhip_pmt_series_workspace_bytes(int(capacity), int(n_particles), int(n_masked)))
+
+    def MakeSeriesDevice(self, d_hits, d_count, capacity, d_out, d_series, d_counts, d_workspace, workspace_bytes, particles=None, masked=None,
+                         device=0, stream=0):
+        """the kernels on device-resident hits (addresses; pairs with ConvertDevice: its d_hits and d_counters): min(*d_count,
+        capacity) records; d_out / d_series: `capacity` entries, d_counts: five uint32 (kept, series, then PMT_SERIES_COUNTERS),
+        d_workspace: SeriesWorkspaceBytes(capacity, len(particles), len(masked)) bytes.  particles / masked are host arrays as for
+        MakeSeriesHost."""
+        keep, pp, n_p, masked, mp, n_m = _series_inputs(particles, masked)
+        _check(self._lib.clsimhip_pmt_series_device(self._h, int(device), C.c_void_p(d_hits), C.c_void_p(d_count), int(capacity), pp, n_p, mp, n_m,
+                                                    C.c_void_p(d_out), C.c_void_p(d_series), C.c_void_p(d_counts), C.c_void_p(d_workspace),
+                                                    int(workspace_bytes), C.c_void_p(stream)))
+
 
 class ConversionResult(tuple):
     """What GetConversionResult / GetConversionResultInPlace return: the tuple (identifier, photons[, histories]) / (identifier,
     photons, release), with the bunch's MCPEs (MCPE_DTYPE) as attribute `mcpes` when the converter has an MCPE generator (None
     otherwise).  With the MCPE series stage `mcpes` are the sorted records, `series` their series table (MCPE_SERIES_DTYPE) and
     `masked` the bunch's MASKED count; with the MCPE merging stage `merged` (MCPE_MERGED_DTYPE), `merged_series`, `parents`
-    (MCPE_PARENT_DTYPE) and `parent_ranges` (MCPE_PARENT_RANGE_DTYPE) beside them.  With a PMT hit generator `pmt_hits` holds the bunch's hits (PMT_HIT_DTYPE)."""
+    (MCPE_PARENT_DTYPE) and `parent_ranges` (MCPE_PARENT_RANGE_DTYPE) beside them.  With a PMT hit generator `pmt_hits` holds the bunch's hits (PMT_HIT_DTYPE);
+    with the PMT series stage they are the sorted records, `pmt_series` their series table (PMT_SERIES_DTYPE) and `masked` the
+    bunch's MASKED count."""
     mcpes = None
     series = None
     masked = None
@@ -531,6 +567,7 @@ class ConversionResult(tuple):
     parents = None
     parent_ranges = None
     pmt_hits = None
+    pmt_series = None
 
 
 class I3CLSimStepToPhotonConverterHIP:
@@ -545,6 +582,7 @@ class I3CLSimStepToPhotonConverterHIP:
         self._series = False
         self._merging = False
         self._pmt = None
+        self._pmt_series = False
 
     def __del__(self):
         try:
@@ -605,6 +643,12 @@ class I3CLSimStepToPhotonConverterHIP:
         (result attributes `mcpes`, `series`, `masked`).  Before Initialize() only; Compile() refuses it without a generator."""
         self._call("clsimhip_set_mcpe_series", int(bool(on)))
         self._series = bool(on)
+    def SetPMTSeries(self, on=True):
+        """the sorting stage behind the PMT hit generator: every result's hits come back as per-frame, per-module, per-PMT time-sorted
+        series (result attributes `pmt_hits`, `pmt_series`, `masked`).  Before Initialize() only; Compile() refuses it without a PMT
+        hit generator."""
+        self._call("clsimhip_set_pmt_series", int(bool(on)))
+        self._pmt_series = bool(on)
     def SetMCPEMerging(self, window, on=True):
         """the merging stage behind the series stage: records of a series within `window` of their group's opener become one merged
         record (result attributes `merged`, `merged_series`, `parents`, `parent_ranges`; `mcpes` and `series` stay the unmerged
@@ -634,7 +678,8 @@ class I3CLSimStepToPhotonConverterHIP:
     # ---- steady state ----
     def EnqueueSteps(self, steps, identifier, particles=None, masked=None):
         """particles (MCPE_PARTICLE_DTYPE, strictly increasing in `id`) and masked (MCPE_MASK_DTYPE): the bunch's particle table and
-        ignored modules for the MCPE series stage (SetMCPESeries); without them the bunch is one frame, 0, with no shift"""
+        ignored modules for the MCPE series stage (SetMCPESeries) or the PMT series stage (SetPMTSeries); without them the bunch is
+        one frame, 0, with no shift"""
         if steps is None:
             raise I3CLSimStepToPhotonConverter_exception("Steps pointer is (null)!", _lib.ERR_ARGUMENT)
         steps = np.ascontiguousarray(steps, dtype=STEP_DTYPE)
@@ -681,9 +726,19 @@ class I3CLSimStepToPhotonConverterHIP:
         return tuple(out)
 
     def _result_pmt_hits(self, ptr):
-        """copy of the PMT hits of the result `ptr` belongs to (None without a PMT hit generator)"""
+        """copy of the PMT hits of the result `ptr` belongs to (None without a PMT hit generator); with the PMT series stage the
+        tuple (sorted records, series table, MASKED count)"""
         if self._pmt is None:
             return None
+        if self._pmt_series:
+            hp, hn, sp, sn, masked = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_size_t(), C.c_uint64()
+            self._call("clsimhip_get_result_pmt_series", ptr, C.byref(hp), C.byref(hn), C.byref(sp), C.byref(sn), C.byref(masked))
+            hits, series = np.zeros(hn.value, dtype=PMT_HIT_DTYPE), np.zeros(sn.value, dtype=PMT_SERIES_DTYPE)
+            if hn.value:
+                C.memmove(hits.ctypes.data, hp.value, hn.value * 24)
+            if sn.value:
+                C.memmove(series.ctypes.data, sp.value, sn.value * 24)
+            return hits, series, int(masked.value)
         hp, hn = C.c_void_p(), C.c_size_t()
         self._call("clsimhip_get_result_pmt_hits", ptr, C.byref(hp), C.byref(hn))
         hits = np.zeros(hn.value, dtype=PMT_HIT_DTYPE)
@@ -735,7 +790,7 @@ class I3CLSimStepToPhotonConverterHIP:
                 self._call("clsimhip_release_result", ptr)
         result = ConversionResult((ident.value, photons, histories) if with_histories else (ident.value, photons))
         self._attach_mcpes(result, mcpes)
-        result.pmt_hits = pmt_hits
+        self._attach_pmt_hits(result, pmt_hits)
         return result
 
     def GetConversionResultInPlace(self):
@@ -762,8 +817,14 @@ class I3CLSimStepToPhotonConverterHIP:
             view.flags.writeable = False
             result = ConversionResult((ident.value, view, (lambda: self._call("clsimhip_release_result", ptr))))
         self._attach_mcpes(result, mcpes)
-        result.pmt_hits = pmt_hits
+        self._attach_pmt_hits(result, pmt_hits)
         return result
+
+    def _attach_pmt_hits(self, result, pmt_hits):
+        if self._pmt_series and pmt_hits is not None:
+            result.pmt_hits, result.pmt_series, result.masked = pmt_hits
+        else:
+            result.pmt_hits = pmt_hits
 
     def _attach_mcpes(self, result, mcpes):
         if self._series and mcpes is not None:
@@ -933,13 +994,14 @@ def initializeHIP(device, geometry, medium, wavelengthGenerationBias, wavelength
                   enableDoubleBuffering=False, doublePrecision=False, stopDetectedPhotons=True, saveAllPhotons=False,
                   saveAllPhotonsPrescale=0.01, fixedNumberOfAbsorptionLengths=float("nan"), pancakeFactor=1.0,
                   photonHistoryEntries=0, limitWorkgroupSize=0, approximateNumberOfWorkItems=262144,
-                  seed=12345, streams=None, tuning=None, mcpeGenerator=None, keepPhotons=True, mcpeSeries=False, pmtHitGenerator=None, mcpeMergeWindow=None):
+                  seed=12345, streams=None, tuning=None, mcpeGenerator=None, keepPhotons=True, mcpeSeries=False, pmtHitGenerator=None, mcpeMergeWindow=None, pmtSeries=False):
     """Canonical configuration sequence, I3CLSimModuleHelper::initializeOpenCL
     (ModuleHelper.cxx:303-372).  tuning: {key: value} for clsimhip_set_tuning, applied before Compile().
     mcpeGenerator: an MCPEGenerator that turns every bunch's photons into MCPEs on the GPU (result attribute `mcpes`);
     keepPhotons=False then leaves the photon records on the device; mcpeSeries=True sorts them into per-frame, per-DOM series;
     mcpeMergeWindow=w then merges the records of a series within w of their group's opener (SetMCPEMerging).
-    pmtHitGenerator: a PMTHitGenerator instead, for modules with several PMTs (result attribute `pmt_hits`; keepPhotons as above)."""
+    pmtHitGenerator: a PMTHitGenerator instead, for modules with several PMTs (result attribute `pmt_hits`; keepPhotons as above);
+    pmtSeries=True sorts its hits into per-frame, per-module, per-PMT series (SetPMTSeries)."""
     conv = I3CLSimStepToPhotonConverterHIP(device)
     for key, value in (tuning or {}).items():
         conv.SetTuning(key, value)
@@ -963,6 +1025,8 @@ def initializeHIP(device, geometry, medium, wavelengthGenerationBias, wavelength
         conv.SetMCPEMerging(mcpeMergeWindow)
     if pmtHitGenerator is not None:
         conv.SetPMTHitGenerator(pmtHitGenerator, keepPhotons)
+    if pmtSeries:
+        conv.SetPMTSeries(True)
     conv.Compile()
     max_wg = conv.GetMaxWorkgroupSize()
     if limitWorkgroupSize:

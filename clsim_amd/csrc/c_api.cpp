@@ -15,6 +15,7 @@
 #include "mcpe.h"
 #include "mcpe_merge.h"
 #include "pmt_hits.h"
+#include "pmt_series.h"
 
 using namespace clsimhip;
 
@@ -1125,6 +1126,41 @@ int clsimhip_set_pmt_generator(clsimhip_converter *c, clsimhip_pmt_generator *g,
 int clsimhip_get_result_pmt_hits(clsimhip_converter *c, const clsimhip_photon *photons, const clsimhip_pmt_hit **hits, size_t *n)
 {
     return guarded(c, [&] { need(c, "converter"); c->impl.result_pmt_hits(photons, hits, n); });
+}
+
+// ---- PMT series (pmt_series.h) ----
+int clsimhip_pmt_series_host(const clsimhip_pmt_generator *g, const clsimhip_pmt_hit *hits, size_t n, const clsimhip_mcpe_particle *particles,
+                             size_t n_particles, const clsimhip_mcpe_mask *masked, size_t n_masked, clsimhip_pmt_hit *out,
+                             clsimhip_pmt_series *series, size_t *n_kept, size_t *n_series, uint64_t counters[3])
+{
+    return guarded(nullptr, [&] {
+        need(g, "generator");
+        if (counters) std::memset(counters, 0, 3 * sizeof(uint64_t));
+        g->impl->series_host(hits, n, particles, n_particles, masked, n_masked, out, series, n_kept, n_series, counters);
+    });
+}
+size_t clsimhip_pmt_series_workspace_bytes(size_t capacity, size_t n_particles, size_t n_masked)
+{
+    return pmt_series_workspace_bytes(capacity, n_particles, n_masked);
+}
+int clsimhip_pmt_series_device(clsimhip_pmt_generator *g, int device, const void *d_hits, const void *d_count, size_t capacity,
+                               const clsimhip_mcpe_particle *particles, size_t n_particles, const clsimhip_mcpe_mask *masked, size_t n_masked,
+                               void *d_out, void *d_series, void *d_counts, void *d_workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return guarded(nullptr, [&] {
+        need(g, "generator");
+        g->impl->series_device(device, d_hits, d_count, capacity, particles, n_particles, masked, n_masked, d_out, d_series, d_counts, d_workspace,
+                               workspace_bytes, static_cast<hipStream_t>(hip_stream));
+    });
+}
+int clsimhip_set_pmt_series(clsimhip_converter *c, int on)
+{
+    return guarded(c, [&] { need(c, "converter"); c->impl.set_pmt_series(on != 0); });
+}
+int clsimhip_get_result_pmt_series(clsimhip_converter *c, const clsimhip_photon *photons, const clsimhip_pmt_hit **hits, size_t *n,
+                                   const clsimhip_pmt_series **series, size_t *n_series, uint64_t *n_masked)
+{
+    return guarded(c, [&] { need(c, "converter"); c->impl.result_pmt_series(photons, hits, n, series, n_series, n_masked); });
 }
 
 } // extern "C"

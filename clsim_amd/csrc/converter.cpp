@@ -7,6 +7,7 @@
 #include "mcpe.h"
 #include "mcpe_merge.h"
 #include "pmt_hits.h"
+#include "pmt_series.h"
 
 #include <chrono>
 #include <cmath>
@@ -182,6 +183,7 @@ void Converter::release_device()
     series_pool_.reset();
     merge_pool_.reset();
     pmt_pool_.reset();
+    pmt_series_pool_.reset();
     bunch_pool_.reset();
 }
 
@@ -301,6 +303,7 @@ void Converter::compile()
 #endif
     if (series_ && !mcpe_) throw Error(CLSIMHIP_ERR_CONFIG, "MCPE series need an MCPE generator (clsimhip_set_mcpe_generator)");
     if (merging_ && !series_) throw Error(CLSIMHIP_ERR_CONFIG, "MCPE merging needs the MCPE series stage (clsimhip_set_mcpe_series)");
+    if (pmt_series_ && !pmt_) throw Error(CLSIMHIP_ERR_CONFIG, "PMT series need a PMT hit generator (clsimhip_set_pmt_generator)");
     if (mcpe_) {
         // the generator reads IDs from the records: every DOM's pair must fit them (the host conversion reports such IDs only when a
         // photon carries them, OpenCL.cxx:1577-1586) and must have a class (log_fatal per photon in the reference, :628-630)
@@ -522,6 +525,14 @@ void Converter::setup_device_buffers(DeviceState &D)
             sl.d_pmt_counters.alloc(4, "PMT hit counters");
             sl.h_pmt_counters.alloc(4, "pinned PMT hit counters");
         }
+        if (pmt_series_) {
+            sl.pmt_series_workspace_bytes = pmt_series_workspace_bytes(max_output_photons_, 0, 0);
+            sl.d_pmt_series_workspace.alloc(sl.pmt_series_workspace_bytes, "PMT series workspace");
+            sl.d_pmt_sorted.alloc(max_output_photons_, "sorted PMT hits");
+            sl.d_pmt_series.alloc(max_output_photons_, "PMT series table");
+            sl.d_pmt_series_counts.alloc(8, "PMT series counts");
+            sl.h_pmt_series_counts.alloc(8, "pinned PMT series counts");
+        }
         if (series_) {
             sl.series_workspace_bytes = mcpe_series_workspace_bytes(max_output_photons_, 0, 0);
             sl.d_series_workspace.alloc(sl.series_workspace_bytes, "MCPE series workspace");
@@ -627,8 +638,8 @@ void Converter::enqueue_steps(const clsimhip_step *steps, size_t n, uint32_t ide
                               const clsimhip_mcpe_mask *masked, size_t n_masked)
 {
     need_init();
-    if ((particles || n_particles || masked || n_masked) && !series_)
-        throw Error(CLSIMHIP_ERR_STATE, "a particle table or mask needs the MCPE series stage (clsimhip_set_mcpe_series)");
+    if ((particles || n_particles || masked || n_masked) && !series_ && !pmt_series_)
+        throw Error(CLSIMHIP_ERR_STATE, "a particle table or mask needs the MCPE series stage (clsimhip_set_mcpe_series) or the PMT series stage (clsimhip_set_pmt_series)");
     check_worker();
     if (!steps) throw Error(CLSIMHIP_ERR_ARGUMENT, "Steps pointer is (null)!");
     if (n == 0) throw Error(CLSIMHIP_ERR_ARGUMENT, "Steps are empty!");
@@ -641,16 +652,17 @@ void Converter::enqueue_steps(const clsimhip_step *steps, size_t n, uint32_t ide
     job.pinned = step_pool_.take(n, std::max(n, std::min(max_workitems_, n + n / 4)), device_);
     if (job.pinned) std::memcpy(job.pinned.get(), steps, n * sizeof(clsimhip_step));
     else job.steps.assign(steps, steps + n);
-    if (series_) {
+    if (series_ || pmt_series_) {
         // checked and brought into the stage's form here, in the caller's thread: a bad table is the caller's error, not the worker's
-        const size_t bytes = mcpe_series_blob_bytes(n_particles, n_masked);
+        const size_t bytes = series_ ? mcpe_series_blob_bytes(n_particles, n_masked) : pmt_series_blob_bytes(n_particles, n_masked);
         job.bunch_pinned = bunch_pool_.take(bytes, bytes + bytes / 4, device_);
         uint8_t *blob = job.bunch_pinned.get();
         if (!blob) {
             job.bunch_blob.resize((bytes + 15u) / 16u);
             blob = job.bunch_blob.data()->bytes;
         }
-        job.bunch = mcpe_->prepare_series(particles, n_particles, masked, n_masked, blob);
+        job.bunch = series_ ? mcpe_->prepare_series(particles, n_particles, masked, n_masked, blob)
+                            : pmt_->prepare_series(particles, n_particles, masked, n_masked, blob);
     }
     in_queue_->put(std::move(job));
 }
@@ -725,6 +737,29 @@ void Converter::submit(Slot &s, Job &job)
         pmt_->convert_device(device_, s.d_photons.get(), s.d_hit_count.get(), max_output_photons_, s.d_pmt_hits.get(), max_output_photons_, s.d_pmt_counters.get(), stream);
         hip_check(hipMemcpyAsync(s.h_pmt_counters.get(), s.d_pmt_counters.get(), 16, hipMemcpyDeviceToHost, stream), "download PMT hit counters");
     }
+    if (pmt_series_) {
+        // behind the PMT hit maker on the same stream, over the hits it stored; all counts stay on the device until finish() fetches them
+        s.bunch_lease = std::move(job.bunch_pinned);
+        const uint8_t *blob = s.bunch_lease.get();
+        if (!blob) {
+            if (s.h_bunch_bytes < job.bunch.bytes) {
+                s.h_bunch.reset();
+                s.h_bunch.alloc(job.bunch.bytes, "pinned PMT series bunch");
+                s.h_bunch_bytes = job.bunch.bytes;
+            }
+            std::memcpy(s.h_bunch.get(), job.bunch_blob.data(), job.bunch.bytes);
+            blob = s.h_bunch.get();
+        }
+        const size_t need = pmt_series_workspace_bytes(max_output_photons_, job.bunch.n_particles, job.bunch.n_masked) + 64;
+        if (s.pmt_series_workspace_bytes < need) {      // (the slot is free: nothing on the device uses its workspace)
+            s.d_pmt_series_workspace.reset();
+            s.d_pmt_series_workspace.alloc(need + need / 4, "PMT series workspace");
+            s.pmt_series_workspace_bytes = need + need / 4;
+        }
+        pmt_->series_device_prepared(device_, s.d_pmt_hits.get(), s.d_pmt_counters.get(), max_output_photons_, job.bunch, blob, s.d_pmt_sorted.get(),
+                                     s.d_pmt_series.get(), s.d_pmt_series_counts.get(), s.d_pmt_series_workspace.get(), s.pmt_series_workspace_bytes, stream);
+        hip_check(hipMemcpyAsync(s.h_pmt_series_counts.get(), s.d_pmt_series_counts.get(), 20, hipMemcpyDeviceToHost, stream), "download PMT series counts");
+    }
     hip_check(hipEventRecord(s.counted.get(), stream), "event");
 }
 
@@ -778,6 +813,16 @@ void Converter::finish(Slot &s, std::chrono::steady_clock::time_point &last_done
         if (pc[3] != 0u)                                    // log_warn in the reference (:140-145)
             std::fprintf(stderr, "clsimhip: PMT hit generator, bunch %u: %u photons are not within 3 cm of their module's sphere\n", s.id, pc[3]);
         n_pmt_hits = std::min(pc[0], max_output_photons_);
+    }
+    uint32_t n_pmt_series = 0;
+    if (pmt_series_) {
+        const uint32_t *sc = s.h_pmt_series_counts.get();   // kept, series, UNKNOWN_PARTICLE, MASKED, UNKNOWN_CHANNEL
+        if ((sc[2] | sc[4]) != 0u)                          // log_fatal in the reference (I3CLSimClientModule.cxx:388-390)
+            throw Error(CLSIMHIP_ERR_DEVICE, "PMT series, bunch " + std::to_string(s.id) + ": " + std::to_string(sc[2]) +
+                                                 " hits of particles the bunch's particle table does not have, " + std::to_string(sc[4]) +
+                                                 " at modules or PMTs the generator does not have");
+        n_pmt_hits = std::min(sc[0], max_output_photons_);
+        n_pmt_series = std::min(sc[1], n_pmt_hits);
     }
     const uint32_t detected = hits;
     if (!carries_photons()) hits = 0;                   // the records stay on the device
@@ -848,10 +893,20 @@ void Converter::finish(Slot &s, std::chrono::steady_clock::time_point &last_done
             r.pmt_pinned = pmt_pool_.take(n_pmt_hits, result_capacity(n_pmt_hits, s.result_min_records), device_);
             clsimhip_pmt_hit *to = r.pmt_pinned.get();
             if (!to) { r.pmt_hits.reset(new std::vector<clsimhip_pmt_hit>(n_pmt_hits)); to = r.pmt_hits->data(); }
-            hip_check(hipMemcpyAsync(to, s.d_pmt_hits.get(), static_cast<size_t>(n_pmt_hits) * sizeof(clsimhip_pmt_hit), hipMemcpyDeviceToHost, copy_stream),
+            const clsimhip_pmt_hit *from = pmt_series_ ? s.d_pmt_sorted.get() : s.d_pmt_hits.get();
+            hip_check(hipMemcpyAsync(to, from, static_cast<size_t>(n_pmt_hits) * sizeof(clsimhip_pmt_hit), hipMemcpyDeviceToHost, copy_stream),
                       "download PMT hits");
+            if (n_pmt_series) {
+                r.pmt_series_pinned = pmt_series_pool_.take(n_pmt_series, result_capacity(n_pmt_series, s.result_min_records), device_);
+                clsimhip_pmt_series *table = r.pmt_series_pinned.get();
+                if (!table) { r.pmt_series.reset(new std::vector<clsimhip_pmt_series>(n_pmt_series)); table = r.pmt_series->data(); }
+                hip_check(hipMemcpyAsync(table, s.d_pmt_series.get(), static_cast<size_t>(n_pmt_series) * sizeof(clsimhip_pmt_series), hipMemcpyDeviceToHost,
+                                         copy_stream), "download PMT series table");
+            }
             hip_check(hipStreamSynchronize(copy_stream), "download PMT hits");
         }
+        r.pmt_series_count = n_pmt_series;
+        if (pmt_series_) r.masked = s.h_pmt_series_counts.get()[3];
         if (!hits && !r.handle) r.handle.reset(new clsimhip_photon());
     }
     std::unique_ptr<std::vector<float>> histories;
@@ -1008,6 +1063,24 @@ void Converter::result_pmt_hits(const clsimhip_photon *photons, const clsimhip_p
     if (it == handed_out_.end()) throw Error(CLSIMHIP_ERR_ARGUMENT, "not a result handed out by GetConversionResult (or already released)");
     *n = it->second.pmt_count;
     if (it->second.pmt_count) *hits = it->second.pmt_data();
+}
+
+void Converter::result_pmt_series(const clsimhip_photon *photons, const clsimhip_pmt_hit **hits, size_t *n, const clsimhip_pmt_series **series, size_t *n_series,
+                                  uint64_t *n_masked)
+{
+    need_init();
+    if (!hits || !n || !series || !n_series) throw Error(CLSIMHIP_ERR_ARGUMENT, "output pointers are (null)");
+    if (!pmt_series_) throw Error(CLSIMHIP_ERR_STATE, "the PMT series stage is off (clsimhip_set_pmt_series)");
+    *hits = nullptr; *series = nullptr;
+    *n = 0; *n_series = 0;
+    std::lock_guard<std::mutex> lk(results_mutex_);
+    auto it = handed_out_.find(photons);
+    if (it == handed_out_.end()) throw Error(CLSIMHIP_ERR_ARGUMENT, "not a result handed out by GetConversionResult (or already released)");
+    *n = it->second.pmt_count;
+    *n_series = it->second.pmt_series_count;
+    if (it->second.pmt_count) *hits = it->second.pmt_data();
+    if (it->second.pmt_series_count) *series = it->second.pmt_series_data();
+    if (n_masked) *n_masked = it->second.masked;
 }
 
 void Converter::result_mcpe_series(const clsimhip_photon *photons, const clsimhip_mcpe **mcpes, size_t *n, const clsimhip_mcpe_series **series, size_t *n_series,

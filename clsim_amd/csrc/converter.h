@@ -289,6 +289,8 @@ public:
     void set_mcpe_merging(bool on, double window);
     // clsimhip_set_pmt_generator: the multi-PMT hit maker runs behind every bunch's propagation (null: off)
     void set_pmt_generator(std::shared_ptr<PmtHitGenerator> g, bool keep_photons);
+    // clsimhip_set_pmt_series: the sorting stage behind the PMT hit maker (pmt_series.h); needs a PMT hit generator (Compile() checks)
+    void set_pmt_series(bool on) { guard(); compiled_ = false; pmt_series_ = on; }
 
     void compile();
     void initialize(uint64_t seed);
@@ -310,6 +312,8 @@ public:
     void result_mcpe_merged(const clsimhip_photon *photons, const clsimhip_mcpe_merged **merged, size_t *n_merged, const clsimhip_mcpe_series **series,
                             size_t *n_series, const clsimhip_mcpe_parent **parents, size_t *n_parents, const clsimhip_mcpe_parent_range **ranges);
     void result_pmt_hits(const clsimhip_photon *photons, const clsimhip_pmt_hit **hits, size_t *n);
+    void result_pmt_series(const clsimhip_photon *photons, const clsimhip_pmt_hit **hits, size_t *n, const clsimhip_pmt_series **series, size_t *n_series,
+                           uint64_t *n_masked);
     void release_result(const clsimhip_photon *photons);
     size_t queue_size() const;
     bool more_photons_available() const;
@@ -350,12 +354,14 @@ private:
     using McpePool = PinnedPool<clsimhip_mcpe>;
     using SeriesPool = PinnedPool<clsimhip_mcpe_series>;
     using PmtHitPool = PinnedPool<clsimhip_pmt_hit>;
+    using PmtSeriesPool = PinnedPool<clsimhip_pmt_series>;
     using BlobPool = PinnedPool<uint8_t>;
     // A bunch on its way to the worker: the caller's steps are copied ONCE, in the caller's thread, into a page-locked buffer of the
     // step pool, which the worker uploads from (round 5; before, a vector here and a second copy into the slot's staging buffer on
     // the worker thread -- 8 ms per million steps in front of the first kernel of a run).  With every pool buffer in flight the
     // steps travel in a vector as before.
-    // With the MCPE series stage the bunch's particle table and mask travel the same way, in the form the stage reads (mcpe_series.h).
+    // With the MCPE series stage the bunch's particle table and mask travel the same way, in the form the stage reads (mcpe_series.h);
+    // with the PMT series stage likewise (pmt_series.h: the two stages never run in one converter).
     struct Job {
         uint32_t id = 0; size_t n = 0; uint64_t generated = 0; StepPool::Lease pinned; std::vector<clsimhip_step> steps;
         SeriesBunch bunch; BlobPool::Lease bunch_pinned; std::vector<SeriesParticle16> bunch_blob;
@@ -394,6 +400,11 @@ private:
         size_t pmt_count = 0;
         std::unique_ptr<std::vector<clsimhip_pmt_hit>> pmt_hits;
         const clsimhip_pmt_hit *pmt_data() const { return pmt_pinned ? pmt_pinned.get() : (pmt_hits ? pmt_hits->data() : nullptr); }
+        // with the PMT series stage: the series table of the (then sorted) hits; the MASKED count is `masked`
+        PmtSeriesPool::Lease pmt_series_pinned;
+        size_t pmt_series_count = 0;
+        std::unique_ptr<std::vector<clsimhip_pmt_series>> pmt_series;
+        const clsimhip_pmt_series *pmt_series_data() const { return pmt_series_pinned ? pmt_series_pinned.get() : (pmt_series ? pmt_series->data() : nullptr); }
     };
 
     void guard() const { if (initialized_) throw Error(CLSIMHIP_ERR_STATE, "I3CLSimStepToPhotonConverterHIP already initialized!"); }
@@ -426,6 +437,7 @@ private:
     double merge_window_ = 0.;
     std::shared_ptr<PmtHitGenerator> pmt_;      // null: no PMT hits are made (the default)
     bool pmt_keep_photons_ = true;
+    bool pmt_series_ = false;                   // the PMT series stage runs behind the PMT hit maker
     bool carries_photons() const { return !(mcpe_ && !keep_photons_) && !(pmt_ && !pmt_keep_photons_); }
 
     std::atomic<bool> compiled_{false}, initialized_{false};    // (atomic: set_tuning() reads them from any thread)
@@ -442,6 +454,7 @@ private:
     SeriesPool series_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
     BlobPool merge_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
     PmtHitPool pmt_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
+    PmtSeriesPool pmt_series_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
     // particle tables and masks of the bunches on their way (input queue depth + one per slot + the one being filled)
     BlobPool bunch_pool_{PinnedPoolPolicy{8, size_t{1} << 28, nullptr}};
     size_t result_capacity(size_t records, size_t min_records) const;
@@ -469,6 +482,13 @@ private:
         DeviceBuffer<clsimhip_pmt_hit> d_pmt_hits;  // with a PMT hit generator: max_output_photons_ records, four counters (pmt_hits.h)
         DeviceBuffer<uint32_t> d_pmt_counters;
         PinnedBuffer<uint32_t> h_pmt_counters;
+        // with the PMT series stage: its workspace (grown when a bunch's table needs it), sorted hits, series table, five counts
+        DeviceBuffer<uint8_t> d_pmt_series_workspace;
+        size_t pmt_series_workspace_bytes = 0;
+        DeviceBuffer<clsimhip_pmt_hit> d_pmt_sorted;
+        DeviceBuffer<clsimhip_pmt_series> d_pmt_series;
+        DeviceBuffer<uint32_t> d_pmt_series_counts;
+        PinnedBuffer<uint32_t> h_pmt_series_counts;
         // with the MCPE series stage: its workspace (grown when a bunch's table needs it), sorted records, series table, five counts
         DeviceBuffer<uint8_t> d_series_workspace;
         size_t series_workspace_bytes = 0;

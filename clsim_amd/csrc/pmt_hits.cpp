@@ -1,6 +1,7 @@
 // The multi-PMT hit generator object: see pmt_hits.h.  Configuration and the host twin here, the kernel in pmt_hits_kernel.hip.
 #include "pmt_hits.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 
@@ -139,6 +140,7 @@ PmtHitGenerator::PmtHitGenerator(const std::vector<FunctionData> &functions, con
     P.pmts = pmts_.data();
     P.module_table = module_table_.data();
     P.modules = modules_.data();
+    build_series_tables();
 }
 
 PmtHitGenerator::~PmtHitGenerator()
@@ -150,6 +152,29 @@ PmtHitGenerator::~PmtHitGenerator()
         DeviceBuffer<PmtEntry> pmts(kv.second.pmts);
         DeviceBuffer<uint64_t> module_table(kv.second.module_table);
         DeviceBuffer<PmtModule> modules(kv.second.modules);
+    }
+}
+
+void PmtHitGenerator::build_series_tables()
+{
+    // PMT series (pmt_series.h): every module's rank in ascending (string ID signed, OM ID) order -- OMKey::operator< -- and its
+    // channels, in arrays of their own beside the table (the table's entries, and what pmt_make reads in them, stay what they are)
+    for (uint64_t e : module_table_)
+        if (e != 0u) module_of_rank_.push_back(static_cast<uint32_t>(e));
+    std::sort(module_of_rank_.begin(), module_of_rank_.end(), [](uint32_t a, uint32_t b) {
+        const int16_t sa = static_cast<int16_t>(a & 0xffffu), sb = static_cast<int16_t>(b & 0xffffu);
+        return sa != sb ? sa < sb : (a >> 16) < (b >> 16);
+    });
+    module_ranks_.assign(module_table_.size(), 0u);
+    channel_bases_.assign(module_table_.size(), 0u);
+    base_.assign(module_of_rank_.size() + 1u, 0u);
+    for (size_t r = 0; r < module_of_rank_.size(); ++r) {                // (at most 2^24 modules of at most 64 PMTs: 32 bits hold the sum)
+        uint32_t slot = mcpe_dom_slot(module_of_rank_[r], params_.module_mask);
+        while (static_cast<uint32_t>(module_table_[slot]) != module_of_rank_[r] || module_table_[slot] == 0u) slot = (slot + 1u) & params_.module_mask;
+        const size_t index = static_cast<size_t>(module_table_[slot] >> 32) - 1u;
+        module_ranks_[slot] = static_cast<uint32_t>(r);
+        channel_bases_[slot] = base_[r];
+        base_[r + 1u] = base_[r] + static_cast<uint32_t>(params_.types[modules_[index].type].count);
     }
 }
 

@@ -158,6 +158,27 @@ public:
     // the sphere radii of the types modules use (Compile() compares them with the radius the converter records photons at)
     const std::vector<double> &used_sphere_radii() const { return used_radii_; }
 
+    // ---- PMT series (pmt_series.h; pmt_series.cpp) ----
+    size_t num_modules() const { return module_of_rank_.size(); }
+    size_t num_channels() const { return base_.back(); }                // PMTs of all modules together
+    // One bunch's particle table and mask, checked and brought into the form the stage reads (pmt_series_blob_bytes(n_particles,
+    // n_masked) bytes at `blob`, 16-byte aligned): CLSIMHIP_ERR_ARGUMENT for a table that is not strictly increasing in
+    // `identifier`, CLSIMHIP_ERR_CONFIG for frames x channels >= 2^32.  particles = nullptr: no table.
+    SeriesBunch prepare_series(const clsimhip_mcpe_particle *particles, size_t n_particles, const clsimhip_mcpe_mask *masked, size_t n_masked,
+                               uint8_t *blob) const;
+    // host twin: out and series hold n entries each; counters[3] += UNKNOWN_PARTICLE, MASKED, UNKNOWN_CHANNEL
+    void series_host(const clsimhip_pmt_hit *in, size_t n, const clsimhip_mcpe_particle *particles, size_t n_particles, const clsimhip_mcpe_mask *masked,
+                     size_t n_masked, clsimhip_pmt_hit *out, clsimhip_pmt_series *series, size_t *n_kept, size_t *n_series, uint64_t counters[3]) const;
+    // the kernels on `stream` of `device`, over min(*d_count, capacity) records; d_counts: five uint32 (kept, series, the counters)
+    void series_device(int device, const void *d_hits, const void *d_count, size_t capacity, const clsimhip_mcpe_particle *particles,
+                       size_t n_particles, const clsimhip_mcpe_mask *masked, size_t n_masked, void *d_out, void *d_series, void *d_counts,
+                       void *d_workspace, size_t workspace_bytes, hipStream_t stream);
+    // the same for a bunch prepared into page-locked memory that stays as it is until the stream has passed the copy this call
+    // begins with; `uploaded` (may be null) is recorded behind that copy
+    void series_device_prepared(int device, const void *d_hits, const void *d_count, size_t capacity, const SeriesBunch &bunch, const uint8_t *h_blob,
+                                void *d_out, void *d_series, void *d_counts, void *d_workspace, size_t workspace_bytes, hipStream_t stream,
+                                hipEvent_t uploaded = nullptr);
+
 private:
     PmtHitParams params_{};
     std::vector<double> values_;
@@ -169,6 +190,22 @@ private:
     std::mutex device_mutex_;
     std::map<int, DeviceImage> images_;
     DeviceImage image_on(int device);
+    // PMT series: beside module_table_ slot by slot the module's rank in ascending (string ID, OM ID) order and its first channel;
+    // by rank the first channel (one entry more: the number of channels) and the record word (string ID | OM ID << 16)
+    std::vector<uint32_t> module_ranks_, channel_bases_, base_, module_of_rank_;
+    void build_series_tables();
+    // what the stage keeps on the devices it has run on: these tables, and the page-locked staging of the stand-alone call's bunch
+    // (pmt_series.cpp; made by the first device call, so that the generator and its host twin need nothing of the HIP runtime)
+    struct SeriesImage { uint32_t *module_ranks = nullptr, *channel_bases = nullptr, *base = nullptr, *module_of_rank = nullptr; };
+    struct SeriesState;
+    std::mutex series_mutex_;
+    std::shared_ptr<SeriesState> series_state_;
+    SeriesState &series_state();
+    SeriesImage series_image_on(int device);
 };
+
+// pmt_series.cpp: the sizes that go with a bunch's particle table and mask (a SeriesBunch of host_model.h, as for the MCPE series)
+size_t pmt_series_blob_bytes(size_t n_particles, size_t n_masked);
+size_t pmt_series_workspace_bytes(size_t capacity, size_t n_particles, size_t n_masked);
 
 } // namespace clsimhip

@@ -240,10 +240,17 @@ public:
             if (!n) check(clsimhip_release_result(handle_, p));     // the handle of a result without photon records
         }
         lastPMTHits_.clear();
+        lastPMTSeries_.clear();
         if (pmtHitGenerator_) {     // (likewise: GetLastPMTHits())
             const clsimhip_pmt_hit *h = nullptr;
             size_t nh = 0;
-            check(clsimhip_get_result_pmt_hits(handle_, p, &h, &nh));
+            if (pmtSeries_) {
+                const clsimhip_pmt_series *s = nullptr;
+                size_t ns = 0;
+                check(clsimhip_get_result_pmt_series(handle_, p, &h, &nh, &s, &ns, &lastMasked_));
+                lastPMTSeries_.assign(s, s + ns);
+            } else
+                check(clsimhip_get_result_pmt_hits(handle_, p, &h, &nh));
             lastPMTHits_.assign(h, h + nh);
             if (!n) check(clsimhip_release_result(handle_, p));
         }
@@ -373,8 +380,32 @@ public:
         check(clsimhip_set_pmt_generator(handle_, generator, keepPhotons ? 1 : 0));
         pmtHitGenerator_ = generator != nullptr;
     }
-    // the hits of the bunch the last GetConversionResult() returned, in no particular order
+    // the hits of the bunch the last GetConversionResult() returned, in no particular order -- with SetPMTSeries(true) in the order
+    // of the series
     const std::vector<clsimhip_pmt_hit> &GetLastPMTHits() const { return lastPMTHits_; }
+
+    // ---- PMT series (include/clsimhip.h, "PMT series"): what replaces the client module's AddPhotonsToFrames loop and the filing
+    // and per-PMT time sort of I3PhotonToMCHitConverterForMultiPMT::DAQ.  Before Initialize(); needs a PMT hit generator.  A bunch is
+    // enqueued with its particle table and its frames' ignored modules (EnqueueSteps below); its result's hits come back per frame,
+    // per module in OMKey order, per PMT, in time order. ----
+    void SetPMTSeries(bool on = true)
+    {
+        check(clsimhip_set_pmt_series(handle_, on ? 1 : 0));
+        pmtSeries_ = on;
+    }
+    // the flat views of the last result: GetLastPMTHits() and its series table (entries partition the records), the MASKED count
+    const std::vector<clsimhip_pmt_series> &GetLastPMTSeries() const { return lastPMTSeries_; }
+    uint64_t GetLastMaskedPMTHits() const { return lastMasked_; }
+    // ... and as the frames receive them: frame -> (string ID, OM ID) -> PMT -> time-ordered hits (an I3MCHitSeriesMultiOMMap per frame)
+    typedef std::map<std::pair<int, unsigned>, std::map<uint32_t, std::vector<clsimhip_pmt_hit> > > PMTHitSeriesMap;
+    std::map<uint32_t, PMTHitSeriesMap> GetLastPMTSeriesMaps() const
+    {
+        std::map<uint32_t, PMTHitSeriesMap> frames;
+        for (const clsimhip_pmt_series &s : lastPMTSeries_)
+            frames[s.frame][std::make_pair(static_cast<int>(s.string_id), static_cast<unsigned>(s.om_id))][s.pmt]
+                .assign(lastPMTHits_.begin() + s.first, lastPMTHits_.begin() + s.first + s.count);
+        return frames;
+    }
 
     // ---- MCPE series (include/clsimhip.h, "MCPE series"): what replaces the client module's AddPhotonsToFrames loop and the per-DOM
     // time sort.  Before Initialize(); needs a generator.  A bunch is enqueued with its particle table (strictly increasing in
@@ -472,6 +503,8 @@ private:
     std::vector<clsimhip_mcpe_parent_range> lastParentRanges_;
     bool pmtHitGenerator_ = false;
     std::vector<clsimhip_pmt_hit> lastPMTHits_;
+    bool pmtSeries_ = false;
+    std::vector<clsimhip_pmt_series> lastPMTSeries_;
 #ifdef CLSIMHIP_WITH_ICETRAY
     I3RandomServicePtr randomService_;
 #endif

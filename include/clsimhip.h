@@ -884,8 +884,8 @@ int clsimhip_mcpe_series_device(clsimhip_mcpe_generator *g, int device, const vo
  * as a bunch with one of the MCPE generator's four conditions does, with the count in the text. */
 int clsimhip_set_mcpe_series(clsimhip_converter *c, int on);
 /* clsimhip_enqueue_steps with the bunch's particle table and mask, which are checked and copied in the caller's thread
- * (CLSIMHIP_ERR_ARGUMENT / CLSIMHIP_ERR_CONFIG as above; CLSIMHIP_ERR_STATE without clsimhip_set_mcpe_series).  A bunch enqueued
- * with clsimhip_enqueue_steps has no table: one frame, 0. */
+ * (CLSIMHIP_ERR_ARGUMENT / CLSIMHIP_ERR_CONFIG as above; CLSIMHIP_ERR_STATE with neither clsimhip_set_mcpe_series nor
+ * clsimhip_set_pmt_series).  A bunch enqueued with clsimhip_enqueue_steps has no table: one frame, 0. */
 int clsimhip_enqueue_steps_with_particles(clsimhip_converter *c, const clsimhip_step *steps, size_t n, uint32_t identifier,
                                           const clsimhip_mcpe_particle *particles, size_t n_particles, const clsimhip_mcpe_mask *masked,
                                           size_t n_masked);
@@ -1047,7 +1047,7 @@ int clsimhip_pmt_convert_device(clsimhip_pmt_generator *g, int device, const voi
 /* Attach the generator to a converter: the kernel then runs on every bunch's stream behind the propagation kernels, over the
  * records the bunch stored.  Before Initialize() only (CLSIMHIP_ERR_STATE after); g = NULL switches it off (the default: no launch
  * and no byte changes anywhere).  keep_photons as for clsimhip_set_mcpe_generator.  Compile() then refuses (CLSIMHIP_ERR_CONFIG):
- * an MCPE generator beside it; clsimhip_set_mcpe_series (series per PMT are not made); a geometry DOM without a module or whose
+ * an MCPE generator beside it; clsimhip_set_mcpe_series (the series of PMT hits are clsimhip_set_pmt_series'); a geometry DOM without a module or whose
  * IDs do not fit the record; a type in use whose sphere radius differs by more than 3 cm from the radius the converter records
  * photons at (the geometry's OM radius / the pancake factor); photon histories together with keep_photons = 0.
  * A bunch with UNKNOWN_MODULE or PROBABILITY_ABOVE_ONE > 0 fails as a bunch with one of the MCPE generator's conditions does, with
@@ -1055,6 +1055,75 @@ int clsimhip_pmt_convert_device(clsimhip_pmt_generator *g, int device, const voi
 int clsimhip_set_pmt_generator(clsimhip_converter *c, clsimhip_pmt_generator *g, int keep_photons);
 /* Hits of the result `photons` belongs to; valid until clsimhip_release_result(c, photons).  *hits is NULL when there are none. */
 int clsimhip_get_result_pmt_hits(clsimhip_converter *c, const clsimhip_photon *photons, const clsimhip_pmt_hit **hits, size_t *n);
+
+/* ---- PMT series: a bunch's PMT hits as per-frame, per-module, per-PMT time-sorted series ---------------------------------
+ * What the reference does with every hit of a multi-PMT module on host threads: the client module files the photons under their
+ * frames with the particles' time shifts and the frames' ignoreModules (private/clsim/I3CLSimClientModule.cxx:359-439), and
+ * I3PhotonToMCHitConverterForMultiPMT::DAQ files every hit under its OMKey and then under its PMT number (I3MCHitSeriesMultiOMMap, a
+ * map of maps) and time-sorts every PMT's vector (private/clsim/dom/I3PhotonToMCHitConverterForMultiPMT.cxx:291-292, 365, 387-395)
+ * -- as a sorting stage behind the PMT hit kernel, the MCPE series' radix passes on a key of its own.
+ * With the generator's modules ranked in ascending (string_id signed, om_id) order, base = the exclusive prefix sum of the modules'
+ * PMT counts (the n_pmts of each module's type) in that order and n_channels its total, a hit's channel is base[module rank] + pmt.
+ * Per record, in this order:
+ *     its module is not one of the generator's, or pmt >= n_pmts of the module's type -> UNKNOWN_CHANNEL, no record (the
+ *     generator's own hits never meet this);
+ *     its identifier is not in the particle table -> UNKNOWN_PARTICLE, no record (log_fatal in the reference, :388-390); without a
+ *     table the frame is 0 and the shift +0.0;
+ *     (frame, string_id, om_id) is in the mask -> MASKED, no record (:399; not an error).  The mask is per module, as ignoreModules
+ *     is: it masks all of the module's PMTs;
+ *     time' = time + time_shift, one binary64 addition.
+ * The kept records come out with reserved = 0, ascending in the 128-bit integer key (group = frame rank x n_channels + channel,
+ * tkey(time'), identifier): frames in ascending frame ID, then modules, then PMTs, then the MCPE series' total order on the time's
+ * bit pattern, then the identifier.  Records with equal keys are byte-identical, so the output is a function of the input as a
+ * multiset: the same bytes from run to run and the same bytes from the kernels and the host twin.  The series table has one entry
+ * per non-empty (frame, module, PMT) in the same order; its entries partition the records.
+ * What differs from the reference, on purpose: its std::sort with < on doubles leaves the order of equal times and of NaNs
+ * unspecified -- here the order is total on bit patterns, with the identifier as tie-break; it adds the shift to the photon's
+ * binary32 time before the conversion -- here it is added once, to the hit's widened time, in binary64.  Not pinned against the
+ * reference's output, like the rest of the multi-PMT hit maker (I3OMTypeInfo and I3Orientation are outside it).
+ * The particle table and the mask are the MCPE series' (clsimhip_mcpe_particle, clsimhip_mcpe_mask), with the same checks. */
+typedef struct {
+    uint32_t frame;
+    int16_t string_id;
+    uint16_t om_id;
+    uint32_t pmt;
+    uint32_t first, count;              /* records [first, first + count) */
+    uint32_t reserved;                  /* 0 */
+} clsimhip_pmt_series;                  /* 24 bytes */
+typedef char clsimhip_pmt_series_is_24_bytes[sizeof(clsimhip_pmt_series) == 24 ? 1 : -1];
+#define CLSIMHIP_PMT_SERIES_UNKNOWN_PARTICLE 0  /* index into the series counters */
+#define CLSIMHIP_PMT_SERIES_MASKED 1
+#define CLSIMHIP_PMT_SERIES_UNKNOWN_CHANNEL 2
+/* The host twin: the definition with std::sort on the key, for callers without a GPU and for the tests.  `g` supplies the modules
+ * and their types.  particles = NULL, n_particles = 0: no table.  out and series hold n entries each; counters[3] (may be NULL)
+ * receives the three counts.  CLSIMHIP_ERR_ARGUMENT for a table that is not strictly increasing in `identifier`,
+ * CLSIMHIP_ERR_CONFIG when frames x n_channels >= 2^32. */
+int clsimhip_pmt_series_host(const clsimhip_pmt_generator *g, const clsimhip_pmt_hit *hits, size_t n, const clsimhip_mcpe_particle *particles,
+                             size_t n_particles, const clsimhip_mcpe_mask *masked, size_t n_masked, clsimhip_pmt_hit *out,
+                             clsimhip_pmt_series *series, size_t *n_kept, size_t *n_series, uint64_t counters[3]);
+/* bytes of device memory the kernels need beside their input and output, for up to `capacity` records and a bunch with this table
+ * and mask */
+size_t clsimhip_pmt_series_workspace_bytes(size_t capacity, size_t n_particles, size_t n_masked);
+/* The kernels, on hits that live in HBM (pairs with clsimhip_pmt_convert_device: d_hits and d_count = its d_counters, whose first
+ * word counts past the capacity): min(*d_count, capacity) records of d_hits.  d_out and d_series: `capacity` entries each, 8-byte
+ * aligned; d_workspace: clsimhip_pmt_series_workspace_bytes(capacity, n_particles, n_masked) bytes, 16-byte aligned; d_counts: five
+ * uint32 -- records kept, series, then the three counters (CLSIMHIP_ERR_ARGUMENT for a misaligned pointer or a workspace that is
+ * too small; nothing is launched then).  The particle table and the mask are host memory: they are checked and copied before the
+ * call returns (which may wait for the previous call's copy, nothing else); the kernels are asynchronous on hip_stream (NULL =
+ * default stream) and nothing else waits for the device. */
+int clsimhip_pmt_series_device(clsimhip_pmt_generator *g, int device, const void *d_hits, const void *d_count, size_t capacity,
+                               const clsimhip_mcpe_particle *particles, size_t n_particles, const clsimhip_mcpe_mask *masked, size_t n_masked,
+                               void *d_out, void *d_series, void *d_counts, void *d_workspace, size_t workspace_bytes, void *hip_stream);
+/* The stage behind every bunch's PMT hit kernel, on the bunch's stream.  Before Initialize() only (CLSIMHIP_ERR_STATE after);
+ * Compile() refuses it without a PMT hit generator (CLSIMHIP_ERR_CONFIG, "need a PMT hit generator").  on = 0 (the default): no
+ * launch and no byte changes anywhere.  With it on, clsimhip_enqueue_steps_with_particles takes the bunch's table and mask,
+ * clsimhip_get_result_pmt_hits returns the sorted records, and a bunch with UNKNOWN_PARTICLE or UNKNOWN_CHANNEL > 0 fails as a bunch
+ * with one of the generator's conditions does (CLSIMHIP_ERR_DEVICE, the counts in the text). */
+int clsimhip_set_pmt_series(clsimhip_converter *c, int on);
+/* Sorted hits and series table of the result `photons` belongs to, valid until clsimhip_release_result(c, photons); n_masked (may
+ * be NULL) receives the MASKED count.  Pointers are NULL where there is nothing.  CLSIMHIP_ERR_STATE without clsimhip_set_pmt_series. */
+int clsimhip_get_result_pmt_series(clsimhip_converter *c, const clsimhip_photon *photons, const clsimhip_pmt_hit **hits, size_t *n,
+                                   const clsimhip_pmt_series **series, size_t *n_series, uint64_t *n_masked);
 
 #ifdef __cplusplus
 }

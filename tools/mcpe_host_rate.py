@@ -14,6 +14,10 @@ particles as a long chain of groups (window 5 ns) and as one group, and on 300 0
 
 --pmt: the multi-PMT hit generator's host twin instead (clsimhip_pmt_convert_host) on the same records, against the 31-PMT layout
 of tests/pmt_common.py, in photon records per second.
+
+--pmt-series N: the PMT series' host twin instead (clsimhip_pmt_series_host), in hits per second, on N synthetic hits at 5160
+modules of 31 PMTs dealt to 1000 particles in 10 frames; --device adds the device stage's time for the same input (HIP events
+around clsimhip_pmt_series_device, best of --repeats; needs a GPU).
 """
 import argparse
 import ctypes as C
@@ -74,6 +78,54 @@ def series_rate(args):
     print(json.dumps(line))
 
 
+def pmt_series_rate(args):
+    from tests import pmt_common as PC
+    n = args.pmt_series
+    rng = np.random.default_rng(1)
+    s, d = np.meshgrid(np.arange(1, 87), np.arange(1, 61), indexing="ij")
+    s, d = s.reshape(-1).astype(np.int32), d.reshape(-1).astype(np.uint32)
+    types, pmts = PC.layout(PC.sphere_radius_of("mie"))
+    modules = np.zeros(len(s), dtype=CV.PMT_MODULE_DTYPE)
+    modules["stringID"], modules["omID"], modules["rotation"] = s, d, np.eye(3).reshape(9)
+    gen = PC.make_generator(PC.standard_functions(), types, pmts, modules)
+    h = np.zeros(n, dtype=CV.PMT_HIT_DTYPE)
+    at = rng.integers(0, len(s), n)
+    h["stringID"], h["omID"], h["pmt"], h["id"], h["time"] = s[at], d[at], rng.integers(0, 31, n), rng.integers(0, 1000, n), rng.uniform(0.0, 1.0e4, n)
+    p = np.zeros(1000, dtype=CV.MCPE_PARTICLE_DTYPE)
+    p["id"], p["frame"], p["timeShift"] = np.arange(1000), np.arange(1000) % 10, rng.uniform(0.0, 1.0e6, 1000)
+    masked = np.zeros(20, dtype=CV.MCPE_MASK_DTYPE)
+    masked["frame"], masked["stringID"], masked["omID"] = np.arange(20) % 10, 40, 30
+    best = float("inf")
+    for _ in range(args.repeats):
+        t0 = time.perf_counter()
+        records, series, counters = gen.MakeSeriesHost(h, p, masked)
+        best = min(best, time.perf_counter() - t0)
+    line = {"pmt_hits": n, "kept": len(records), "series": len(series), "host_seconds": best, "host_hits_per_s": n / best, "threads": 1}
+    if args.device:
+        import torch
+        dev = torch.device("cuda", 0)
+        d_in = torch.from_numpy(h.view(np.uint8).reshape(-1, 24).copy()).to(dev)
+        d_cnt = torch.tensor([n], dtype=torch.int32, device=dev)
+        d_out, d_series = torch.zeros((n, 24), dtype=torch.uint8, device=dev), torch.zeros((n, 24), dtype=torch.uint8, device=dev)
+        d_counts = torch.zeros(5, dtype=torch.int32, device=dev)
+        ws = CV.PMTHitGenerator.SeriesWorkspaceBytes(n, len(p), len(masked))
+        d_ws = torch.zeros(ws, dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream().cuda_stream
+        times = []
+        for _ in range(args.repeats + 1):
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            gen.MakeSeriesDevice(d_in.data_ptr(), d_cnt.data_ptr(), n, d_out.data_ptr(), d_series.data_ptr(), d_counts.data_ptr(), d_ws.data_ptr(), ws,
+                                 p, masked, stream=stream)
+            stop.record()
+            torch.cuda.synchronize()
+            times.append(start.elapsed_time(stop) * 1e-3)
+        got = d_out.cpu().numpy()[:len(records)].copy().view(CV.PMT_HIT_DTYPE).reshape(-1)
+        assert int(d_counts[0]) == len(records) and got.tobytes() == records.tobytes()
+        line.update(device_seconds=min(times[1:]), device_hits_per_s=n / min(times[1:]))
+    print(json.dumps(line))
+
+
 def merge_rate(args):
     from tests import mcpe_merge_common as MM
     from tests import mcpe_series_common as S
@@ -125,7 +177,10 @@ def main():
     ap.add_argument("--device", action="store_true")
     ap.add_argument("--pmt", action="store_true")
     ap.add_argument("--merge", action="store_true")
+    ap.add_argument("--pmt-series", type=int, default=0, metavar="N")
     args = ap.parse_args()
+    if args.pmt_series:
+        return pmt_series_rate(args)
     if args.merge:
         return merge_rate(args)
     if args.series:
