@@ -135,6 +135,9 @@ SYMBOLS = [
     "clsimhip_pmt_convert_host", "clsimhip_pmt_convert_device", "clsimhip_set_pmt_generator", "clsimhip_get_result_pmt_hits",
     "clsimhip_pmt_series_host", "clsimhip_pmt_series_workspace_bytes", "clsimhip_pmt_series_device", "clsimhip_set_pmt_series",
     "clsimhip_get_result_pmt_series",
+    "clsimhip_frame_photon_doms_create", "clsimhip_frame_photon_doms_destroy", "clsimhip_frame_photon_doms_last_error",
+    "clsimhip_frame_photons_host", "clsimhip_frame_photons_workspace_bytes", "clsimhip_frame_photons_device", "clsimhip_set_frame_photons",
+    "clsimhip_get_result_frame_photons",
 ]
 
 # clsimhip_get_last_launch: CLSIMHIP_FAMILY_* and CLSIMHIP_LENGTHS_* by name
@@ -325,6 +328,14 @@ def load():
         "clsimhip_pmt_series_device": (i32, [vp, i32, vp, vp, sz, vp, sz, vp, sz, vp, vp, vp, vp, sz, vp]),
         "clsimhip_set_pmt_series": (i32, [vp, i32]),
         "clsimhip_get_result_pmt_series": (i32, [vp, vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(u64)]),
+        "clsimhip_frame_photon_doms_create": (i32, [sz, vp, vp, C.POINTER(vp)]),
+        "clsimhip_frame_photon_doms_destroy": (None, [vp]),
+        "clsimhip_frame_photon_doms_last_error": (C.c_char_p, [vp]),
+        "clsimhip_frame_photons_host": (i32, [vp, vp, sz, vp, sz, vp, sz, vp, vp, C.POINTER(sz), C.POINTER(sz), vp]),
+        "clsimhip_frame_photons_workspace_bytes": (sz, [sz, sz, sz]),
+        "clsimhip_frame_photons_device": (i32, [vp, i32, vp, vp, sz, vp, sz, vp, sz, vp, vp, vp, vp, sz, vp]),
+        "clsimhip_set_frame_photons": (i32, [vp, i32, i32]),
+        "clsimhip_get_result_frame_photons": (i32, [vp, vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(u64)]),
         "clsimhip_tabulator_write_fits_file": (i32, [vp, C.c_char_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double), sz]),
     }
     for name in SYMBOLS:

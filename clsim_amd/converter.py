@@ -551,6 +551,68 @@ class PMTHitGenerator:
                                                     int(workspace_bytes), C.c_void_p(stream)))
 
 
+# Frame photons (include/clsimhip.h): one record of the result -- an I3CompressedPhoton with the module it is filed under; the
+# series table is MCPE_SERIES_DTYPE, the particle table and the mask are the MCPE series'
+FRAME_PHOTON_DTYPE = np.dtype([("id", "<u4"), ("stringID", "<i2"), ("omID", "<u2"), ("time", "<f8"), ("weight", "<f4"), ("wavelength", "<f4"),
+                               ("groupVelocity", "<f4"), ("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("theta", "<f4"), ("phi", "<f4")])
+FRAME_PHOTON_COUNTERS = ("unknown_particle", "masked", "unknown_dom", "tie_overflow")
+FRAME_PHOTON_TIE_BOUND = 2048
+
+
+class FramePhotonDoms:
+    """The DOM list of the frame photons stage (clsimhip_frame_photon_doms): the modules a detected photon may be filed under, as the
+    client module's PropagatedPhotons map files them (private/clsim/I3CLSimClientModule.cxx:359-439).  stringIDs, omIDs: one pair per
+    DOM (a pair named twice is one DOM)."""
+
+    def __init__(self, stringIDs, omIDs):
+        self._lib = _lib.load()
+        sid = np.ascontiguousarray(stringIDs, dtype=np.int32)
+        oid = np.ascontiguousarray(omIDs, dtype=np.uint32)
+        if sid.ndim != 1 or sid.shape != oid.shape:
+            raise ValueError("stringIDs and omIDs: one entry per DOM each")
+        h = C.c_void_p()
+        _check(self._lib.clsimhip_frame_photon_doms_create(len(sid), sid.ctypes.data_as(C.c_void_p), oid.ctypes.data_as(C.c_void_p), C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                self._lib.clsimhip_frame_photon_doms_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def MakeFramePhotonsHost(self, photons, particles=None, masked=None):
+        """(records, series, counters): the host twin of the frame photons stage.  photons: PHOTON_DTYPE with string and OM IDs;
+        particles: MCPE_PARTICLE_DTYPE, strictly increasing in `id` (None: no table -- one frame, 0, no shift); masked:
+        MCPE_MASK_DTYPE.  records: FRAME_PHOTON_DTYPE, the kept photons with shifted times, ascending in (frame, stringID, omID, time
+        key, id, h, the eight floats' bit patterns); series: MCPE_SERIES_DTYPE, one entry per non-empty (frame, module); counters =
+        {name: count} (FRAME_PHOTON_COUNTERS).  With tie_overflow > 0 there are no records."""
+        photons = np.ascontiguousarray(photons, dtype=PHOTON_DTYPE)
+        keep, pp, n_p, masked, mp, n_m = _series_inputs(particles, masked)
+        out = np.zeros(len(photons), dtype=FRAME_PHOTON_DTYPE)
+        series = np.zeros(len(photons), dtype=MCPE_SERIES_DTYPE)
+        n_kept, n_series, counters = C.c_size_t(), C.c_size_t(), np.zeros(4, dtype=np.uint64)
+        _check(self._lib.clsimhip_frame_photons_host(self._h, photons.ctypes.data_as(C.c_void_p), len(photons), pp, n_p, mp, n_m,
+                                                     out.ctypes.data_as(C.c_void_p), series.ctypes.data_as(C.c_void_p), C.byref(n_kept),
+                                                     C.byref(n_series), counters.ctypes.data_as(C.c_void_p)))
+        return out[:n_kept.value], series[:n_series.value], dict(zip(FRAME_PHOTON_COUNTERS, (int(c) for c in counters)))
+
+    @staticmethod
+    def WorkspaceBytes(capacity, n_particles=0, n_masked=0):
+        return int(_lib.load().clsimhip_frame_photons_workspace_bytes(int(capacity), int(n_particles), int(n_masked)))
+
+    def MakeFramePhotonsDevice(self, d_photons, d_count, capacity, d_out, d_series, d_counts, d_workspace, workspace_bytes, particles=None, masked=None,
+                               device=0, stream=0):
+        """the kernels on device-resident photon records (addresses, 16-byte aligned): min(*d_count, capacity) records; d_out /
+        d_series: `capacity` entries, d_counts: six uint32 (kept, series, then FRAME_PHOTON_COUNTERS), d_workspace:
+        WorkspaceBytes(capacity, len(particles), len(masked)) bytes.  particles / masked are host arrays as for MakeFramePhotonsHost."""
+        keep, pp, n_p, masked, mp, n_m = _series_inputs(particles, masked)
+        _check(self._lib.clsimhip_frame_photons_device(self._h, int(device), C.c_void_p(d_photons), C.c_void_p(d_count), int(capacity), pp, n_p, mp, n_m,
+                                                       C.c_void_p(d_out), C.c_void_p(d_series), C.c_void_p(d_counts), C.c_void_p(d_workspace),
+                                                       int(workspace_bytes), C.c_void_p(stream)))
+
+
 class ConversionResult(tuple):
     """What GetConversionResult / GetConversionResultInPlace return: the tuple (identifier, photons[, histories]) / (identifier,
     photons, release), with the bunch's MCPEs (MCPE_DTYPE) as attribute `mcpes` when the converter has an MCPE generator (None
@@ -558,7 +620,11 @@ class ConversionResult(tuple):
     `masked` the bunch's MASKED count; with the MCPE merging stage `merged` (MCPE_MERGED_DTYPE), `merged_series`, `parents`
     (MCPE_PARENT_DTYPE) and `parent_ranges` (MCPE_PARENT_RANGE_DTYPE) beside them.  With a PMT hit generator `pmt_hits` holds the bunch's hits (PMT_HIT_DTYPE);
     with the PMT series stage they are the sorted records, `pmt_series` their series table (PMT_SERIES_DTYPE) and `masked` the
-    bunch's MASKED count."""
+    bunch's MASKED count.  With the frame photons stage `frame_photons` (FRAME_PHOTON_DTYPE), `frame_photon_series` (MCPE_SERIES_DTYPE)
+    and `frame_photons_masked`."""
+    frame_photons = None
+    frame_photon_series = None
+    frame_photons_masked = None
     mcpes = None
     series = None
     masked = None
@@ -583,6 +649,7 @@ class I3CLSimStepToPhotonConverterHIP:
         self._merging = False
         self._pmt = None
         self._pmt_series = False
+        self._frame_photons = False
 
     def __del__(self):
         try:
@@ -649,6 +716,13 @@ class I3CLSimStepToPhotonConverterHIP:
         hit generator."""
         self._call("clsimhip_set_pmt_series", int(bool(on)))
         self._pmt_series = bool(on)
+    def SetFramePhotons(self, on=True, keepPhotons=True):
+        """the sorting stage behind the propagation kernel's photon records: every result's detected photons come back as per-frame,
+        per-module sorted series of compressed photons, the client module's PropagatedPhotons (result attributes `frame_photons`,
+        `frame_photon_series`, `frame_photons_masked`); independent of the hit generators.  keepPhotons=False leaves the 80-byte
+        records on the device.  Before Initialize() only."""
+        self._call("clsimhip_set_frame_photons", int(bool(on)), int(bool(keepPhotons)))
+        self._frame_photons = bool(on)
     def SetMCPEMerging(self, window, on=True):
         """the merging stage behind the series stage: records of a series within `window` of their group's opener become one merged
         record (result attributes `merged`, `merged_series`, `parents`, `parent_ranges`; `mcpes` and `series` stay the unmerged
@@ -748,7 +822,23 @@ class I3CLSimStepToPhotonConverterHIP:
 
     def _has_handle(self):
         """a result without photon records still has a handle to release when a hit maker is attached"""
-        return self._mcpe is not None or self._pmt is not None
+        return self._mcpe is not None or self._pmt is not None or self._frame_photons
+
+    def GetResultFramePhotons(self, ptr):
+        """copies of the frame photons of the result `ptr` belongs to: (records, series table, MASKED count); CLSIMHIP_ERR_STATE
+        without SetFramePhotons"""
+        rp, rn, sp, sn, masked = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_size_t(), C.c_uint64()
+        self._call("clsimhip_get_result_frame_photons", ptr, C.byref(rp), C.byref(rn), C.byref(sp), C.byref(sn), C.byref(masked))
+        records, series = np.zeros(rn.value, dtype=FRAME_PHOTON_DTYPE), np.zeros(sn.value, dtype=MCPE_SERIES_DTYPE)
+        if rn.value:
+            C.memmove(records.ctypes.data, rp.value, rn.value * 48)
+        if sn.value:
+            C.memmove(series.ctypes.data, sp.value, sn.value * 16)
+        return records, series, int(masked.value)
+
+    def _attach_frame_photons(self, result, fp):
+        if fp is not None:
+            result.frame_photons, result.frame_photon_series, result.frame_photons_masked = fp
 
     def GetConversionResult(self, with_histories=False, out=None):
         """ConversionResult_t (I3CLSimStepToPhotonConverter.h:70-90): (identifier, photons), plus with
@@ -785,12 +875,14 @@ class I3CLSimStepToPhotonConverterHIP:
                     histories = []
             mcpes = self._result_mcpes(ptr)
             pmt_hits = self._result_pmt_hits(ptr)
+            fp = self.GetResultFramePhotons(ptr) if self._frame_photons else None
         finally:
             if n.value or self._has_handle():
                 self._call("clsimhip_release_result", ptr)
         result = ConversionResult((ident.value, photons, histories) if with_histories else (ident.value, photons))
         self._attach_mcpes(result, mcpes)
         self._attach_pmt_hits(result, pmt_hits)
+        self._attach_frame_photons(result, fp)
         return result
 
     def GetConversionResultInPlace(self):
@@ -803,6 +895,7 @@ class I3CLSimStepToPhotonConverterHIP:
         try:
             mcpes = self._result_mcpes(ptr)
             pmt_hits = self._result_pmt_hits(ptr)
+            fp = self.GetResultFramePhotons(ptr) if self._frame_photons else None
         except Exception:
             if n.value or self._has_handle():
                 self._call("clsimhip_release_result", ptr)
@@ -818,6 +911,7 @@ class I3CLSimStepToPhotonConverterHIP:
             result = ConversionResult((ident.value, view, (lambda: self._call("clsimhip_release_result", ptr))))
         self._attach_mcpes(result, mcpes)
         self._attach_pmt_hits(result, pmt_hits)
+        self._attach_frame_photons(result, fp)
         return result
 
     def _attach_pmt_hits(self, result, pmt_hits):
@@ -994,14 +1088,17 @@ def initializeHIP(device, geometry, medium, wavelengthGenerationBias, wavelength
                   enableDoubleBuffering=False, doublePrecision=False, stopDetectedPhotons=True, saveAllPhotons=False,
                   saveAllPhotonsPrescale=0.01, fixedNumberOfAbsorptionLengths=float("nan"), pancakeFactor=1.0,
                   photonHistoryEntries=0, limitWorkgroupSize=0, approximateNumberOfWorkItems=262144,
-                  seed=12345, streams=None, tuning=None, mcpeGenerator=None, keepPhotons=True, mcpeSeries=False, pmtHitGenerator=None, mcpeMergeWindow=None, pmtSeries=False):
+                  seed=12345, streams=None, tuning=None, mcpeGenerator=None, keepPhotons=True, mcpeSeries=False, pmtHitGenerator=None, mcpeMergeWindow=None, pmtSeries=False,
+                  framePhotons=False):
     """Canonical configuration sequence, I3CLSimModuleHelper::initializeOpenCL
     (ModuleHelper.cxx:303-372).  tuning: {key: value} for clsimhip_set_tuning, applied before Compile().
     mcpeGenerator: an MCPEGenerator that turns every bunch's photons into MCPEs on the GPU (result attribute `mcpes`);
     keepPhotons=False then leaves the photon records on the device; mcpeSeries=True sorts them into per-frame, per-DOM series;
     mcpeMergeWindow=w then merges the records of a series within w of their group's opener (SetMCPEMerging).
     pmtHitGenerator: a PMTHitGenerator instead, for modules with several PMTs (result attribute `pmt_hits`; keepPhotons as above);
-    pmtSeries=True sorts its hits into per-frame, per-module, per-PMT series (SetPMTSeries)."""
+    pmtSeries=True sorts its hits into per-frame, per-module, per-PMT series (SetPMTSeries).
+    framePhotons=True files the detected photons themselves into per-frame, per-module sorted series (SetFramePhotons; keepPhotons as
+    above)."""
     conv = I3CLSimStepToPhotonConverterHIP(device)
     for key, value in (tuning or {}).items():
         conv.SetTuning(key, value)
@@ -1027,6 +1124,8 @@ def initializeHIP(device, geometry, medium, wavelengthGenerationBias, wavelength
         conv.SetPMTHitGenerator(pmtHitGenerator, keepPhotons)
     if pmtSeries:
         conv.SetPMTSeries(True)
+    if framePhotons:
+        conv.SetFramePhotons(True, keepPhotons)
     conv.Compile()
     max_wg = conv.GetMaxWorkgroupSize()
     if limitWorkgroupSize:

@@ -15,6 +15,7 @@
 #include "mcpe.h"
 #include "mcpe_merge.h"
 #include "pmt_hits.h"
+#include "frame_photons.h"
 #include "pmt_series.h"
 
 using namespace clsimhip;
@@ -23,6 +24,7 @@ struct clsimhip_converter { Converter impl; explicit clsimhip_converter(int dev)
 struct clsimhip_medium { MediumData data; };
 struct clsimhip_mcpe_generator { std::shared_ptr<McpeGenerator> impl; };
 struct clsimhip_pmt_generator { std::shared_ptr<PmtHitGenerator> impl; };
+struct clsimhip_frame_photon_doms { std::shared_ptr<FramePhotonDoms> impl; };
 struct clsimhip_tabulator {
     std::unique_ptr<Tabulator> impl;
 };
@@ -1161,6 +1163,50 @@ int clsimhip_get_result_pmt_series(clsimhip_converter *c, const clsimhip_photon 
                                    const clsimhip_pmt_series **series, size_t *n_series, uint64_t *n_masked)
 {
     return guarded(c, [&] { need(c, "converter"); c->impl.result_pmt_series(photons, hits, n, series, n_series, n_masked); });
+}
+
+// ---- Frame photons (frame_photons.h) ----
+int clsimhip_frame_photon_doms_create(size_t n_doms, const int32_t *string_ids, const uint32_t *om_ids, clsimhip_frame_photon_doms **out)
+{
+    return guarded(nullptr, [&] {
+        need(out, "out");
+        *out = new clsimhip_frame_photon_doms{std::make_shared<FramePhotonDoms>(string_ids, om_ids, n_doms)};
+    });
+}
+void clsimhip_frame_photon_doms_destroy(clsimhip_frame_photon_doms *d) { delete d; }
+const char *clsimhip_frame_photon_doms_last_error(const clsimhip_frame_photon_doms *d) { (void)d; return g_last_error.c_str(); }
+int clsimhip_frame_photons_host(const clsimhip_frame_photon_doms *d, const clsimhip_photon *photons, size_t n, const clsimhip_mcpe_particle *particles,
+                                size_t n_particles, const clsimhip_mcpe_mask *masked, size_t n_masked, clsimhip_frame_photon *out,
+                                clsimhip_mcpe_series *series, size_t *n_kept, size_t *n_series, uint64_t counters[4])
+{
+    return guarded(nullptr, [&] {
+        need(d, "DOM list");
+        if (counters) std::memset(counters, 0, 4 * sizeof(uint64_t));
+        d->impl->host(photons, n, particles, n_particles, masked, n_masked, out, series, n_kept, n_series, counters);
+    });
+}
+size_t clsimhip_frame_photons_workspace_bytes(size_t capacity, size_t n_particles, size_t n_masked)
+{
+    return frame_photons_workspace_bytes(capacity, n_particles, n_masked);
+}
+int clsimhip_frame_photons_device(clsimhip_frame_photon_doms *d, int device, const void *d_photons, const void *d_count, size_t capacity,
+                                  const clsimhip_mcpe_particle *particles, size_t n_particles, const clsimhip_mcpe_mask *masked, size_t n_masked,
+                                  void *d_out, void *d_series, void *d_counts, void *d_workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return guarded(nullptr, [&] {
+        need(d, "DOM list");
+        d->impl->device(device, d_photons, d_count, capacity, particles, n_particles, masked, n_masked, d_out, d_series, d_counts, d_workspace,
+                        workspace_bytes, static_cast<hipStream_t>(hip_stream));
+    });
+}
+int clsimhip_set_frame_photons(clsimhip_converter *c, int on, int keep_photons)
+{
+    return guarded(c, [&] { need(c, "converter"); c->impl.set_frame_photons(on != 0, keep_photons != 0); });
+}
+int clsimhip_get_result_frame_photons(clsimhip_converter *c, const clsimhip_photon *photons, const clsimhip_frame_photon **records, size_t *n,
+                                      const clsimhip_mcpe_series **series, size_t *n_series, uint64_t *n_masked)
+{
+    return guarded(c, [&] { need(c, "converter"); c->impl.result_frame_photons(photons, records, n, series, n_series, n_masked); });
 }
 
 } // extern "C"

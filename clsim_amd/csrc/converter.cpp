@@ -7,6 +7,7 @@
 #include "mcpe.h"
 #include "mcpe_merge.h"
 #include "pmt_hits.h"
+#include "frame_photons.h"
 #include "pmt_series.h"
 
 #include <chrono>
@@ -184,6 +185,8 @@ void Converter::release_device()
     merge_pool_.reset();
     pmt_pool_.reset();
     pmt_series_pool_.reset();
+    fp_pool_.reset();
+    fp_series_pool_.reset();
     bunch_pool_.reset();
 }
 
@@ -341,6 +344,18 @@ void Converter::compile()
                 throw Error(CLSIMHIP_ERR_CONFIG, "PMT hit generator: a module type's sphere radius is " + std::to_string(radius) + " m, photons are recorded at " +
                                                      std::to_string(recorded_at) + " m");
         if (history_entries_ && !pmt_keep_photons_) throw Error(CLSIMHIP_ERR_CONFIG, "photon histories need keep_photons");
+    }
+    fp_doms_.reset();
+    if (frame_photons_) {
+        // the stage reads IDs from the records and files them under the geometry's DOMs: every pair must fit the record
+        for (size_t i = 0; i < geometry_.string_ids.size(); ++i) {
+            const int32_t sid = geometry_.string_ids[i];
+            const uint32_t did = geometry_.dom_ids[i];
+            if (sid < -32768 || sid > 32767 || did > 65535u)
+                throw Error(CLSIMHIP_ERR_CONFIG, "frame photons: string ID " + std::to_string(sid) + " / OM ID " + std::to_string(did) + " does not fit the photon record");
+        }
+        if (history_entries_ && !fp_keep_photons_) throw Error(CLSIMHIP_ERR_CONFIG, "photon histories need keep_photons");
+        fp_doms_ = std::make_shared<FramePhotonDoms>(geometry_.string_ids.data(), geometry_.dom_ids.data(), geometry_.string_ids.size());
     }
     tables_ = compile_tables(medium_, geometry_, generators_, bias_, pancake_, table_tuning_);
     if (!std::isnan(fixed_abs_lengths_)) {                      // OpenCL.cxx:425-431
@@ -533,6 +548,15 @@ void Converter::setup_device_buffers(DeviceState &D)
             sl.d_pmt_series_counts.alloc(8, "PMT series counts");
             sl.h_pmt_series_counts.alloc(8, "pinned PMT series counts");
         }
+        if (frame_photons_) {
+            if (!D.id_strings) throw Error(CLSIMHIP_ERR_CONFIG, "frame photons: the geometry has no DOM");
+            sl.fp_workspace_bytes = frame_photons_workspace_bytes(max_output_photons_, 0, 0);
+            sl.d_fp_workspace.alloc(sl.fp_workspace_bytes, "frame photons workspace");
+            sl.d_fp_out.alloc(max_output_photons_, "frame photons");
+            sl.d_fp_series.alloc(max_output_photons_, "frame photons series table");
+            sl.d_fp_counts.alloc(8, "frame photons counts");
+            sl.h_fp_counts.alloc(8, "pinned frame photons counts");
+        }
         if (series_) {
             sl.series_workspace_bytes = mcpe_series_workspace_bytes(max_output_photons_, 0, 0);
             sl.d_series_workspace.alloc(sl.series_workspace_bytes, "MCPE series workspace");
@@ -638,8 +662,9 @@ void Converter::enqueue_steps(const clsimhip_step *steps, size_t n, uint32_t ide
                               const clsimhip_mcpe_mask *masked, size_t n_masked)
 {
     need_init();
-    if ((particles || n_particles || masked || n_masked) && !series_ && !pmt_series_)
-        throw Error(CLSIMHIP_ERR_STATE, "a particle table or mask needs the MCPE series stage (clsimhip_set_mcpe_series) or the PMT series stage (clsimhip_set_pmt_series)");
+    if ((particles || n_particles || masked || n_masked) && !series_ && !pmt_series_ && !frame_photons_)
+        throw Error(CLSIMHIP_ERR_STATE, "a particle table or mask needs the MCPE series stage (clsimhip_set_mcpe_series), the PMT series stage (clsimhip_set_pmt_series) "
+                                        "or the frame photons stage (clsimhip_set_frame_photons)");
     check_worker();
     if (!steps) throw Error(CLSIMHIP_ERR_ARGUMENT, "Steps pointer is (null)!");
     if (n == 0) throw Error(CLSIMHIP_ERR_ARGUMENT, "Steps are empty!");
@@ -663,6 +688,16 @@ void Converter::enqueue_steps(const clsimhip_step *steps, size_t n, uint32_t ide
         }
         job.bunch = series_ ? mcpe_->prepare_series(particles, n_particles, masked, n_masked, blob)
                             : pmt_->prepare_series(particles, n_particles, masked, n_masked, blob);
+    }
+    if (frame_photons_) {
+        const size_t bytes = frame_photons_blob_bytes(n_particles, n_masked);
+        job.fp_bunch_pinned = bunch_pool_.take(bytes, bytes + bytes / 4, device_);
+        uint8_t *blob = job.fp_bunch_pinned.get();
+        if (!blob) {
+            job.fp_bunch_blob.resize((bytes + 15u) / 16u);
+            blob = job.fp_bunch_blob.data()->bytes;
+        }
+        job.fp_bunch = fp_doms_->prepare(particles, n_particles, masked, n_masked, blob);
     }
     in_queue_->put(std::move(job));
 }
@@ -760,6 +795,29 @@ void Converter::submit(Slot &s, Job &job)
                                      s.d_pmt_series.get(), s.d_pmt_series_counts.get(), s.d_pmt_series_workspace.get(), s.pmt_series_workspace_bytes, stream);
         hip_check(hipMemcpyAsync(s.h_pmt_series_counts.get(), s.d_pmt_series_counts.get(), 20, hipMemcpyDeviceToHost, stream), "download PMT series counts");
     }
+    if (frame_photons_) {
+        // behind assemble_hits_kernel on the bunch's stream, over the records the bunch stored; beside whatever hit maker ran above
+        s.fp_bunch_lease = std::move(job.fp_bunch_pinned);
+        const uint8_t *blob = s.fp_bunch_lease.get();
+        if (!blob) {
+            if (s.h_fp_bunch_bytes < job.fp_bunch.bytes) {
+                s.h_fp_bunch.reset();
+                s.h_fp_bunch.alloc(job.fp_bunch.bytes, "pinned frame photons bunch");
+                s.h_fp_bunch_bytes = job.fp_bunch.bytes;
+            }
+            std::memcpy(s.h_fp_bunch.get(), job.fp_bunch_blob.data(), job.fp_bunch.bytes);
+            blob = s.h_fp_bunch.get();
+        }
+        const size_t need = frame_photons_workspace_bytes(max_output_photons_, job.fp_bunch.n_particles, job.fp_bunch.n_masked) + 64;
+        if (s.fp_workspace_bytes < need) {              // (the slot is free: nothing on the device uses its workspace)
+            s.d_fp_workspace.reset();
+            s.d_fp_workspace.alloc(need + need / 4, "frame photons workspace");
+            s.fp_workspace_bytes = need + need / 4;
+        }
+        fp_doms_->device_prepared(device_, s.d_photons.get(), s.d_hit_count.get(), max_output_photons_, job.fp_bunch, blob, s.d_fp_out.get(), s.d_fp_series.get(),
+                                  s.d_fp_counts.get(), s.d_fp_workspace.get(), s.fp_workspace_bytes, stream);
+        hip_check(hipMemcpyAsync(s.h_fp_counts.get(), s.d_fp_counts.get(), 24, hipMemcpyDeviceToHost, stream), "download frame photons counts");
+    }
     hip_check(hipEventRecord(s.counted.get(), stream), "event");
 }
 
@@ -823,6 +881,16 @@ void Converter::finish(Slot &s, std::chrono::steady_clock::time_point &last_done
                                                  " at modules or PMTs the generator does not have");
         n_pmt_hits = std::min(sc[0], max_output_photons_);
         n_pmt_series = std::min(sc[1], n_pmt_hits);
+    }
+    uint32_t n_fp = 0, n_fp_series = 0;
+    if (frame_photons_) {
+        const uint32_t *fc = s.h_fp_counts.get();           // kept, series, UNKNOWN_PARTICLE, MASKED, UNKNOWN_DOM, TIE_OVERFLOW
+        if ((fc[2] | fc[4] | fc[5]) != 0u)                  // log_fatal in the reference (I3CLSimClientModule.cxx:388-390)
+            throw Error(CLSIMHIP_ERR_DEVICE, "frame photons, bunch " + std::to_string(s.id) + ": " + std::to_string(fc[2]) +
+                                                 " photons of particles the bunch's particle table does not have, " + std::to_string(fc[4]) +
+                                                 " at DOMs the geometry does not have, " + std::to_string(fc[5]) + " in runs of colliding records beyond the bound");
+        n_fp = std::min(fc[0], max_output_photons_);
+        n_fp_series = std::min(fc[1], n_fp);
     }
     const uint32_t detected = hits;
     if (!carries_photons()) hits = 0;                   // the records stay on the device
@@ -907,6 +975,27 @@ void Converter::finish(Slot &s, std::chrono::steady_clock::time_point &last_done
         }
         r.pmt_series_count = n_pmt_series;
         if (pmt_series_) r.masked = s.h_pmt_series_counts.get()[3];
+        if (!hits && !r.handle) r.handle.reset(new clsimhip_photon());
+    }
+    if (frame_photons_) {
+        r.fp_count = n_fp;
+        if (n_fp) {
+            r.fp_pinned = fp_pool_.take(n_fp, result_capacity(n_fp, s.result_min_records), device_);
+            clsimhip_frame_photon *to = r.fp_pinned.get();
+            if (!to) { r.fp_records.reset(new std::vector<clsimhip_frame_photon>(n_fp)); to = r.fp_records->data(); }
+            hip_check(hipMemcpyAsync(to, s.d_fp_out.get(), static_cast<size_t>(n_fp) * sizeof(clsimhip_frame_photon), hipMemcpyDeviceToHost, copy_stream),
+                      "download frame photons");
+            if (n_fp_series) {
+                r.fp_series_pinned = fp_series_pool_.take(n_fp_series, result_capacity(n_fp_series, s.result_min_records), device_);
+                clsimhip_mcpe_series *table = r.fp_series_pinned.get();
+                if (!table) { r.fp_series.reset(new std::vector<clsimhip_mcpe_series>(n_fp_series)); table = r.fp_series->data(); }
+                hip_check(hipMemcpyAsync(table, s.d_fp_series.get(), static_cast<size_t>(n_fp_series) * sizeof(clsimhip_mcpe_series), hipMemcpyDeviceToHost,
+                                         copy_stream), "download frame photons series table");
+            }
+            hip_check(hipStreamSynchronize(copy_stream), "download frame photons");
+        }
+        r.fp_series_count = n_fp_series;
+        r.fp_masked = s.h_fp_counts.get()[3];
         if (!hits && !r.handle) r.handle.reset(new clsimhip_photon());
     }
     std::unique_ptr<std::vector<float>> histories;
@@ -1081,6 +1170,24 @@ void Converter::result_pmt_series(const clsimhip_photon *photons, const clsimhip
     if (it->second.pmt_count) *hits = it->second.pmt_data();
     if (it->second.pmt_series_count) *series = it->second.pmt_series_data();
     if (n_masked) *n_masked = it->second.masked;
+}
+
+void Converter::result_frame_photons(const clsimhip_photon *photons, const clsimhip_frame_photon **records, size_t *n, const clsimhip_mcpe_series **series,
+                                     size_t *n_series, uint64_t *n_masked)
+{
+    need_init();
+    if (!records || !n || !series || !n_series) throw Error(CLSIMHIP_ERR_ARGUMENT, "output pointers are (null)");
+    if (!frame_photons_) throw Error(CLSIMHIP_ERR_STATE, "the frame photons stage is off (clsimhip_set_frame_photons)");
+    *records = nullptr; *series = nullptr;
+    *n = 0; *n_series = 0;
+    std::lock_guard<std::mutex> lk(results_mutex_);
+    auto it = handed_out_.find(photons);
+    if (it == handed_out_.end()) throw Error(CLSIMHIP_ERR_ARGUMENT, "not a result handed out by GetConversionResult (or already released)");
+    *n = it->second.fp_count;
+    *n_series = it->second.fp_series_count;
+    if (it->second.fp_count) *records = it->second.fp_data();
+    if (it->second.fp_series_count) *series = it->second.fp_series_data();
+    if (n_masked) *n_masked = it->second.fp_masked;
 }
 
 void Converter::result_mcpe_series(const clsimhip_photon *photons, const clsimhip_mcpe **mcpes, size_t *n, const clsimhip_mcpe_series **series, size_t *n_series,

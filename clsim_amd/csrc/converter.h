@@ -24,6 +24,7 @@ namespace clsimhip {
 
 class McpeGenerator;            // mcpe.h
 class PmtHitGenerator;          // pmt_hits.h
+class FramePhotonDoms;          // frame_photons.h
 struct alignas(16) SeriesParticle16 { uint8_t bytes[16]; };     // 16-byte aligned storage for a bunch's table and mask (mcpe_series.h)
 
 // RCCL gather of detected photons (comm.cpp)
@@ -291,6 +292,9 @@ public:
     void set_pmt_generator(std::shared_ptr<PmtHitGenerator> g, bool keep_photons);
     // clsimhip_set_pmt_series: the sorting stage behind the PMT hit maker (pmt_series.h); needs a PMT hit generator (Compile() checks)
     void set_pmt_series(bool on) { guard(); compiled_ = false; pmt_series_ = on; }
+    // clsimhip_set_frame_photons: the sorting stage behind the propagation kernel's photon records (frame_photons.h), with the
+    // geometry's DOMs as its list (Compile() makes it); beside either hit generator or none
+    void set_frame_photons(bool on, bool keep_photons) { guard(); compiled_ = false; frame_photons_ = on; fp_keep_photons_ = keep_photons; }
 
     void compile();
     void initialize(uint64_t seed);
@@ -314,6 +318,8 @@ public:
     void result_pmt_hits(const clsimhip_photon *photons, const clsimhip_pmt_hit **hits, size_t *n);
     void result_pmt_series(const clsimhip_photon *photons, const clsimhip_pmt_hit **hits, size_t *n, const clsimhip_pmt_series **series, size_t *n_series,
                            uint64_t *n_masked);
+    void result_frame_photons(const clsimhip_photon *photons, const clsimhip_frame_photon **records, size_t *n, const clsimhip_mcpe_series **series,
+                              size_t *n_series, uint64_t *n_masked);
     void release_result(const clsimhip_photon *photons);
     size_t queue_size() const;
     bool more_photons_available() const;
@@ -355,16 +361,19 @@ private:
     using SeriesPool = PinnedPool<clsimhip_mcpe_series>;
     using PmtHitPool = PinnedPool<clsimhip_pmt_hit>;
     using PmtSeriesPool = PinnedPool<clsimhip_pmt_series>;
+    using FramePhotonPool = PinnedPool<clsimhip_frame_photon>;
     using BlobPool = PinnedPool<uint8_t>;
     // A bunch on its way to the worker: the caller's steps are copied ONCE, in the caller's thread, into a page-locked buffer of the
     // step pool, which the worker uploads from (round 5; before, a vector here and a second copy into the slot's staging buffer on
     // the worker thread -- 8 ms per million steps in front of the first kernel of a run).  With every pool buffer in flight the
     // steps travel in a vector as before.
     // With the MCPE series stage the bunch's particle table and mask travel the same way, in the form the stage reads (mcpe_series.h);
-    // with the PMT series stage likewise (pmt_series.h: the two stages never run in one converter).
+    // with the PMT series stage likewise (pmt_series.h: the two stages never run in one converter).  The frame photons stage ranks the
+    // geometry's DOMs, not a generator's, so its table and mask travel in a blob of their own.
     struct Job {
         uint32_t id = 0; size_t n = 0; uint64_t generated = 0; StepPool::Lease pinned; std::vector<clsimhip_step> steps;
         SeriesBunch bunch; BlobPool::Lease bunch_pinned; std::vector<SeriesParticle16> bunch_blob;
+        SeriesBunch fp_bunch; BlobPool::Lease fp_bunch_pinned; std::vector<SeriesParticle16> fp_bunch_blob;
     };
     // The photons of a result live in a page-locked buffer of the converter's pool (the download lands there and the
     // caller reads them there until ReleaseResult: no host copy in between), or -- when the pool is exhausted because the
@@ -405,6 +414,16 @@ private:
         size_t pmt_series_count = 0;
         std::unique_ptr<std::vector<clsimhip_pmt_series>> pmt_series;
         const clsimhip_pmt_series *pmt_series_data() const { return pmt_series_pinned ? pmt_series_pinned.get() : (pmt_series ? pmt_series->data() : nullptr); }
+        // with the frame photons stage: its records, its series table and its MASKED count (and `handle` for a result without photon records)
+        FramePhotonPool::Lease fp_pinned;
+        size_t fp_count = 0;
+        std::unique_ptr<std::vector<clsimhip_frame_photon>> fp_records;
+        const clsimhip_frame_photon *fp_data() const { return fp_pinned ? fp_pinned.get() : (fp_records ? fp_records->data() : nullptr); }
+        SeriesPool::Lease fp_series_pinned;
+        size_t fp_series_count = 0;
+        uint64_t fp_masked = 0;
+        std::unique_ptr<std::vector<clsimhip_mcpe_series>> fp_series;
+        const clsimhip_mcpe_series *fp_series_data() const { return fp_series_pinned ? fp_series_pinned.get() : (fp_series ? fp_series->data() : nullptr); }
     };
 
     void guard() const { if (initialized_) throw Error(CLSIMHIP_ERR_STATE, "I3CLSimStepToPhotonConverterHIP already initialized!"); }
@@ -438,7 +457,10 @@ private:
     std::shared_ptr<PmtHitGenerator> pmt_;      // null: no PMT hits are made (the default)
     bool pmt_keep_photons_ = true;
     bool pmt_series_ = false;                   // the PMT series stage runs behind the PMT hit maker
-    bool carries_photons() const { return !(mcpe_ && !keep_photons_) && !(pmt_ && !pmt_keep_photons_); }
+    bool frame_photons_ = false;                // the frame photons stage runs behind the propagation kernel
+    bool fp_keep_photons_ = true;
+    std::shared_ptr<FramePhotonDoms> fp_doms_;  // the geometry's DOMs (Compile())
+    bool carries_photons() const { return !(mcpe_ && !keep_photons_) && !(pmt_ && !pmt_keep_photons_) && !(frame_photons_ && !fp_keep_photons_); }
 
     std::atomic<bool> compiled_{false}, initialized_{false};    // (atomic: set_tuning() reads them from any thread)
     CompiledTables tables_;
@@ -455,6 +477,8 @@ private:
     BlobPool merge_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
     PmtHitPool pmt_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
     PmtSeriesPool pmt_series_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
+    FramePhotonPool fp_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
+    SeriesPool fp_series_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
     // particle tables and masks of the bunches on their way (input queue depth + one per slot + the one being filled)
     BlobPool bunch_pool_{PinnedPoolPolicy{8, size_t{1} << 28, nullptr}};
     size_t result_capacity(size_t records, size_t min_records) const;
@@ -505,6 +529,17 @@ private:
         DeviceBuffer<clsimhip_mcpe_parent_range> d_ranges;
         DeviceBuffer<uint32_t> d_merge_counts;
         PinnedBuffer<uint32_t> h_merge_counts;
+        // with the frame photons stage: its workspace (grown when a bunch's table needs it), records, series table, six counts, and the
+        // bunch's table as for the series stages
+        DeviceBuffer<uint8_t> d_fp_workspace;
+        size_t fp_workspace_bytes = 0;
+        DeviceBuffer<clsimhip_frame_photon> d_fp_out;
+        DeviceBuffer<clsimhip_mcpe_series> d_fp_series;
+        DeviceBuffer<uint32_t> d_fp_counts;
+        PinnedBuffer<uint32_t> h_fp_counts;
+        BlobPool::Lease fp_bunch_lease;
+        PinnedBuffer<uint8_t> h_fp_bunch;
+        size_t h_fp_bunch_bytes = 0;
         BlobPool::Lease bunch_lease;            // the pool buffer the slot's table upload reads; back to the pool when the slot is used again
         PinnedBuffer<uint8_t> h_bunch;          // pinned staging (for a job that came without a pool buffer)
         size_t h_bunch_bytes = 0;

@@ -215,6 +215,18 @@ public:
         lastSeries_.clear();
         lastMerged_.clear(); lastMergedSeries_.clear(); lastParents_.clear(); lastParentRanges_.clear();
         lastMasked_ = 0;
+        lastFramePhotons_.clear();
+        lastFramePhotonSeries_.clear();
+        lastMaskedFramePhotons_ = 0;
+        if (framePhotons_) {        // (fetched first: a result without photon records is released behind the last getter)
+            const clsimhip_frame_photon *f = nullptr;
+            const clsimhip_mcpe_series *s = nullptr;
+            size_t nf = 0, ns = 0;
+            check(clsimhip_get_result_frame_photons(handle_, p, &f, &nf, &s, &ns, &lastMaskedFramePhotons_));
+            lastFramePhotons_.assign(f, f + nf);
+            lastFramePhotonSeries_.assign(s, s + ns);
+            if (!n && !mcpeGenerator_ && !pmtHitGenerator_) check(clsimhip_release_result(handle_, p));
+        }
         if (mcpeGenerator_) {       // (ConversionResult_t has no place for them: GetLastMCPEs())
             const clsimhip_mcpe *m = nullptr;
             size_t nm = 0;
@@ -407,6 +419,31 @@ public:
         return frames;
     }
 
+    // ---- Frame photons (include/clsimhip.h, "Frame photons"): the client module's PropagatedPhotons, an I3CompressedPhotonSeriesMap per
+    // frame, made on the GPU from the bunch's photon records.  Before Initialize(); beside either hit generator or none.  A bunch is
+    // enqueued with its particle table and its frames' ignored modules (EnqueueSteps below); keepPhotons = false leaves the 80-byte
+    // records on the device. ----
+    void SetFramePhotons(bool on = true, bool keepPhotons = true)
+    {
+        check(clsimhip_set_frame_photons(handle_, on ? 1 : 0, keepPhotons ? 1 : 0));
+        framePhotons_ = on;
+    }
+    // the flat views of the last result: the records in the order of the series, the series table (entries partition the records),
+    // the MASKED count
+    const std::vector<clsimhip_frame_photon> &GetLastFramePhotons() const { return lastFramePhotons_; }
+    const std::vector<clsimhip_mcpe_series> &GetLastFramePhotonSeries() const { return lastFramePhotonSeries_; }
+    uint64_t GetLastMaskedFramePhotons() const { return lastMaskedFramePhotons_; }
+    // ... and as the frames receive them: frame -> (string ID, OM ID) -> the module's photons
+    typedef std::map<std::pair<int, unsigned>, std::vector<clsimhip_frame_photon> > FramePhotonSeriesMap;
+    std::map<uint32_t, FramePhotonSeriesMap> GetLastFramePhotonMaps() const
+    {
+        std::map<uint32_t, FramePhotonSeriesMap> frames;
+        for (const clsimhip_mcpe_series &s : lastFramePhotonSeries_)
+            frames[s.frame][std::make_pair(static_cast<int>(s.string_id), static_cast<unsigned>(s.om_id))]
+                .assign(lastFramePhotons_.begin() + s.first, lastFramePhotons_.begin() + s.first + s.count);
+        return frames;
+    }
+
     // ---- MCPE series (include/clsimhip.h, "MCPE series"): what replaces the client module's AddPhotonsToFrames loop and the per-DOM
     // time sort.  Before Initialize(); needs a generator.  A bunch is enqueued with its particle table (strictly increasing in
     // identifier) and its frames' ignored modules; its result's MCPEs come back per frame, per DOM in OMKey order, in time order. ----
@@ -504,6 +541,10 @@ private:
     bool pmtHitGenerator_ = false;
     std::vector<clsimhip_pmt_hit> lastPMTHits_;
     bool pmtSeries_ = false;
+    bool framePhotons_ = false;
+    std::vector<clsimhip_frame_photon> lastFramePhotons_;
+    std::vector<clsimhip_mcpe_series> lastFramePhotonSeries_;
+    uint64_t lastMaskedFramePhotons_ = 0;
     std::vector<clsimhip_pmt_series> lastPMTSeries_;
 #ifdef CLSIMHIP_WITH_ICETRAY
     I3RandomServicePtr randomService_;

@@ -884,8 +884,8 @@ int clsimhip_mcpe_series_device(clsimhip_mcpe_generator *g, int device, const vo
  * as a bunch with one of the MCPE generator's four conditions does, with the count in the text. */
 int clsimhip_set_mcpe_series(clsimhip_converter *c, int on);
 /* clsimhip_enqueue_steps with the bunch's particle table and mask, which are checked and copied in the caller's thread
- * (CLSIMHIP_ERR_ARGUMENT / CLSIMHIP_ERR_CONFIG as above; CLSIMHIP_ERR_STATE with neither clsimhip_set_mcpe_series nor
- * clsimhip_set_pmt_series).  A bunch enqueued with clsimhip_enqueue_steps has no table: one frame, 0. */
+ * (CLSIMHIP_ERR_ARGUMENT / CLSIMHIP_ERR_CONFIG as above; CLSIMHIP_ERR_STATE with none of clsimhip_set_mcpe_series,
+ * clsimhip_set_pmt_series and clsimhip_set_frame_photons).  A bunch enqueued with clsimhip_enqueue_steps has no table: one frame, 0. */
 int clsimhip_enqueue_steps_with_particles(clsimhip_converter *c, const clsimhip_step *steps, size_t n, uint32_t identifier,
                                           const clsimhip_mcpe_particle *particles, size_t n_particles, const clsimhip_mcpe_mask *masked,
                                           size_t n_masked);
@@ -1124,6 +1124,84 @@ int clsimhip_set_pmt_series(clsimhip_converter *c, int on);
  * be NULL) receives the MASKED count.  Pointers are NULL where there is nothing.  CLSIMHIP_ERR_STATE without clsimhip_set_pmt_series. */
 int clsimhip_get_result_pmt_series(clsimhip_converter *c, const clsimhip_photon *photons, const clsimhip_pmt_hit **hits, size_t *n,
                                    const clsimhip_pmt_series **series, size_t *n_series, uint64_t *n_masked);
+
+/* ---- Frame photons: a bunch's detected photons as per-frame, per-module sorted series -------------------------------------
+ * The client module's default output, PhotonSeriesMapName = "PropagatedPhotons": an I3CompressedPhotonSeriesMap that
+ * AddPhotonsToFrames (private/clsim/I3CLSimClientModule.cxx:359-439) builds at :407-415 through Emit<I3CompressedPhoton>
+ * (:327-349) -- as a sorting stage behind the propagation kernel's photon records, the MCPE series' radix passes run twice.
+ * ("Frame photons", because clsimhip_photon_series_* is the wire format above.)  Per clsimhip_photon, in this order:
+ *     its module is not in the stage's DOM list -> UNKNOWN_DOM, no record;
+ *     its identifier is not in the particle table -> UNKNOWN_PARTICLE, no record (log_fatal in the reference, :388-390); without a
+ *     table the frame is 0 and the shift +0.0;
+ *     (frame, string_id, om_id) is in the mask -> MASKED, no record (:399; not an error);
+ *     time' = (double)time + time_shift, one binary64 addition (:334), which quiets a signalling NaN; weight, wavelength,
+ *     group_velocity, x, y, z, theta and phi are copied bit for bit.  theta and phi stay as the propagator stored them: the
+ *     reference passes them through I3Direction::SetThetaPhi, which lies outside it.
+ * The kept records come out ascending in
+ *     frame (ascending frame ID), module (ascending (string_id signed, om_id): OMKey::operator<), tkey(time'), identifier, h,
+ *     w0 ... w7
+ * where tkey is the MCPE series' total order on the time's bit pattern, w0 ... w7 are the eight float fields as uint32 bit patterns
+ * in declared order, and h is FNV-1a over their 32 bytes: h = 2166136261; for each word w0 ... w7, for each of its bytes from the least
+ * significant one: h = (h ^ byte) * 16777619 (mod 2^32).  h decides order, so it is part of this contract.  Records equal in all of
+ * that are byte-identical, so the output is a function of the input as a multiset: the same bytes from run to run, whatever the
+ * schedule, and the same bytes from the kernels and the host twin.  The series table (clsimhip_mcpe_series: frame, module, first,
+ * count) has one entry per non-empty (frame, module) in the same order; its entries partition the records.
+ * What differs from the reference, on purpose: it appends to each (frame, ModuleKey) vector in arrival order, which no two runs
+ * repeat -- here the order within a series is the one above; it adds the shift in the photon's binary32 -- here once, in binary64.
+ * One bound keeps every input's cost bounded.  Take a run of records equal in (frame, module, tkey, identifier, h) that holds at
+ * least two distinct contents: if it has more than 2 048 members, each member is counted as TIE_OVERFLOW and the call delivers no
+ * records (kept = series = 0); a bunch behind the converter fails then, as it does for UNKNOWN_PARTICLE.  A run of identical records
+ * of any length is fine.  Reaching the bound takes crafted 32-bit collisions at one module, time and particle. */
+typedef struct {
+    uint32_t identifier;
+    int16_t string_id;
+    uint16_t om_id;
+    double time;
+    float weight, wavelength, group_velocity, x, y, z, theta, phi;
+} clsimhip_frame_photon;                /* 48 bytes */
+typedef char clsimhip_frame_photon_is_48_bytes[sizeof(clsimhip_frame_photon) == 48 ? 1 : -1];
+#define CLSIMHIP_FRAME_PHOTONS_UNKNOWN_PARTICLE 0       /* index into the four counters */
+#define CLSIMHIP_FRAME_PHOTONS_MASKED 1
+#define CLSIMHIP_FRAME_PHOTONS_UNKNOWN_DOM 2
+#define CLSIMHIP_FRAME_PHOTONS_TIE_OVERFLOW 3
+#define CLSIMHIP_FRAME_PHOTONS_TIE_BOUND 2048
+/* The stage's DOM list (host only): the modules a photon may be filed under.  A pair named twice is one DOM.
+ * CLSIMHIP_ERR_ARGUMENT for a string ID outside int16 or an OM ID outside uint16. */
+typedef struct clsimhip_frame_photon_doms clsimhip_frame_photon_doms;
+int clsimhip_frame_photon_doms_create(size_t n_doms, const int32_t *string_ids, const uint32_t *om_ids, clsimhip_frame_photon_doms **out);
+void clsimhip_frame_photon_doms_destroy(clsimhip_frame_photon_doms *d);
+const char *clsimhip_frame_photon_doms_last_error(const clsimhip_frame_photon_doms *d);
+/* The host twin: the definition with std::sort on the full order, for callers without a GPU and for the tests.  particles = NULL,
+ * n_particles = 0: no table.  out and series hold n entries each; counters[4] (may be NULL) receives the four counts.
+ * CLSIMHIP_ERR_ARGUMENT for a table that is not strictly increasing in `identifier`, CLSIMHIP_ERR_CONFIG when frames x DOMs >= 2^32. */
+int clsimhip_frame_photons_host(const clsimhip_frame_photon_doms *d, const clsimhip_photon *photons, size_t n, const clsimhip_mcpe_particle *particles,
+                                size_t n_particles, const clsimhip_mcpe_mask *masked, size_t n_masked, clsimhip_frame_photon *out,
+                                clsimhip_mcpe_series *series, size_t *n_kept, size_t *n_series, uint64_t counters[4]);
+/* bytes of device memory the kernels need beside their input and output, for up to `capacity` records and a bunch with this table
+ * and mask */
+size_t clsimhip_frame_photons_workspace_bytes(size_t capacity, size_t n_particles, size_t n_masked);
+/* The kernels, on photon records that live in HBM with string and OM IDs in them: min(*d_count, capacity) records of d_photons.
+ * d_out and d_series: `capacity` entries each; d_photons, d_out, d_series and d_workspace
+ * (clsimhip_frame_photons_workspace_bytes(capacity, n_particles, n_masked) bytes) 16-byte aligned; d_counts: six uint32 -- records
+ * kept, series, then the four counters (CLSIMHIP_ERR_ARGUMENT for a misaligned pointer or a workspace that is too small; nothing is
+ * launched then).  The particle table and the mask are host memory: they are checked and copied before the call returns (which may
+ * wait for the previous call's copy, nothing else); the kernels are asynchronous on hip_stream (NULL = default stream) and nothing
+ * else waits for the device. */
+int clsimhip_frame_photons_device(clsimhip_frame_photon_doms *d, int device, const void *d_photons, const void *d_count, size_t capacity,
+                                  const clsimhip_mcpe_particle *particles, size_t n_particles, const clsimhip_mcpe_mask *masked, size_t n_masked,
+                                  void *d_out, void *d_series, void *d_counts, void *d_workspace, size_t workspace_bytes, void *hip_stream);
+/* The stage behind every bunch's propagation kernel, on the bunch's stream, with the geometry's DOMs as its list; independent of the
+ * hit generators and of their series stages, beside which it may run.  Before Initialize() only (CLSIMHIP_ERR_STATE after).
+ * on = 0 (the default): no launch, no allocation, no byte changes anywhere.  keep_photons = 0: the 80-byte records do not cross to
+ * the host, and the result's `photons` pointer is only the handle, as for the MCPE generator (Compile() refuses photon histories
+ * then, and a geometry whose IDs do not fit the record: CLSIMHIP_ERR_CONFIG).  With it on,
+ * clsimhip_enqueue_steps_with_particles takes the bunch's table and mask, and a bunch with UNKNOWN_PARTICLE, UNKNOWN_DOM or
+ * TIE_OVERFLOW > 0 fails (CLSIMHIP_ERR_DEVICE, the counts in the text). */
+int clsimhip_set_frame_photons(clsimhip_converter *c, int on, int keep_photons);
+/* Records and series table of the result `photons` belongs to, valid until clsimhip_release_result(c, photons); n_masked (may be
+ * NULL) receives the MASKED count.  Pointers are NULL where there is nothing.  CLSIMHIP_ERR_STATE without clsimhip_set_frame_photons. */
+int clsimhip_get_result_frame_photons(clsimhip_converter *c, const clsimhip_photon *photons, const clsimhip_frame_photon **records, size_t *n,
+                                      const clsimhip_mcpe_series **series, size_t *n_series, uint64_t *n_masked);
 
 #ifdef __cplusplus
 }

@@ -18,6 +18,9 @@ of tests/pmt_common.py, in photon records per second.
 --pmt-series N: the PMT series' host twin instead (clsimhip_pmt_series_host), in hits per second, on N synthetic hits at 5160
 modules of 31 PMTs dealt to 1000 particles in 10 frames; --device adds the device stage's time for the same input (HIP events
 around clsimhip_pmt_series_device, best of --repeats; needs a GPU).
+
+--frame-photons N: the frame photons' host twin instead (clsimhip_frame_photons_host), in photon records per second, on N synthetic
+records at 5160 DOMs dealt to 1000 particles in 10 frames; --device likewise (clsimhip_frame_photons_device).
 """
 import argparse
 import ctypes as C
@@ -126,6 +129,52 @@ def pmt_series_rate(args):
     print(json.dumps(line))
 
 
+def frame_photons_rate(args):
+    n = args.frame_photons
+    rng = np.random.default_rng(1)
+    s, d = np.meshgrid(np.arange(1, 87), np.arange(1, 61), indexing="ij")
+    s, d = s.reshape(-1).astype(np.int32), d.reshape(-1).astype(np.uint32)
+    doms = CV.FramePhotonDoms(s, d)
+    m = np.zeros(n, dtype=CV.PHOTON_DTYPE)
+    at = rng.integers(0, len(s), n)
+    m["stringID"], m["omID"], m["id"], m["t"] = s[at], d[at], rng.integers(0, 1000, n), rng.uniform(0.0, 1.0e4, n)
+    for name in ("x", "y", "z", "theta", "phi", "wavelength", "weight", "groupVelocity"):
+        m[name] = rng.uniform(0.1, 1.0, n)
+    p = np.zeros(1000, dtype=CV.MCPE_PARTICLE_DTYPE)
+    p["id"], p["frame"], p["timeShift"] = np.arange(1000), np.arange(1000) % 10, rng.uniform(0.0, 1.0e6, 1000)
+    masked = np.zeros(20, dtype=CV.MCPE_MASK_DTYPE)
+    masked["frame"], masked["stringID"], masked["omID"] = np.arange(20) % 10, 40, 30
+    best = float("inf")
+    for _ in range(args.repeats):
+        t0 = time.perf_counter()
+        records, series, counters = doms.MakeFramePhotonsHost(m, p, masked)
+        best = min(best, time.perf_counter() - t0)
+    line = {"photon_records": n, "kept": len(records), "series": len(series), "host_seconds": best, "host_records_per_s": n / best, "threads": 1}
+    if args.device:
+        import torch
+        dev = torch.device("cuda", 0)
+        d_in = torch.from_numpy(m.view(np.uint8).reshape(-1, 80).copy()).to(dev)
+        d_cnt = torch.tensor([n], dtype=torch.int32, device=dev)
+        d_out, d_series = torch.zeros((n, 48), dtype=torch.uint8, device=dev), torch.zeros((n, 16), dtype=torch.uint8, device=dev)
+        d_counts = torch.zeros(6, dtype=torch.int32, device=dev)
+        ws = CV.FramePhotonDoms.WorkspaceBytes(n, len(p), len(masked))
+        d_ws = torch.zeros(ws, dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream().cuda_stream
+        times = []
+        for _ in range(args.repeats + 1):
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            doms.MakeFramePhotonsDevice(d_in.data_ptr(), d_cnt.data_ptr(), n, d_out.data_ptr(), d_series.data_ptr(), d_counts.data_ptr(), d_ws.data_ptr(), ws,
+                                        p, masked, stream=stream)
+            stop.record()
+            torch.cuda.synchronize()
+            times.append(start.elapsed_time(stop) * 1e-3)
+        got = d_out.cpu().numpy()[:len(records)].copy().view(CV.FRAME_PHOTON_DTYPE).reshape(-1)
+        assert int(d_counts[0]) == len(records) and got.tobytes() == records.tobytes()
+        line.update(device_seconds=min(times[1:]), device_records_per_s=n / min(times[1:]))
+    print(json.dumps(line))
+
+
 def merge_rate(args):
     from tests import mcpe_merge_common as MM
     from tests import mcpe_series_common as S
@@ -178,7 +227,10 @@ def main():
     ap.add_argument("--pmt", action="store_true")
     ap.add_argument("--merge", action="store_true")
     ap.add_argument("--pmt-series", type=int, default=0, metavar="N")
+    ap.add_argument("--frame-photons", type=int, default=0, metavar="N")
     args = ap.parse_args()
+    if args.frame_photons:
+        return frame_photons_rate(args)
     if args.pmt_series:
         return pmt_series_rate(args)
     if args.merge:

@@ -4,10 +4,13 @@ the MCPE series stage, steps dealt to 1000 particles in 10 frames: the run to pu
 the stage's kernels beside the propagation kernel.  Prints the counts and the host-side wall time of the bunch.
 
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/mcpe_series_profile.py [--steps 1048576] [--no-series] [--merge-window NS]
+                                                                                   [--pmt] [--frame-photons]
 
 --merge-window NS: the MCPE merging stage behind the series stage, with that window.
 --pmt: a 31-PMT module (tests/pmt_common.py) at every DOM instead: the multi-PMT hit maker and the PMT series stage (--no-series:
 the hit maker alone).
+--frame-photons: no hit maker; the frame photons stage on the bunch's photon records, which stay on the device (--no-series: the
+propagation alone, records downloaded).
 """
 import argparse
 import json
@@ -44,12 +47,33 @@ def pmt_bunch(args, cfg, bias):
                       "pmt_series": None if r.pmt_series is None else len(r.pmt_series), "wall_seconds_second_bunch": wall}))
 
 
+def frame_photons_bunch(args, cfg, bias):
+    conv = CV.initializeHIP(0, CV.I3CLSimSimpleGeometry.from_dict(cfg["geom"]), cfg["med_p"], bias, common.product_generators(cfg, bias), pancakeFactor=5.0,
+                            stopDetectedPhotons=True, approximateNumberOfWorkItems=args.steps, keepPhotons=False, framePhotons=not args.no_series)
+    steps = common.steps_for(cfg, args.steps, seed=3).copy()
+    steps["id"] = np.arange(len(steps)) % 1000
+    p = np.zeros(1000, dtype=CV.MCPE_PARTICLE_DTYPE)
+    p["id"], p["frame"], p["timeShift"] = np.arange(1000), np.arange(1000) % 10, np.arange(1000) * 1000.0
+    for bunch in range(2):          # the first bunch allocates the pools
+        t0 = time.perf_counter()
+        if args.no_series:
+            conv.EnqueueSteps(steps, bunch)
+        else:
+            conv.EnqueueSteps(steps, bunch, particles=p)
+        r = conv.GetConversionResult()
+        wall = time.perf_counter() - t0
+    print(json.dumps({"steps": len(steps), "photons": int(steps["num"].sum()), "photon_records": len(r[1]),
+                      "frame_photons": None if r.frame_photons is None else len(r.frame_photons),
+                      "frame_photon_series": None if r.frame_photon_series is None else len(r.frame_photon_series), "wall_seconds_second_bunch": wall}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=1 << 20)
     ap.add_argument("--no-series", action="store_true")
     ap.add_argument("--merge-window", type=float, default=None, metavar="NS")
     ap.add_argument("--pmt", action="store_true")
+    ap.add_argument("--frame-photons", action="store_true")
     args = ap.parse_args()
     cfg = common.config("mie")
     g = cfg["geom"]
@@ -58,6 +82,8 @@ def main():
     bias = CV.GetIceCubeDOMAcceptance()
     if args.pmt:
         return pmt_bunch(args, cfg, bias)
+    if args.frame_photons:
+        return frame_photons_bunch(args, cfg, bias)
     conv = CV.initializeHIP(0, CV.I3CLSimSimpleGeometry.from_dict(g), cfg["med_p"], bias, common.product_generators(cfg, bias), pancakeFactor=5.0,
                             stopDetectedPhotons=True, approximateNumberOfWorkItems=args.steps, mcpeGenerator=gen, keepPhotons=False,
                             mcpeSeries=not args.no_series, mcpeMergeWindow=args.merge_window)
