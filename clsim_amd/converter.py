@@ -763,6 +763,15 @@ class I3CLSimStepToPhotonConverterHIP:
         keep, pp, n_p, masked, mp, n_m = _series_inputs(particles, masked)
         self._call("clsimhip_enqueue_steps_with_particles", steps.ctypes.data_as(C.c_void_p), len(steps), int(identifier), pp, n_p, mp, n_m)
 
+    @staticmethod
+    def _copy_records(address, count, dtype):
+        """copy of `count` records of `dtype` at `address` (a c_void_p the library filled in)"""
+        dtype = np.dtype(dtype)
+        array = np.zeros(count, dtype=dtype)
+        if count:
+            C.memmove(array.ctypes.data, address.value, count * dtype.itemsize)
+        return array
+
     def _result_mcpes(self, ptr):
         """copy of the MCPEs of the result `ptr` belongs to (None without a generator); with the MCPE series stage the tuple
         (sorted records, series table, MASKED count)"""
@@ -771,33 +780,20 @@ class I3CLSimStepToPhotonConverterHIP:
         if self._series:
             mp, mn, sp, sn, masked = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_size_t(), C.c_uint64()
             self._call("clsimhip_get_result_mcpe_series", ptr, C.byref(mp), C.byref(mn), C.byref(sp), C.byref(sn), C.byref(masked))
-            mcpes, series = np.zeros(mn.value, dtype=MCPE_DTYPE), np.zeros(sn.value, dtype=MCPE_SERIES_DTYPE)
-            if mn.value:
-                C.memmove(mcpes.ctypes.data, mp.value, mn.value * 16)
-            if sn.value:
-                C.memmove(series.ctypes.data, sp.value, sn.value * 16)
+            mcpes, series = self._copy_records(mp, mn.value, MCPE_DTYPE), self._copy_records(sp, sn.value, MCPE_SERIES_DTYPE)
             if self._merging:
                 return mcpes, series, int(masked.value), self._result_merged(ptr)
             return mcpes, series, int(masked.value)
         mp, mn = C.c_void_p(), C.c_size_t()
         self._call("clsimhip_get_result_mcpes", ptr, C.byref(mp), C.byref(mn))
-        mcpes = np.zeros(mn.value, dtype=MCPE_DTYPE)
-        if mn.value:
-            C.memmove(mcpes.ctypes.data, mp.value, mn.value * 16)
-        return mcpes
+        return self._copy_records(mp, mn.value, MCPE_DTYPE)
 
     def _result_merged(self, ptr):
         """copies of (merged records, merged series table, parents, parent ranges) of the result `ptr` belongs to"""
         gp, gn, sp, sn, pp, pn, rp = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_size_t(), C.c_void_p()
         self._call("clsimhip_get_result_mcpe_merged", ptr, C.byref(gp), C.byref(gn), C.byref(sp), C.byref(sn), C.byref(pp), C.byref(pn), C.byref(rp))
-        out = []
-        for address, count, dtype in ((gp, gn.value, MCPE_MERGED_DTYPE), (sp, sn.value, MCPE_SERIES_DTYPE), (pp, pn.value, MCPE_PARENT_DTYPE),
-                                      (rp, sn.value, MCPE_PARENT_RANGE_DTYPE)):
-            array = np.zeros(count, dtype=dtype)
-            if count:
-                C.memmove(array.ctypes.data, address.value, count * dtype.itemsize)
-            out.append(array)
-        return tuple(out)
+        return (self._copy_records(gp, gn.value, MCPE_MERGED_DTYPE), self._copy_records(sp, sn.value, MCPE_SERIES_DTYPE),
+                self._copy_records(pp, pn.value, MCPE_PARENT_DTYPE), self._copy_records(rp, sn.value, MCPE_PARENT_RANGE_DTYPE))
 
     def _result_pmt_hits(self, ptr):
         """copy of the PMT hits of the result `ptr` belongs to (None without a PMT hit generator); with the PMT series stage the
@@ -807,18 +803,10 @@ class I3CLSimStepToPhotonConverterHIP:
         if self._pmt_series:
             hp, hn, sp, sn, masked = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_size_t(), C.c_uint64()
             self._call("clsimhip_get_result_pmt_series", ptr, C.byref(hp), C.byref(hn), C.byref(sp), C.byref(sn), C.byref(masked))
-            hits, series = np.zeros(hn.value, dtype=PMT_HIT_DTYPE), np.zeros(sn.value, dtype=PMT_SERIES_DTYPE)
-            if hn.value:
-                C.memmove(hits.ctypes.data, hp.value, hn.value * 24)
-            if sn.value:
-                C.memmove(series.ctypes.data, sp.value, sn.value * 24)
-            return hits, series, int(masked.value)
+            return self._copy_records(hp, hn.value, PMT_HIT_DTYPE), self._copy_records(sp, sn.value, PMT_SERIES_DTYPE), int(masked.value)
         hp, hn = C.c_void_p(), C.c_size_t()
         self._call("clsimhip_get_result_pmt_hits", ptr, C.byref(hp), C.byref(hn))
-        hits = np.zeros(hn.value, dtype=PMT_HIT_DTYPE)
-        if hn.value:
-            C.memmove(hits.ctypes.data, hp.value, hn.value * 24)
-        return hits
+        return self._copy_records(hp, hn.value, PMT_HIT_DTYPE)
 
     def _has_handle(self):
         """a result without photon records still has a handle to release when a hit maker is attached"""
@@ -829,12 +817,7 @@ class I3CLSimStepToPhotonConverterHIP:
         without SetFramePhotons"""
         rp, rn, sp, sn, masked = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_size_t(), C.c_uint64()
         self._call("clsimhip_get_result_frame_photons", ptr, C.byref(rp), C.byref(rn), C.byref(sp), C.byref(sn), C.byref(masked))
-        records, series = np.zeros(rn.value, dtype=FRAME_PHOTON_DTYPE), np.zeros(sn.value, dtype=MCPE_SERIES_DTYPE)
-        if rn.value:
-            C.memmove(records.ctypes.data, rp.value, rn.value * 48)
-        if sn.value:
-            C.memmove(series.ctypes.data, sp.value, sn.value * 16)
-        return records, series, int(masked.value)
+        return self._copy_records(rp, rn.value, FRAME_PHOTON_DTYPE), self._copy_records(sp, sn.value, MCPE_SERIES_DTYPE), int(masked.value)
 
     def _attach_frame_photons(self, result, fp):
         if fp is not None:

@@ -307,17 +307,23 @@ void Converter::compile()
     if (series_ && !mcpe_) throw Error(CLSIMHIP_ERR_CONFIG, "MCPE series need an MCPE generator (clsimhip_set_mcpe_generator)");
     if (merging_ && !series_) throw Error(CLSIMHIP_ERR_CONFIG, "MCPE merging needs the MCPE series stage (clsimhip_set_mcpe_series)");
     if (pmt_series_ && !pmt_) throw Error(CLSIMHIP_ERR_CONFIG, "PMT series need a PMT hit generator (clsimhip_set_pmt_generator)");
-    if (mcpe_) {
-        // the generator reads IDs from the records: every DOM's pair must fit them (the host conversion reports such IDs only when a
-        // photon carries them, OpenCL.cxx:1577-1586) and must have a class (log_fatal per photon in the reference, :628-630)
+    // The stages read IDs from the records: DOM by DOM, the pair must fit them (the host conversion reports such IDs only when a
+    // photon carries them, OpenCL.cxx:1577-1586) and pass the stage's own check
+    const auto require_ids_fit_record = [&](const char *stage, auto also) {
         for (size_t i = 0; i < geometry_.string_ids.size(); ++i) {
             const int32_t sid = geometry_.string_ids[i];
             const uint32_t did = geometry_.dom_ids[i];
             if (sid < -32768 || sid > 32767 || did > 65535u)
-                throw Error(CLSIMHIP_ERR_CONFIG, "MCPE generator: string ID " + std::to_string(sid) + " / OM ID " + std::to_string(did) + " does not fit the photon record");
+                throw Error(CLSIMHIP_ERR_CONFIG, std::string(stage) + ": string ID " + std::to_string(sid) + " / OM ID " + std::to_string(did) + " does not fit the photon record");
+            also(sid, did);
+        }
+    };
+    if (mcpe_) {
+        // every DOM must have a class (log_fatal per photon in the reference, :628-630)
+        require_ids_fit_record("MCPE generator", [&](int32_t sid, uint32_t did) {
             if (!mcpe_->has_class(sid, did))
                 throw Error(CLSIMHIP_ERR_CONFIG, "No wavelength acceptance configured for OMKey(" + std::to_string(sid) + "," + std::to_string(did) + ")");
-        }
+        });
         if (history_entries_ && !keep_photons_) throw Error(CLSIMHIP_ERR_CONFIG, "photon histories need keep_photons");
         // records of a converter with another pancake factor sit at another radius: every one of them would be OFF_SURFACE
         if (mcpe_->pancake() != pancake_)
@@ -326,16 +332,11 @@ void Converter::compile()
     if (pmt_) {
         if (mcpe_) throw Error(CLSIMHIP_ERR_CONFIG, "a converter takes an MCPE generator or a PMT hit generator, not both");
         if (series_) throw Error(CLSIMHIP_ERR_CONFIG, "MCPE series are not made from PMT hits (clsimhip_set_mcpe_series with a PMT hit generator)");
-        // as for the MCPE generator: every DOM's pair must fit the records and must have a module (log_fatal per module in the
-        // reference, I3PhotonToMCHitConverterForMultiPMT.cxx:281-287)
-        for (size_t i = 0; i < geometry_.string_ids.size(); ++i) {
-            const int32_t sid = geometry_.string_ids[i];
-            const uint32_t did = geometry_.dom_ids[i];
-            if (sid < -32768 || sid > 32767 || did > 65535u)
-                throw Error(CLSIMHIP_ERR_CONFIG, "PMT hit generator: string ID " + std::to_string(sid) + " / OM ID " + std::to_string(did) + " does not fit the photon record");
+        // every DOM must have a module (log_fatal per module in the reference, I3PhotonToMCHitConverterForMultiPMT.cxx:281-287)
+        require_ids_fit_record("PMT hit generator", [&](int32_t sid, uint32_t did) {
             if (!pmt_->has_module(sid, did))
                 throw Error(CLSIMHIP_ERR_CONFIG, "No module configured for OMKey(" + std::to_string(sid) + "," + std::to_string(did) + ")");
-        }
+        });
         // records sit at the geometry's (oversized) OM radius, flattened by the pancake factor: a type made for another radius would
         // find every record OFF_SURFACE and its discs in the wrong places
         const double recorded_at = geometry_.om_radius / pancake_;
@@ -347,13 +348,8 @@ void Converter::compile()
     }
     fp_doms_.reset();
     if (frame_photons_) {
-        // the stage reads IDs from the records and files them under the geometry's DOMs: every pair must fit the record
-        for (size_t i = 0; i < geometry_.string_ids.size(); ++i) {
-            const int32_t sid = geometry_.string_ids[i];
-            const uint32_t did = geometry_.dom_ids[i];
-            if (sid < -32768 || sid > 32767 || did > 65535u)
-                throw Error(CLSIMHIP_ERR_CONFIG, "frame photons: string ID " + std::to_string(sid) + " / OM ID " + std::to_string(did) + " does not fit the photon record");
-        }
+        // (the stage files the records under the geometry's DOMs)
+        require_ids_fit_record("frame photons", [](int32_t, uint32_t) {});
         if (history_entries_ && !fp_keep_photons_) throw Error(CLSIMHIP_ERR_CONFIG, "photon histories need keep_photons");
         fp_doms_ = std::make_shared<FramePhotonDoms>(geometry_.string_ids.data(), geometry_.dom_ids.data(), geometry_.string_ids.size());
     }
@@ -540,31 +536,17 @@ void Converter::setup_device_buffers(DeviceState &D)
             sl.d_pmt_counters.alloc(4, "PMT hit counters");
             sl.h_pmt_counters.alloc(4, "pinned PMT hit counters");
         }
-        if (pmt_series_) {
-            sl.pmt_series_workspace_bytes = pmt_series_workspace_bytes(max_output_photons_, 0, 0);
-            sl.d_pmt_series_workspace.alloc(sl.pmt_series_workspace_bytes, "PMT series workspace");
-            sl.d_pmt_sorted.alloc(max_output_photons_, "sorted PMT hits");
-            sl.d_pmt_series.alloc(max_output_photons_, "PMT series table");
-            sl.d_pmt_series_counts.alloc(8, "PMT series counts");
-            sl.h_pmt_series_counts.alloc(8, "pinned PMT series counts");
-        }
+        if (pmt_series_)
+            sl.pmt_series.alloc(max_output_photons_, pmt_series_workspace_bytes(max_output_photons_, 0, 0),
+                                {"PMT series workspace", "sorted PMT hits", "PMT series table", "PMT series counts", "pinned PMT series counts"});
         if (frame_photons_) {
             if (!D.id_strings) throw Error(CLSIMHIP_ERR_CONFIG, "frame photons: the geometry has no DOM");
-            sl.fp_workspace_bytes = frame_photons_workspace_bytes(max_output_photons_, 0, 0);
-            sl.d_fp_workspace.alloc(sl.fp_workspace_bytes, "frame photons workspace");
-            sl.d_fp_out.alloc(max_output_photons_, "frame photons");
-            sl.d_fp_series.alloc(max_output_photons_, "frame photons series table");
-            sl.d_fp_counts.alloc(8, "frame photons counts");
-            sl.h_fp_counts.alloc(8, "pinned frame photons counts");
+            sl.fp.alloc(max_output_photons_, frame_photons_workspace_bytes(max_output_photons_, 0, 0),
+                        {"frame photons workspace", "frame photons", "frame photons series table", "frame photons counts", "pinned frame photons counts"});
         }
-        if (series_) {
-            sl.series_workspace_bytes = mcpe_series_workspace_bytes(max_output_photons_, 0, 0);
-            sl.d_series_workspace.alloc(sl.series_workspace_bytes, "MCPE series workspace");
-            sl.d_sorted.alloc(max_output_photons_, "sorted MCPEs");
-            sl.d_series.alloc(max_output_photons_, "MCPE series table");
-            sl.d_series_counts.alloc(8, "MCPE series counts");
-            sl.h_series_counts.alloc(8, "pinned MCPE series counts");
-        }
+        if (series_)
+            sl.series.alloc(max_output_photons_, mcpe_series_workspace_bytes(max_output_photons_, 0, 0),
+                            {"MCPE series workspace", "sorted MCPEs", "MCPE series table", "MCPE series counts", "pinned MCPE series counts"});
         if (merging_) {
             sl.merge_workspace_bytes = mcpe_merge_workspace_bytes(max_output_photons_);
             sl.d_merge_workspace.alloc(sl.merge_workspace_bytes, "MCPE merging workspace");
@@ -677,28 +659,23 @@ void Converter::enqueue_steps(const clsimhip_step *steps, size_t n, uint32_t ide
     job.pinned = step_pool_.take(n, std::max(n, std::min(max_workitems_, n + n / 4)), device_);
     if (job.pinned) std::memcpy(job.pinned.get(), steps, n * sizeof(clsimhip_step));
     else job.steps.assign(steps, steps + n);
-    if (series_ || pmt_series_) {
-        // checked and brought into the stage's form here, in the caller's thread: a bad table is the caller's error, not the worker's
-        const size_t bytes = series_ ? mcpe_series_blob_bytes(n_particles, n_masked) : pmt_series_blob_bytes(n_particles, n_masked);
-        job.bunch_pinned = bunch_pool_.take(bytes, bytes + bytes / 4, device_);
-        uint8_t *blob = job.bunch_pinned.get();
+    // the table and the mask are checked and brought into the stage's form here, in the caller's thread: a bad table is the caller's
+    // error, not the worker's
+    const auto fill = [&](BunchTable &table, size_t bytes, auto prepare) {
+        table.pinned = bunch_pool_.take(bytes, bytes + bytes / 4, device_);
+        uint8_t *blob = table.pinned.get();
         if (!blob) {
-            job.bunch_blob.resize((bytes + 15u) / 16u);
-            blob = job.bunch_blob.data()->bytes;
+            table.pageable.resize((bytes + 15u) / 16u);
+            blob = table.pageable.data()->bytes;
         }
-        job.bunch = series_ ? mcpe_->prepare_series(particles, n_particles, masked, n_masked, blob)
-                            : pmt_->prepare_series(particles, n_particles, masked, n_masked, blob);
-    }
-    if (frame_photons_) {
-        const size_t bytes = frame_photons_blob_bytes(n_particles, n_masked);
-        job.fp_bunch_pinned = bunch_pool_.take(bytes, bytes + bytes / 4, device_);
-        uint8_t *blob = job.fp_bunch_pinned.get();
-        if (!blob) {
-            job.fp_bunch_blob.resize((bytes + 15u) / 16u);
-            blob = job.fp_bunch_blob.data()->bytes;
-        }
-        job.fp_bunch = fp_doms_->prepare(particles, n_particles, masked, n_masked, blob);
-    }
+        table.bunch = prepare(blob);
+    };
+    if (series_ || pmt_series_)
+        fill(job.bunch, series_ ? mcpe_series_blob_bytes(n_particles, n_masked) : pmt_series_blob_bytes(n_particles, n_masked), [&](uint8_t *blob) {
+            return series_ ? mcpe_->prepare_series(particles, n_particles, masked, n_masked, blob) : pmt_->prepare_series(particles, n_particles, masked, n_masked, blob);
+        });
+    if (frame_photons_)
+        fill(job.fp_bunch, frame_photons_blob_bytes(n_particles, n_masked), [&](uint8_t *blob) { return fp_doms_->prepare(particles, n_particles, masked, n_masked, blob); });
     in_queue_->put(std::move(job));
 }
 
@@ -731,38 +708,29 @@ void Converter::submit(Slot &s, Job &job)
     hip_check(hipEventRecord(s.stop.get(), stream), "event");
     hip_check(hipMemcpyAsync(s.h_hit_count.get(), s.d_hit_count.get(), 4, hipMemcpyDeviceToHost, stream), "download hit counter");
     hip_check(hipMemcpyAsync(s.h_hit_count.get() + 1, P.queue + 2, 12, hipMemcpyDeviceToHost, stream), "download skipped-step and bad-record counters");
+    // A series stage, on the bunch's stream like everything here: the bunch's table from where the job brought it, a workspace that
+    // holds it, the stage's kernels (`launch`), and its counts, which stay on the device until finish() fetches them
+    const auto run_series_stage = [&](auto &buffers, BunchUpload &upload, BunchTable &table, size_t (*workspace_bytes)(size_t, size_t, size_t), const char *staging_name,
+                                      size_t counts_bytes, const char *counts_download, auto launch) {
+        const uint8_t *blob = upload.source(table, staging_name);
+        buffers.grow_workspace(workspace_bytes(max_output_photons_, table.bunch.n_particles, table.bunch.n_masked));
+        launch(blob);
+        hip_check(hipMemcpyAsync(buffers.h_counts.get(), buffers.d_counts.get(), counts_bytes, hipMemcpyDeviceToHost, stream), counts_download);
+    };
     if (mcpe_) {
         // behind assemble_hits_kernel on the bunch's stream, over the records the bunch stored (min(hit counter, capacity)); outside
         // the start / stop pair: the propagation kernel's time stays what it was
         mcpe_->convert_device(device_, s.d_photons.get(), s.d_hit_count.get(), max_output_photons_, s.d_mcpes.get(), max_output_photons_, s.d_mcpe_counters.get(), stream);
         hip_check(hipMemcpyAsync(s.h_mcpe_counters.get(), s.d_mcpe_counters.get(), 20, hipMemcpyDeviceToHost, stream), "download MCPE counters");
     }
-    if (series_) {
-        // behind the hit maker on the same stream, over the MCPEs it stored; all counts stay on the device until finish() fetches them
-        s.bunch_lease = std::move(job.bunch_pinned);
-        const uint8_t *blob = s.bunch_lease.get();
-        if (!blob) {
-            if (s.h_bunch_bytes < job.bunch.bytes) {
-                s.h_bunch.reset();
-                s.h_bunch.alloc(job.bunch.bytes, "pinned MCPE series bunch");
-                s.h_bunch_bytes = job.bunch.bytes;
-            }
-            std::memcpy(s.h_bunch.get(), job.bunch_blob.data(), job.bunch.bytes);
-            blob = s.h_bunch.get();
-        }
-        const size_t need = mcpe_series_workspace_bytes(max_output_photons_, job.bunch.n_particles, job.bunch.n_masked) + 64;
-        if (s.series_workspace_bytes < need) {          // (the slot is free: nothing on the device uses its workspace)
-            s.d_series_workspace.reset();
-            s.d_series_workspace.alloc(need + need / 4, "MCPE series workspace");
-            s.series_workspace_bytes = need + need / 4;
-        }
-        mcpe_->series_device_prepared(device_, s.d_mcpes.get(), s.d_mcpe_counters.get(), max_output_photons_, job.bunch, blob, s.d_sorted.get(),
-                                      s.d_series.get(), s.d_series_counts.get(), s.d_series_workspace.get(), s.series_workspace_bytes, stream);
-        hip_check(hipMemcpyAsync(s.h_series_counts.get(), s.d_series_counts.get(), 20, hipMemcpyDeviceToHost, stream), "download MCPE series counts");
-    }
+    if (series_)        // behind the hit maker, over the MCPEs it stored
+        run_series_stage(s.series, s.bunch, job.bunch, mcpe_series_workspace_bytes, "pinned MCPE series bunch", 20, "download MCPE series counts", [&](const uint8_t *blob) {
+            mcpe_->series_device_prepared(device_, s.d_mcpes.get(), s.d_mcpe_counters.get(), max_output_photons_, job.bunch.bunch, blob, s.series.out.get(),
+                                          s.series.series.get(), s.series.d_counts.get(), s.series.workspace.get(), s.series.workspace_bytes, stream);
+        });
     if (merging_) {
         // behind the series stage on the same stream, over the records and the table it left; reads its sizes from the stage's counts
-        mcpe_merge_device(device_, s.d_sorted.get(), s.d_series.get(), s.d_series_counts.get(), max_output_photons_, merge_window_, s.d_merged.get(),
+        mcpe_merge_device(device_, s.series.out.get(), s.series.series.get(), s.series.d_counts.get(), max_output_photons_, merge_window_, s.d_merged.get(),
                           s.d_merged_series.get(), s.d_parents.get(), s.d_ranges.get(), s.d_merge_counts.get(), s.d_merge_workspace.get(),
                           s.merge_workspace_bytes, stream);
         hip_check(hipMemcpyAsync(s.h_merge_counts.get(), s.d_merge_counts.get(), 8, hipMemcpyDeviceToHost, stream), "download MCPE merging counts");
@@ -772,53 +740,26 @@ void Converter::submit(Slot &s, Job &job)
         pmt_->convert_device(device_, s.d_photons.get(), s.d_hit_count.get(), max_output_photons_, s.d_pmt_hits.get(), max_output_photons_, s.d_pmt_counters.get(), stream);
         hip_check(hipMemcpyAsync(s.h_pmt_counters.get(), s.d_pmt_counters.get(), 16, hipMemcpyDeviceToHost, stream), "download PMT hit counters");
     }
-    if (pmt_series_) {
-        // behind the PMT hit maker on the same stream, over the hits it stored; all counts stay on the device until finish() fetches them
-        s.bunch_lease = std::move(job.bunch_pinned);
-        const uint8_t *blob = s.bunch_lease.get();
-        if (!blob) {
-            if (s.h_bunch_bytes < job.bunch.bytes) {
-                s.h_bunch.reset();
-                s.h_bunch.alloc(job.bunch.bytes, "pinned PMT series bunch");
-                s.h_bunch_bytes = job.bunch.bytes;
-            }
-            std::memcpy(s.h_bunch.get(), job.bunch_blob.data(), job.bunch.bytes);
-            blob = s.h_bunch.get();
-        }
-        const size_t need = pmt_series_workspace_bytes(max_output_photons_, job.bunch.n_particles, job.bunch.n_masked) + 64;
-        if (s.pmt_series_workspace_bytes < need) {      // (the slot is free: nothing on the device uses its workspace)
-            s.d_pmt_series_workspace.reset();
-            s.d_pmt_series_workspace.alloc(need + need / 4, "PMT series workspace");
-            s.pmt_series_workspace_bytes = need + need / 4;
-        }
-        pmt_->series_device_prepared(device_, s.d_pmt_hits.get(), s.d_pmt_counters.get(), max_output_photons_, job.bunch, blob, s.d_pmt_sorted.get(),
-                                     s.d_pmt_series.get(), s.d_pmt_series_counts.get(), s.d_pmt_series_workspace.get(), s.pmt_series_workspace_bytes, stream);
-        hip_check(hipMemcpyAsync(s.h_pmt_series_counts.get(), s.d_pmt_series_counts.get(), 20, hipMemcpyDeviceToHost, stream), "download PMT series counts");
-    }
-    if (frame_photons_) {
-        // behind assemble_hits_kernel on the bunch's stream, over the records the bunch stored; beside whatever hit maker ran above
-        s.fp_bunch_lease = std::move(job.fp_bunch_pinned);
-        const uint8_t *blob = s.fp_bunch_lease.get();
-        if (!blob) {
-            if (s.h_fp_bunch_bytes < job.fp_bunch.bytes) {
-                s.h_fp_bunch.reset();
-                s.h_fp_bunch.alloc(job.fp_bunch.bytes, "pinned frame photons bunch");
-                s.h_fp_bunch_bytes = job.fp_bunch.bytes;
-            }
-            std::memcpy(s.h_fp_bunch.get(), job.fp_bunch_blob.data(), job.fp_bunch.bytes);
-            blob = s.h_fp_bunch.get();
-        }
-        const size_t need = frame_photons_workspace_bytes(max_output_photons_, job.fp_bunch.n_particles, job.fp_bunch.n_masked) + 64;
-        if (s.fp_workspace_bytes < need) {              // (the slot is free: nothing on the device uses its workspace)
-            s.d_fp_workspace.reset();
-            s.d_fp_workspace.alloc(need + need / 4, "frame photons workspace");
-            s.fp_workspace_bytes = need + need / 4;
-        }
-        fp_doms_->device_prepared(device_, s.d_photons.get(), s.d_hit_count.get(), max_output_photons_, job.fp_bunch, blob, s.d_fp_out.get(), s.d_fp_series.get(),
-                                  s.d_fp_counts.get(), s.d_fp_workspace.get(), s.fp_workspace_bytes, stream);
-        hip_check(hipMemcpyAsync(s.h_fp_counts.get(), s.d_fp_counts.get(), 24, hipMemcpyDeviceToHost, stream), "download frame photons counts");
-    }
+    if (pmt_series_)    // behind the PMT hit maker, over the hits it stored
+        run_series_stage(s.pmt_series, s.bunch, job.bunch, pmt_series_workspace_bytes, "pinned PMT series bunch", 20, "download PMT series counts", [&](const uint8_t *blob) {
+            pmt_->series_device_prepared(device_, s.d_pmt_hits.get(), s.d_pmt_counters.get(), max_output_photons_, job.bunch.bunch, blob, s.pmt_series.out.get(),
+                                         s.pmt_series.series.get(), s.pmt_series.d_counts.get(), s.pmt_series.workspace.get(), s.pmt_series.workspace_bytes, stream);
+        });
+    if (frame_photons_) // behind assemble_hits_kernel, over the records the bunch stored; beside whatever hit maker ran above
+        run_series_stage(s.fp, s.fp_bunch, job.fp_bunch, frame_photons_workspace_bytes, "pinned frame photons bunch", 24, "download frame photons counts", [&](const uint8_t *blob) {
+            fp_doms_->device_prepared(device_, s.d_photons.get(), s.d_hit_count.get(), max_output_photons_, job.fp_bunch.bunch, blob, s.fp.out.get(), s.fp.series.get(),
+                                      s.fp.d_counts.get(), s.fp.workspace.get(), s.fp.workspace_bytes, stream);
+        });
     hip_check(hipEventRecord(s.counted.get(), stream), "event");
+}
+
+template <class T>
+T *Converter::download(HostRecords<T> &to, PinnedPool<T> &pool, const void *d_from, size_t n, size_t min_records, const char *what)
+{
+    if (!n) return nullptr;
+    T *where = to.take(pool, n, result_capacity(n, min_records), device_);
+    hip_check(hipMemcpyAsync(where, d_from, n * sizeof(T), hipMemcpyDeviceToHost, dev_.copy_stream.get()), what);
+    return where;
 }
 
 // OpenCL.cxx:994-1086: wait for the bunch, download and convert its photons (on the copy stream, so that the
@@ -843,6 +784,19 @@ void Converter::finish(Slot &s, std::chrono::steady_clock::time_point &last_done
     // thread: round 2 zero-filled a vector per result, copied the download into it and converted indices one by one -- 0.4 s
     // per bunch of 8.4 M photons in the reference's benchmark, the device idle 80 % of the time).  With every pool buffer in
     // the caller's hands the records go into a plain vector.
+    // A series stage's counts: kept, series, UNKNOWN_PARTICLE, MASKED, a module the stage does not have, and with `ties` TIE_OVERFLOW.
+    // The fatal ones end the bunch with the stage's words for them (log_fatal in the reference, I3CLSimClientModule.cxx:388-390); else
+    // the records and the series to download
+    struct FatalWords { const char *stage, *records, *whose; bool ties; };
+    struct Kept { uint32_t records, series; };
+    const auto series_counts = [&](const uint32_t *c, const FatalWords &w) {
+        if ((c[2] | c[4] | (w.ties ? c[5] : 0u)) != 0u)
+            throw Error(CLSIMHIP_ERR_DEVICE, std::string(w.stage) + ", bunch " + std::to_string(s.id) + ": " + std::to_string(c[2]) + " " + w.records +
+                                                 " of particles the bunch's particle table does not have, " + std::to_string(c[4]) + " at " + w.whose + " does not have" +
+                                                 (w.ties ? ", " + std::to_string(c[5]) + " in runs of colliding records beyond the bound" : std::string()));
+        const uint32_t kept = std::min(c[0], max_output_photons_);
+        return Kept{kept, std::min(c[1], kept)};
+    };
     uint32_t n_mcpes = 0;
     if (mcpe_) {
         const uint32_t *mc = s.h_mcpe_counters.get();
@@ -854,13 +808,8 @@ void Converter::finish(Slot &s, std::chrono::steady_clock::time_point &last_done
     }
     uint32_t n_series = 0;
     if (series_) {
-        const uint32_t *sc = s.h_series_counts.get();       // kept, series, UNKNOWN_PARTICLE, MASKED, UNKNOWN_DOM
-        if ((sc[2] | sc[4]) != 0u)                          // log_fatal in the reference (I3CLSimClientModule.cxx:388-390)
-            throw Error(CLSIMHIP_ERR_DEVICE, "MCPE series, bunch " + std::to_string(s.id) + ": " + std::to_string(sc[2]) +
-                                                 " MCPEs of particles the bunch's particle table does not have, " + std::to_string(sc[4]) +
-                                                 " at DOMs the generator does not have");
-        n_mcpes = std::min(sc[0], max_output_photons_);
-        n_series = std::min(sc[1], n_mcpes);
+        const Kept k = series_counts(s.series.h_counts.get(), {"MCPE series", "MCPEs", "DOMs the generator", false});
+        n_mcpes = k.records; n_series = k.series;
     }
     uint32_t n_pmt_hits = 0;
     if (pmt_) {
@@ -874,35 +823,19 @@ void Converter::finish(Slot &s, std::chrono::steady_clock::time_point &last_done
     }
     uint32_t n_pmt_series = 0;
     if (pmt_series_) {
-        const uint32_t *sc = s.h_pmt_series_counts.get();   // kept, series, UNKNOWN_PARTICLE, MASKED, UNKNOWN_CHANNEL
-        if ((sc[2] | sc[4]) != 0u)                          // log_fatal in the reference (I3CLSimClientModule.cxx:388-390)
-            throw Error(CLSIMHIP_ERR_DEVICE, "PMT series, bunch " + std::to_string(s.id) + ": " + std::to_string(sc[2]) +
-                                                 " hits of particles the bunch's particle table does not have, " + std::to_string(sc[4]) +
-                                                 " at modules or PMTs the generator does not have");
-        n_pmt_hits = std::min(sc[0], max_output_photons_);
-        n_pmt_series = std::min(sc[1], n_pmt_hits);
+        const Kept k = series_counts(s.pmt_series.h_counts.get(), {"PMT series", "hits", "modules or PMTs the generator", false});
+        n_pmt_hits = k.records; n_pmt_series = k.series;
     }
-    uint32_t n_fp = 0, n_fp_series = 0;
-    if (frame_photons_) {
-        const uint32_t *fc = s.h_fp_counts.get();           // kept, series, UNKNOWN_PARTICLE, MASKED, UNKNOWN_DOM, TIE_OVERFLOW
-        if ((fc[2] | fc[4] | fc[5]) != 0u)                  // log_fatal in the reference (I3CLSimClientModule.cxx:388-390)
-            throw Error(CLSIMHIP_ERR_DEVICE, "frame photons, bunch " + std::to_string(s.id) + ": " + std::to_string(fc[2]) +
-                                                 " photons of particles the bunch's particle table does not have, " + std::to_string(fc[4]) +
-                                                 " at DOMs the geometry does not have, " + std::to_string(fc[5]) + " in runs of colliding records beyond the bound");
-        n_fp = std::min(fc[0], max_output_photons_);
-        n_fp_series = std::min(fc[1], n_fp);
-    }
+    const Kept fp = frame_photons_ ? series_counts(s.fp.h_counts.get(), {"frame photons", "photons", "DOMs the geometry", true}) : Kept{0u, 0u};
+    const uint32_t n_fp = fp.records, n_fp_series = fp.series;
     const uint32_t detected = hits;
     if (!carries_photons()) hits = 0;                   // the records stay on the device
+    // (a failure from here on drops r, whose pool buffers go back to their pools)
     Result r;
-    r.count = hits;
-    std::unique_ptr<std::vector<clsimhip_photon>> photons;
-    clsimhip_photon *where = nullptr;
+    const size_t min_records = s.result_min_records;
+    clsimhip_photon *where = download(r.photons, result_pool_, s.d_photons.get(), hits, min_records, "download photons");
     if (hits) {
-        r.pinned = result_pool_.take(hits, result_capacity(hits, s.result_min_records), device_);
-        if (r.pinned) {
-            where = r.pinned.get();
-        } else {
+        if (!r.photons.pinned) {
             // every pool buffer is with the caller (or the host refuses to page-lock more): the download goes into pageable memory,
             // which is correct and slower -- said once, because nothing else shows it
             static std::once_flag noted;
@@ -910,94 +843,47 @@ void Converter::finish(Slot &s, std::chrono::steady_clock::time_point &last_done
                 std::fprintf(stderr, "clsimhip: every page-locked result buffer is in the caller's hands (release them with "
                                      "clsimhip_release_result); photons are downloaded into pageable memory until one is free\n");
             });
-            photons.reset(new std::vector<clsimhip_photon>(hits));
-            where = photons->data();
         }
-        // (a failure from here on drops r, whose pool buffers go back to their pools)
-        hip_check(hipMemcpyAsync(where, s.d_photons.get(), static_cast<size_t>(hits) * sizeof(DevPhoton), hipMemcpyDeviceToHost, copy_stream), "download photons");
         hip_check(hipStreamSynchronize(copy_stream), "download photons");
         if (!dev_.id_strings) replace_indices(where, hits);      // OpenCL.cxx:1604-1619 does this on the caller thread
     }
+    // every stage: its records, behind them its series table, one wait for both
     if (mcpe_) {
-        r.mcpe_count = n_mcpes;
-        if (n_mcpes) {
-            r.mcpe_pinned = mcpe_pool_.take(n_mcpes, result_capacity(n_mcpes, s.result_min_records), device_);
-            clsimhip_mcpe *to = r.mcpe_pinned.get();
-            if (!to) { r.mcpes.reset(new std::vector<clsimhip_mcpe>(n_mcpes)); to = r.mcpes->data(); }
-            const clsimhip_mcpe *from = series_ ? s.d_sorted.get() : s.d_mcpes.get();
-            hip_check(hipMemcpyAsync(to, from, static_cast<size_t>(n_mcpes) * sizeof(clsimhip_mcpe), hipMemcpyDeviceToHost, copy_stream), "download MCPEs");
-            if (n_series) {
-                r.series_pinned = series_pool_.take(n_series, result_capacity(n_series, s.result_min_records), device_);
-                clsimhip_mcpe_series *table = r.series_pinned.get();
-                if (!table) { r.series.reset(new std::vector<clsimhip_mcpe_series>(n_series)); table = r.series->data(); }
-                hip_check(hipMemcpyAsync(table, s.d_series.get(), static_cast<size_t>(n_series) * sizeof(clsimhip_mcpe_series), hipMemcpyDeviceToHost, copy_stream),
-                          "download MCPE series table");
-            }
-            if (merging_ && n_series) {
-                const uint32_t n_merged = std::min(s.h_merge_counts.get()[0], n_mcpes), n_parents = std::min(s.h_merge_counts.get()[1], n_mcpes);
-                const size_t at_series = static_cast<size_t>(n_merged) * sizeof(clsimhip_mcpe_merged);
-                const size_t at_parents = at_series + static_cast<size_t>(n_series) * sizeof(clsimhip_mcpe_series);
-                const size_t at_ranges = at_parents + static_cast<size_t>(n_parents) * sizeof(clsimhip_mcpe_parent);
-                const size_t bytes = at_ranges + static_cast<size_t>(n_series) * sizeof(clsimhip_mcpe_parent_range);
-                r.merge_pinned = merge_pool_.take(bytes, (bytes + bytes / 4 + 4095) / 4096 * 4096, device_);
-                uint8_t *blob = r.merge_pinned.get();
-                if (!blob) { r.merge_blob.reset(new std::vector<uint64_t>(bytes / 8)); blob = reinterpret_cast<uint8_t *>(r.merge_blob->data()); }
-                hip_check(hipMemcpyAsync(blob, s.d_merged.get(), at_series, hipMemcpyDeviceToHost, copy_stream), "download merged MCPEs");
-                hip_check(hipMemcpyAsync(blob + at_series, s.d_merged_series.get(), at_parents - at_series, hipMemcpyDeviceToHost, copy_stream), "download merged MCPE series table");
-                hip_check(hipMemcpyAsync(blob + at_parents, s.d_parents.get(), at_ranges - at_parents, hipMemcpyDeviceToHost, copy_stream), "download MCPE parents");
-                hip_check(hipMemcpyAsync(blob + at_ranges, s.d_ranges.get(), bytes - at_ranges, hipMemcpyDeviceToHost, copy_stream), "download MCPE parent ranges");
-                r.merged_count = n_merged;
-                r.parent_count = n_parents;
-            }
-            hip_check(hipStreamSynchronize(copy_stream), "download MCPEs");
+        download(r.mcpes, mcpe_pool_, series_ ? s.series.out.get() : s.d_mcpes.get(), n_mcpes, min_records, "download MCPEs");
+        download(r.series, series_pool_, s.series.series.get(), n_series, min_records, "download MCPE series table");
+        if (merging_ && n_series) {
+            const uint32_t n_merged = std::min(s.h_merge_counts.get()[0], n_mcpes), n_parents = std::min(s.h_merge_counts.get()[1], n_mcpes);
+            const size_t at_series = static_cast<size_t>(n_merged) * sizeof(clsimhip_mcpe_merged);
+            const size_t at_parents = at_series + static_cast<size_t>(n_series) * sizeof(clsimhip_mcpe_series);
+            const size_t at_ranges = at_parents + static_cast<size_t>(n_parents) * sizeof(clsimhip_mcpe_parent);
+            const size_t bytes = at_ranges + static_cast<size_t>(n_series) * sizeof(clsimhip_mcpe_parent_range);
+            r.merge_pinned = merge_pool_.take(bytes, (bytes + bytes / 4 + 4095) / 4096 * 4096, device_);
+            uint8_t *blob = r.merge_pinned.get();
+            if (!blob) { r.merge_blob.reset(new std::vector<uint64_t>(bytes / 8)); blob = reinterpret_cast<uint8_t *>(r.merge_blob->data()); }
+            hip_check(hipMemcpyAsync(blob, s.d_merged.get(), at_series, hipMemcpyDeviceToHost, copy_stream), "download merged MCPEs");
+            hip_check(hipMemcpyAsync(blob + at_series, s.d_merged_series.get(), at_parents - at_series, hipMemcpyDeviceToHost, copy_stream), "download merged MCPE series table");
+            hip_check(hipMemcpyAsync(blob + at_parents, s.d_parents.get(), at_ranges - at_parents, hipMemcpyDeviceToHost, copy_stream), "download MCPE parents");
+            hip_check(hipMemcpyAsync(blob + at_ranges, s.d_ranges.get(), bytes - at_ranges, hipMemcpyDeviceToHost, copy_stream), "download MCPE parent ranges");
+            r.merged_count = n_merged;
+            r.parent_count = n_parents;
         }
-        r.series_count = n_series;
-        if (series_) r.masked = s.h_series_counts.get()[3];
-        if (!hits) r.handle.reset(new clsimhip_photon());
+        if (n_mcpes) hip_check(hipStreamSynchronize(copy_stream), "download MCPEs");
+        if (series_) r.masked = s.series.h_counts.get()[3];
     }
     if (pmt_) {
-        r.pmt_count = n_pmt_hits;
-        if (n_pmt_hits) {
-            r.pmt_pinned = pmt_pool_.take(n_pmt_hits, result_capacity(n_pmt_hits, s.result_min_records), device_);
-            clsimhip_pmt_hit *to = r.pmt_pinned.get();
-            if (!to) { r.pmt_hits.reset(new std::vector<clsimhip_pmt_hit>(n_pmt_hits)); to = r.pmt_hits->data(); }
-            const clsimhip_pmt_hit *from = pmt_series_ ? s.d_pmt_sorted.get() : s.d_pmt_hits.get();
-            hip_check(hipMemcpyAsync(to, from, static_cast<size_t>(n_pmt_hits) * sizeof(clsimhip_pmt_hit), hipMemcpyDeviceToHost, copy_stream),
-                      "download PMT hits");
-            if (n_pmt_series) {
-                r.pmt_series_pinned = pmt_series_pool_.take(n_pmt_series, result_capacity(n_pmt_series, s.result_min_records), device_);
-                clsimhip_pmt_series *table = r.pmt_series_pinned.get();
-                if (!table) { r.pmt_series.reset(new std::vector<clsimhip_pmt_series>(n_pmt_series)); table = r.pmt_series->data(); }
-                hip_check(hipMemcpyAsync(table, s.d_pmt_series.get(), static_cast<size_t>(n_pmt_series) * sizeof(clsimhip_pmt_series), hipMemcpyDeviceToHost,
-                                         copy_stream), "download PMT series table");
-            }
-            hip_check(hipStreamSynchronize(copy_stream), "download PMT hits");
-        }
-        r.pmt_series_count = n_pmt_series;
-        if (pmt_series_) r.masked = s.h_pmt_series_counts.get()[3];
-        if (!hits && !r.handle) r.handle.reset(new clsimhip_photon());
+        download(r.pmt_hits, pmt_pool_, pmt_series_ ? s.pmt_series.out.get() : s.d_pmt_hits.get(), n_pmt_hits, min_records, "download PMT hits");
+        download(r.pmt_series, pmt_series_pool_, s.pmt_series.series.get(), n_pmt_series, min_records, "download PMT series table");
+        if (n_pmt_hits) hip_check(hipStreamSynchronize(copy_stream), "download PMT hits");
+        if (pmt_series_) r.pmt_masked = s.pmt_series.h_counts.get()[3];
     }
     if (frame_photons_) {
-        r.fp_count = n_fp;
-        if (n_fp) {
-            r.fp_pinned = fp_pool_.take(n_fp, result_capacity(n_fp, s.result_min_records), device_);
-            clsimhip_frame_photon *to = r.fp_pinned.get();
-            if (!to) { r.fp_records.reset(new std::vector<clsimhip_frame_photon>(n_fp)); to = r.fp_records->data(); }
-            hip_check(hipMemcpyAsync(to, s.d_fp_out.get(), static_cast<size_t>(n_fp) * sizeof(clsimhip_frame_photon), hipMemcpyDeviceToHost, copy_stream),
-                      "download frame photons");
-            if (n_fp_series) {
-                r.fp_series_pinned = fp_series_pool_.take(n_fp_series, result_capacity(n_fp_series, s.result_min_records), device_);
-                clsimhip_mcpe_series *table = r.fp_series_pinned.get();
-                if (!table) { r.fp_series.reset(new std::vector<clsimhip_mcpe_series>(n_fp_series)); table = r.fp_series->data(); }
-                hip_check(hipMemcpyAsync(table, s.d_fp_series.get(), static_cast<size_t>(n_fp_series) * sizeof(clsimhip_mcpe_series), hipMemcpyDeviceToHost,
-                                         copy_stream), "download frame photons series table");
-            }
-            hip_check(hipStreamSynchronize(copy_stream), "download frame photons");
-        }
-        r.fp_series_count = n_fp_series;
-        r.fp_masked = s.h_fp_counts.get()[3];
-        if (!hits && !r.handle) r.handle.reset(new clsimhip_photon());
+        download(r.fp_records, fp_pool_, s.fp.out.get(), n_fp, min_records, "download frame photons");
+        download(r.fp_series, fp_series_pool_, s.fp.series.get(), n_fp_series, min_records, "download frame photons series table");
+        if (n_fp) hip_check(hipStreamSynchronize(copy_stream), "download frame photons");
+        r.fp_masked = s.fp.h_counts.get()[3];
     }
+    // a result with no photon records but a stage attached is known by a record of its own
+    if (!hits && (mcpe_ || pmt_ || frame_photons_)) r.handle.reset(new clsimhip_photon());
     std::unique_ptr<std::vector<float>> histories;
     if (hits && history_entries_) {
         // ConvertPhotonHistories (OpenCL.cxx:940-989): unroll each ring into forward order
@@ -1031,7 +917,6 @@ void Converter::finish(Slot &s, std::chrono::steady_clock::time_point &last_done
     first = false;
     last_done = now;
     r.id = s.id;
-    r.photons = std::move(photons);
     r.histories = std::move(histories);
     out_queue_->put(std::move(r));
 }
@@ -1101,9 +986,9 @@ void Converter::get_result(uint32_t *identifier, const clsimhip_photon **photons
         throw Error(CLSIMHIP_ERR_STATE, "converter is shutting down");
     }
     *identifier = r.id;
-    *n = r.count;
+    *n = r.photons.count;
     static const clsimhip_photon empty_sentinel{};
-    const clsimhip_photon *key = r.count ? r.data() : r.handle.get();
+    const clsimhip_photon *key = r.photons.count ? r.photons.data() : r.handle.get();
     *photons = key ? key : &empty_sentinel;
     if (key) {
         std::lock_guard<std::mutex> lk(results_mutex_);
@@ -1126,86 +1011,66 @@ void Converter::result_histories(const clsimhip_photon *photons, const float **h
     if (it->second.histories) *histories = it->second.histories->data();
 }
 
-void Converter::result_mcpes(const clsimhip_photon *photons, const clsimhip_mcpe **mcpes, size_t *n)
+template <class T>
+void Converter::result_records(const clsimhip_photon *photons, bool on, HostRecords<T> Result::*payload, const T **records, size_t *n)
 {
     need_init();
-    if (!mcpes || !n) throw Error(CLSIMHIP_ERR_ARGUMENT, "output pointers are (null)");
-    *mcpes = nullptr;
+    if (!records || !n) throw Error(CLSIMHIP_ERR_ARGUMENT, "output pointers are (null)");
+    *records = nullptr;
     *n = 0;
-    if (!mcpe_) return;
+    if (!on) return;
     std::lock_guard<std::mutex> lk(results_mutex_);
     auto it = handed_out_.find(photons);
     if (it == handed_out_.end()) throw Error(CLSIMHIP_ERR_ARGUMENT, "not a result handed out by GetConversionResult (or already released)");
-    *n = it->second.mcpe_count;
-    if (it->second.mcpe_count) *mcpes = it->second.mcpe_data();
+    (it->second.*payload).get(records, n);
 }
 
-void Converter::result_pmt_hits(const clsimhip_photon *photons, const clsimhip_pmt_hit **hits, size_t *n)
-{
-    need_init();
-    if (!hits || !n) throw Error(CLSIMHIP_ERR_ARGUMENT, "output pointers are (null)");
-    *hits = nullptr;
-    *n = 0;
-    if (!pmt_) return;
-    std::lock_guard<std::mutex> lk(results_mutex_);
-    auto it = handed_out_.find(photons);
-    if (it == handed_out_.end()) throw Error(CLSIMHIP_ERR_ARGUMENT, "not a result handed out by GetConversionResult (or already released)");
-    *n = it->second.pmt_count;
-    if (it->second.pmt_count) *hits = it->second.pmt_data();
-}
-
-void Converter::result_pmt_series(const clsimhip_photon *photons, const clsimhip_pmt_hit **hits, size_t *n, const clsimhip_pmt_series **series, size_t *n_series,
-                                  uint64_t *n_masked)
-{
-    need_init();
-    if (!hits || !n || !series || !n_series) throw Error(CLSIMHIP_ERR_ARGUMENT, "output pointers are (null)");
-    if (!pmt_series_) throw Error(CLSIMHIP_ERR_STATE, "the PMT series stage is off (clsimhip_set_pmt_series)");
-    *hits = nullptr; *series = nullptr;
-    *n = 0; *n_series = 0;
-    std::lock_guard<std::mutex> lk(results_mutex_);
-    auto it = handed_out_.find(photons);
-    if (it == handed_out_.end()) throw Error(CLSIMHIP_ERR_ARGUMENT, "not a result handed out by GetConversionResult (or already released)");
-    *n = it->second.pmt_count;
-    *n_series = it->second.pmt_series_count;
-    if (it->second.pmt_count) *hits = it->second.pmt_data();
-    if (it->second.pmt_series_count) *series = it->second.pmt_series_data();
-    if (n_masked) *n_masked = it->second.masked;
-}
-
-void Converter::result_frame_photons(const clsimhip_photon *photons, const clsimhip_frame_photon **records, size_t *n, const clsimhip_mcpe_series **series,
-                                     size_t *n_series, uint64_t *n_masked)
+template <class Rec, class Ser>
+void Converter::result_series(const clsimhip_photon *photons, bool on, const char *off_text, HostRecords<Rec> Result::*payload, HostRecords<Ser> Result::*table,
+                              uint64_t Result::*masked, const Rec **records, size_t *n, const Ser **series, size_t *n_series, uint64_t *n_masked)
 {
     need_init();
     if (!records || !n || !series || !n_series) throw Error(CLSIMHIP_ERR_ARGUMENT, "output pointers are (null)");
-    if (!frame_photons_) throw Error(CLSIMHIP_ERR_STATE, "the frame photons stage is off (clsimhip_set_frame_photons)");
+    if (!on) throw Error(CLSIMHIP_ERR_STATE, off_text);
     *records = nullptr; *series = nullptr;
     *n = 0; *n_series = 0;
     std::lock_guard<std::mutex> lk(results_mutex_);
     auto it = handed_out_.find(photons);
     if (it == handed_out_.end()) throw Error(CLSIMHIP_ERR_ARGUMENT, "not a result handed out by GetConversionResult (or already released)");
-    *n = it->second.fp_count;
-    *n_series = it->second.fp_series_count;
-    if (it->second.fp_count) *records = it->second.fp_data();
-    if (it->second.fp_series_count) *series = it->second.fp_series_data();
-    if (n_masked) *n_masked = it->second.fp_masked;
+    (it->second.*payload).get(records, n);
+    (it->second.*table).get(series, n_series);
+    if (n_masked) *n_masked = it->second.*masked;
+}
+
+void Converter::result_mcpes(const clsimhip_photon *photons, const clsimhip_mcpe **mcpes, size_t *n)
+{
+    result_records(photons, mcpe_ != nullptr, &Result::mcpes, mcpes, n);
+}
+
+void Converter::result_pmt_hits(const clsimhip_photon *photons, const clsimhip_pmt_hit **hits, size_t *n)
+{
+    result_records(photons, pmt_ != nullptr, &Result::pmt_hits, hits, n);
 }
 
 void Converter::result_mcpe_series(const clsimhip_photon *photons, const clsimhip_mcpe **mcpes, size_t *n, const clsimhip_mcpe_series **series, size_t *n_series,
                                    uint64_t *n_masked)
 {
-    need_init();
-    if (!mcpes || !n || !series || !n_series) throw Error(CLSIMHIP_ERR_ARGUMENT, "output pointers are (null)");
-    if (!series_) throw Error(CLSIMHIP_ERR_STATE, "the MCPE series stage is off (clsimhip_set_mcpe_series)");
-    *mcpes = nullptr; *series = nullptr;
-    *n = 0; *n_series = 0;
-    std::lock_guard<std::mutex> lk(results_mutex_);
-    auto it = handed_out_.find(photons);
-    if (it == handed_out_.end()) throw Error(CLSIMHIP_ERR_ARGUMENT, "not a result handed out by GetConversionResult (or already released)");
-    *n = it->second.mcpe_count;
-    *n_series = it->second.series_count;
-    if (it->second.mcpe_count) *mcpes = it->second.mcpe_data();
-    if (it->second.series_count) *series = it->second.series_data();
-    if (n_masked) *n_masked = it->second.masked;
+    result_series(photons, series_, "the MCPE series stage is off (clsimhip_set_mcpe_series)", &Result::mcpes, &Result::series, &Result::masked, mcpes, n, series,
+                  n_series, n_masked);
+}
+
+void Converter::result_pmt_series(const clsimhip_photon *photons, const clsimhip_pmt_hit **hits, size_t *n, const clsimhip_pmt_series **series, size_t *n_series,
+                                  uint64_t *n_masked)
+{
+    result_series(photons, pmt_series_, "the PMT series stage is off (clsimhip_set_pmt_series)", &Result::pmt_hits, &Result::pmt_series, &Result::pmt_masked, hits, n,
+                  series, n_series, n_masked);
+}
+
+void Converter::result_frame_photons(const clsimhip_photon *photons, const clsimhip_frame_photon **records, size_t *n, const clsimhip_mcpe_series **series,
+                                     size_t *n_series, uint64_t *n_masked)
+{
+    result_series(photons, frame_photons_, "the frame photons stage is off (clsimhip_set_frame_photons)", &Result::fp_records, &Result::fp_series, &Result::fp_masked,
+                  records, n, series, n_series, n_masked);
 }
 
 void Converter::set_mcpe_merging(bool on, double window)
@@ -1232,9 +1097,9 @@ void Converter::result_mcpe_merged(const clsimhip_photon *photons, const clsimhi
     const uint8_t *blob = r.merge_data();
     if (!blob) return;
     const size_t at_series = r.merged_count * sizeof(clsimhip_mcpe_merged);
-    const size_t at_parents = at_series + r.series_count * sizeof(clsimhip_mcpe_series);
+    const size_t at_parents = at_series + r.series.count * sizeof(clsimhip_mcpe_series);
     const size_t at_ranges = at_parents + r.parent_count * sizeof(clsimhip_mcpe_parent);
-    *n_merged = r.merged_count; *n_series = r.series_count; *n_parents = r.parent_count;
+    *n_merged = r.merged_count; *n_series = r.series.count; *n_parents = r.parent_count;
     *merged = reinterpret_cast<const clsimhip_mcpe_merged *>(blob);
     *series = reinterpret_cast<const clsimhip_mcpe_series *>(blob + at_series);
     *parents = reinterpret_cast<const clsimhip_mcpe_parent *>(blob + at_parents);

@@ -9,6 +9,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
+#include <cstring>
 #include <deque>
 #include <memory>
 #include <mutex>
@@ -233,6 +234,27 @@ private:
     bool noticed_ = false;
 };
 
+// Records of a result on the host: in a buffer of their pool, which the download lands in and the caller reads until the result is
+// released, or -- every pool buffer being out -- in a vector of their own
+template <class T>
+struct HostRecords {
+    typename PinnedPool<T>::Lease pinned;
+    std::unique_ptr<std::vector<T>> pageable;
+    size_t count = 0;
+    const T *data() const { return pinned ? pinned.get() : (pageable ? pageable->data() : nullptr); }
+    // room for n > 0 records: where to download them to
+    T *take(PinnedPool<T> &pool, size_t n, size_t new_capacity, int device)
+    {
+        count = n;
+        pinned = pool.take(n, new_capacity, device);
+        if (pinned) return pinned.get();
+        pageable.reset(new std::vector<T>(n));
+        return pageable->data();
+    }
+    // what a result_* call hands out
+    void get(const T **records, size_t *n) const { *n = count; *records = count ? data() : nullptr; }
+};
+
 // What a launch is tuned by ("kernel" ... "result_min_records" of clsimhip_set_tuning) and what Initialize() derives from it.
 // A launch works on ONE copy of this, taken under the converter's tuning mutex.
 struct LaunchTuning {
@@ -370,60 +392,38 @@ private:
     // With the MCPE series stage the bunch's particle table and mask travel the same way, in the form the stage reads (mcpe_series.h);
     // with the PMT series stage likewise (pmt_series.h: the two stages never run in one converter).  The frame photons stage ranks the
     // geometry's DOMs, not a generator's, so its table and mask travel in a blob of their own.
+    struct BunchTable { SeriesBunch bunch; BlobPool::Lease pinned; std::vector<SeriesParticle16> pageable; };
     struct Job {
         uint32_t id = 0; size_t n = 0; uint64_t generated = 0; StepPool::Lease pinned; std::vector<clsimhip_step> steps;
-        SeriesBunch bunch; BlobPool::Lease bunch_pinned; std::vector<SeriesParticle16> bunch_blob;
-        SeriesBunch fp_bunch; BlobPool::Lease fp_bunch_pinned; std::vector<SeriesParticle16> fp_bunch_blob;
+        BunchTable bunch, fp_bunch;
     };
-    // The photons of a result live in a page-locked buffer of the converter's pool (the download lands there and the
-    // caller reads them there until ReleaseResult: no host copy in between), or -- when the pool is exhausted because the
-    // caller holds more results than it has buffers -- in a vector of their own.
+    // The records of a result live in page-locked buffers of the converter's pools (back to their pool with release_result, or with
+    // a result nobody fetched), or -- when a pool is exhausted because the caller holds more results than it has buffers -- in
+    // vectors of their own.
     struct Result {
         uint32_t id = 0;
-        PhotonPool::Lease pinned;                           // pool buffer (back to the pool with release_result, or with a result nobody fetched)
-        size_t count = 0;
-        std::unique_ptr<std::vector<clsimhip_photon>> photons;
+        HostRecords<clsimhip_photon> photons;
         std::unique_ptr<std::vector<float>> histories;     // [photons][history_entries_][4], forward order
-        const clsimhip_photon *data() const { return pinned ? pinned.get() : (photons ? photons->data() : nullptr); }
-        // with an MCPE generator: the bunch's MCPEs, in a page-locked buffer of the MCPE pool or (pool exhausted) a vector, and --
-        // when the result carries no photon record -- a record of its own whose address is the result's handle
-        McpePool::Lease mcpe_pinned;
-        size_t mcpe_count = 0;
-        std::unique_ptr<std::vector<clsimhip_mcpe>> mcpes;
+        // with a stage attached, a result that carries no photon record has a record of its own whose address is the result's handle
         std::unique_ptr<clsimhip_photon> handle;
-        const clsimhip_mcpe *mcpe_data() const { return mcpe_pinned ? mcpe_pinned.get() : (mcpes ? mcpes->data() : nullptr); }
-        // with the MCPE series stage: the series table of the (then sorted) MCPEs and the MASKED count
-        SeriesPool::Lease series_pinned;
-        size_t series_count = 0;
+        // with an MCPE generator: the bunch's MCPEs; with the MCPE series stage sorted, with their series table and the MASKED count
+        HostRecords<clsimhip_mcpe> mcpes;
+        HostRecords<clsimhip_mcpe_series> series;
         uint64_t masked = 0;
-        std::unique_ptr<std::vector<clsimhip_mcpe_series>> series;
-        const clsimhip_mcpe_series *series_data() const { return series_pinned ? series_pinned.get() : (series ? series->data() : nullptr); }
         // with the MCPE merging stage: merged records, merged series table, parent table and its ranges, one behind the other (every
         // one starts at a multiple of 8 bytes) in a page-locked buffer of the merge pool or (pool exhausted) a vector
         BlobPool::Lease merge_pinned;
         std::unique_ptr<std::vector<uint64_t>> merge_blob;
         size_t merged_count = 0, parent_count = 0;
         const uint8_t *merge_data() const { return merge_pinned ? merge_pinned.get() : (merge_blob ? reinterpret_cast<const uint8_t *>(merge_blob->data()) : nullptr); }
-        // with a PMT hit generator: the bunch's hits, kept as the MCPEs are (and `handle` for a result without photon records)
-        PmtHitPool::Lease pmt_pinned;
-        size_t pmt_count = 0;
-        std::unique_ptr<std::vector<clsimhip_pmt_hit>> pmt_hits;
-        const clsimhip_pmt_hit *pmt_data() const { return pmt_pinned ? pmt_pinned.get() : (pmt_hits ? pmt_hits->data() : nullptr); }
-        // with the PMT series stage: the series table of the (then sorted) hits; the MASKED count is `masked`
-        PmtSeriesPool::Lease pmt_series_pinned;
-        size_t pmt_series_count = 0;
-        std::unique_ptr<std::vector<clsimhip_pmt_series>> pmt_series;
-        const clsimhip_pmt_series *pmt_series_data() const { return pmt_series_pinned ? pmt_series_pinned.get() : (pmt_series ? pmt_series->data() : nullptr); }
-        // with the frame photons stage: its records, its series table and its MASKED count (and `handle` for a result without photon records)
-        FramePhotonPool::Lease fp_pinned;
-        size_t fp_count = 0;
-        std::unique_ptr<std::vector<clsimhip_frame_photon>> fp_records;
-        const clsimhip_frame_photon *fp_data() const { return fp_pinned ? fp_pinned.get() : (fp_records ? fp_records->data() : nullptr); }
-        SeriesPool::Lease fp_series_pinned;
-        size_t fp_series_count = 0;
+        // with a PMT hit generator: the bunch's hits; with the PMT series stage sorted, with their series table and the MASKED count
+        HostRecords<clsimhip_pmt_hit> pmt_hits;
+        HostRecords<clsimhip_pmt_series> pmt_series;
+        uint64_t pmt_masked = 0;
+        // with the frame photons stage: its records, its series table and its MASKED count
+        HostRecords<clsimhip_frame_photon> fp_records;
+        HostRecords<clsimhip_mcpe_series> fp_series;
         uint64_t fp_masked = 0;
-        std::unique_ptr<std::vector<clsimhip_mcpe_series>> fp_series;
-        const clsimhip_mcpe_series *fp_series_data() const { return fp_series_pinned ? fp_series_pinned.get() : (fp_series ? fp_series->data() : nullptr); }
     };
 
     void guard() const { if (initialized_) throw Error(CLSIMHIP_ERR_STATE, "I3CLSimStepToPhotonConverterHIP already initialized!"); }
@@ -482,11 +482,71 @@ private:
     // particle tables and masks of the bunches on their way (input queue depth + one per slot + the one being filled)
     BlobPool bunch_pool_{PinnedPoolPolicy{8, size_t{1} << 28, nullptr}};
     size_t result_capacity(size_t records, size_t min_records) const;
+    // `n` records from the device into a payload of the result being made, queued on the copy stream; where they land (n = 0: null)
+    template <class T>
+    T *download(HostRecords<T> &to, PinnedPool<T> &pool, const void *d_from, size_t n, size_t min_records, const char *what);
+    // the result_* calls: one payload of the result `photons` is the handle of, or a stage's records, series table and MASKED count
+    template <class T>
+    void result_records(const clsimhip_photon *photons, bool on, HostRecords<T> Result::*payload, const T **records, size_t *n);
+    template <class Rec, class Ser>
+    void result_series(const clsimhip_photon *photons, bool on, const char *off_text, HostRecords<Rec> Result::*payload, HostRecords<Ser> Result::*table,
+                       uint64_t Result::*masked, const Rec **records, size_t *n, const Ser **series, size_t *n_series, uint64_t *n_masked);
     // Step buffers (see Job): input queue depth + one per slot + the one being filled, each sized by the bunch it first carried (a
     // quarter more) and replaced by a larger one when a later bunch needs it, at most 1 GiB in all
     StepPool step_pool_{PinnedPoolPolicy{8, size_t{1} << 30,
         "clsimhip: all %d page-locked step buffers are in flight; this bunch of %zu steps is staged through pageable memory\n"}};
 
+    // What a series stage has in a slot: its workspace (grown when a bunch's table needs it), its records in order, their series
+    // table, its counts on the device and where finish() reads them
+    struct StageNames { const char *workspace, *out, *series, *counts, *pinned_counts; };
+    template <class Rec, class Ser>
+    struct SeriesStageBuffers {
+        DeviceBuffer<uint8_t> workspace;
+        size_t workspace_bytes = 0;
+        const char *workspace_name = nullptr;
+        DeviceBuffer<Rec> out;
+        DeviceBuffer<Ser> series;
+        DeviceBuffer<uint32_t> d_counts;
+        PinnedBuffer<uint32_t> h_counts;
+        void alloc(size_t capacity, size_t initial_workspace_bytes, const StageNames &names)
+        {
+            workspace_name = names.workspace;
+            workspace_bytes = initial_workspace_bytes;
+            workspace.alloc(workspace_bytes, names.workspace);
+            out.alloc(capacity, names.out);
+            series.alloc(capacity, names.series);
+            d_counts.alloc(8, names.counts);
+            h_counts.alloc(8, names.pinned_counts);
+        }
+        // for a bunch whose stage needs stage_bytes (the slot is free: nothing on the device uses its workspace)
+        void grow_workspace(size_t stage_bytes)
+        {
+            const size_t need = stage_bytes + 64;
+            if (workspace_bytes >= need) return;
+            workspace.reset();
+            workspace.alloc(need + need / 4, workspace_name);
+            workspace_bytes = need + need / 4;
+        }
+    };
+    // Where a slot's table upload reads: the job's pool buffer, which goes back to the pool when the slot is used again, or -- for a
+    // job that came without one -- pinned staging of the slot's own
+    struct BunchUpload {
+        BlobPool::Lease lease;
+        PinnedBuffer<uint8_t> staging;
+        size_t staging_bytes = 0;
+        const uint8_t *source(BunchTable &table, const char *what)
+        {
+            lease = std::move(table.pinned);
+            if (lease) return lease.get();
+            if (staging_bytes < table.bunch.bytes) {
+                staging.reset();
+                staging.alloc(table.bunch.bytes, what);
+                staging_bytes = table.bunch.bytes;
+            }
+            std::memcpy(staging.get(), table.pageable.data(), table.bunch.bytes);
+            return staging.get();
+        }
+    };
     // One buffer set per bunch in flight (OpenCL.cxx:296-340 allocates numBuffers = 1 or 2 of each): while
     // the kernel of bunch k+1 runs, the photons of bunch k are downloaded on the copy stream and converted.
     // (In every struct here events come first: they go before the buffers their work touches.)
@@ -506,20 +566,12 @@ private:
         DeviceBuffer<clsimhip_pmt_hit> d_pmt_hits;  // with a PMT hit generator: max_output_photons_ records, four counters (pmt_hits.h)
         DeviceBuffer<uint32_t> d_pmt_counters;
         PinnedBuffer<uint32_t> h_pmt_counters;
-        // with the PMT series stage: its workspace (grown when a bunch's table needs it), sorted hits, series table, five counts
-        DeviceBuffer<uint8_t> d_pmt_series_workspace;
-        size_t pmt_series_workspace_bytes = 0;
-        DeviceBuffer<clsimhip_pmt_hit> d_pmt_sorted;
-        DeviceBuffer<clsimhip_pmt_series> d_pmt_series;
-        DeviceBuffer<uint32_t> d_pmt_series_counts;
-        PinnedBuffer<uint32_t> h_pmt_series_counts;
-        // with the MCPE series stage: its workspace (grown when a bunch's table needs it), sorted records, series table, five counts
-        DeviceBuffer<uint8_t> d_series_workspace;
-        size_t series_workspace_bytes = 0;
-        DeviceBuffer<clsimhip_mcpe> d_sorted;
-        DeviceBuffer<clsimhip_mcpe_series> d_series;
-        DeviceBuffer<uint32_t> d_series_counts;
-        PinnedBuffer<uint32_t> h_series_counts;
+        // with the MCPE series, the PMT series, the frame photons stage: its buffers; the bunch's table and mask for the hit maker's
+        // series stage (the two never run in one converter) and for the frame photons stage
+        SeriesStageBuffers<clsimhip_mcpe, clsimhip_mcpe_series> series;
+        SeriesStageBuffers<clsimhip_pmt_hit, clsimhip_pmt_series> pmt_series;
+        SeriesStageBuffers<clsimhip_frame_photon, clsimhip_mcpe_series> fp;
+        BunchUpload bunch, fp_bunch;
         // with the MCPE merging stage: its workspace, merged records, merged series table, parents, ranges, two counts
         DeviceBuffer<uint8_t> d_merge_workspace;
         size_t merge_workspace_bytes = 0;
@@ -529,20 +581,6 @@ private:
         DeviceBuffer<clsimhip_mcpe_parent_range> d_ranges;
         DeviceBuffer<uint32_t> d_merge_counts;
         PinnedBuffer<uint32_t> h_merge_counts;
-        // with the frame photons stage: its workspace (grown when a bunch's table needs it), records, series table, six counts, and the
-        // bunch's table as for the series stages
-        DeviceBuffer<uint8_t> d_fp_workspace;
-        size_t fp_workspace_bytes = 0;
-        DeviceBuffer<clsimhip_frame_photon> d_fp_out;
-        DeviceBuffer<clsimhip_mcpe_series> d_fp_series;
-        DeviceBuffer<uint32_t> d_fp_counts;
-        PinnedBuffer<uint32_t> h_fp_counts;
-        BlobPool::Lease fp_bunch_lease;
-        PinnedBuffer<uint8_t> h_fp_bunch;
-        size_t h_fp_bunch_bytes = 0;
-        BlobPool::Lease bunch_lease;            // the pool buffer the slot's table upload reads; back to the pool when the slot is used again
-        PinnedBuffer<uint8_t> h_bunch;          // pinned staging (for a job that came without a pool buffer)
-        size_t h_bunch_bytes = 0;
         uint32_t id = 0;
         uint64_t generated = 0;
         size_t result_min_records = 0;          // of the tuning the bunch was launched with

@@ -8,8 +8,6 @@
 namespace clsimhip {
 
 namespace {
-size_t round16(size_t v) { return (v + 15u) & ~size_t{15}; }
-
 // the workspace: header and the two histograms (zeroed together by every call), tile counts, run counts, three key buffers, the
 // records' places, the runs, the bunch's blob
 struct FramePhotonsWorkspace {
@@ -32,8 +30,6 @@ struct FramePhotonsWorkspace {
     }
 };
 
-uint32_t record_word(int32_t string_id, uint32_t om_id) { return static_cast<uint32_t>(static_cast<uint16_t>(string_id)) | (om_id << 16); }
-
 // what the twin sorts: the key of the two rounds and the content
 struct Kept { SeriesKey key; uint32_t h; FramePhotonContent content; };
 
@@ -52,15 +48,12 @@ bool kept_less(const Kept &a, const Kept &b)
 }
 } // namespace
 
-// (the blob has the MCPE series' layout: table, frame IDs by rank, masked groups)
-size_t frame_photons_blob_bytes(size_t n_particles, size_t n_masked)
-{
-    return round16(n_particles * sizeof(SeriesParticle)) + round16(std::max<size_t>(n_particles, 1u) * sizeof(uint32_t)) + round16(n_masked * sizeof(uint32_t)) + 16u;
-}
+// (the blob has the MCPE series' layout: series_bunch.h)
+size_t frame_photons_blob_bytes(size_t n_particles, size_t n_masked) { return series_blob_bytes(n_particles, n_masked); }
 
 size_t frame_photons_workspace_bytes(size_t capacity, size_t n_particles, size_t n_masked)
 {
-    return FramePhotonsWorkspace(capacity, frame_photons_blob_bytes(n_particles, n_masked)).bytes;
+    return FramePhotonsWorkspace(capacity, series_blob_bytes(n_particles, n_masked)).bytes;
 }
 
 FramePhotonDoms::FramePhotonDoms(const int32_t *string_ids, const uint32_t *om_ids, size_t n)
@@ -99,63 +92,17 @@ FramePhotonDoms::~FramePhotonDoms()
         DeviceBuffer<uint64_t> table(kv.second.dom_table);
         DeviceBuffer<uint32_t> ranks(kv.second.dom_ranks);
     }
-    for (auto &kv : stages_) {
-        DeviceGuard on_device(kv.first, std::nothrow);
-        kv.second = Stage();
-    }
 }
 
 SeriesBunch FramePhotonDoms::prepare(const clsimhip_mcpe_particle *particles, size_t n_particles, const clsimhip_mcpe_mask *masked, size_t n_masked,
                                      uint8_t *blob) const
 {
-    if (n_particles && !particles) throw Error(CLSIMHIP_ERR_ARGUMENT, "particles is (null)");
-    if (n_masked && !masked) throw Error(CLSIMHIP_ERR_ARGUMENT, "masked is (null)");
-    if (!blob) throw Error(CLSIMHIP_ERR_ARGUMENT, "blob is (null)");
-    if (n_particles > 0xffffffffull || n_masked > 0xffffffffull) throw Error(CLSIMHIP_ERR_ARGUMENT, "more than 2^32 - 1 particles or masked modules");
-    SeriesBunch B;
-    B.have_table = particles != nullptr;
-    B.n_particles = static_cast<uint32_t>(n_particles);
-    B.frames_offset = round16(n_particles * sizeof(SeriesParticle));
-    B.masked_offset = B.frames_offset + round16(std::max<size_t>(n_particles, 1u) * sizeof(uint32_t));
-    B.bytes = frame_photons_blob_bytes(n_particles, n_masked);
-    SeriesParticle *table = reinterpret_cast<SeriesParticle *>(blob);
-    uint32_t *frames = reinterpret_cast<uint32_t *>(blob + B.frames_offset);
-    uint32_t *groups = reinterpret_cast<uint32_t *>(blob + B.masked_offset);
-    // frames: the distinct frame IDs, ascending; a table entry carries its frame's rank
-    size_t n_frames = 1;
-    frames[0] = 0u;
-    if (n_particles > 0) {
-        for (size_t i = 0; i < n_particles; ++i) {
-            if (i > 0 && !(particles[i].identifier > particles[i - 1].identifier))
-                throw Error(CLSIMHIP_ERR_ARGUMENT, "the particle table is not strictly increasing in identifier (entry " + std::to_string(i) + ")");
-            frames[i] = particles[i].frame;
-        }
-        std::sort(frames, frames + n_particles);
-        n_frames = static_cast<size_t>(std::unique(frames, frames + n_particles) - frames);
-        for (size_t i = 0; i < n_particles; ++i) {
-            table[i].identifier = particles[i].identifier;
-            table[i].frame_rank = static_cast<uint32_t>(std::lower_bound(frames, frames + n_frames, particles[i].frame) - frames);
-            table[i].time_shift = particles[i].time_shift;
-        }
-        B.consecutive = static_cast<uint64_t>(particles[n_particles - 1].identifier) - particles[0].identifier + 1u == n_particles;
-    }
-    const uint64_t n_doms = num_doms();
-    if (static_cast<uint64_t>(n_frames) * std::max<uint64_t>(n_doms, 1u) >= (uint64_t{1} << 32))
-        throw Error(CLSIMHIP_ERR_CONFIG, "frame photons: " + std::to_string(n_frames) + " frames x " + std::to_string(n_doms) + " DOMs do not fit 32 bits");
-    B.n_frames = static_cast<uint32_t>(n_frames);
-    // mask: the (frame, module) pairs it names, ascending and distinct; what names no frame of the table or no DOM of the list is
-    // ignored
-    size_t kept = 0;
-    for (size_t i = 0; i < n_masked; ++i) {
-        const uint32_t *f = std::lower_bound(frames, frames + n_frames, masked[i].frame);
-        if (f == frames + n_frames || *f != masked[i].frame || (B.have_table && n_particles == 0)) continue;
-        const int64_t rank = series_dom_rank(dom_table_.data(), dom_ranks_.data(), dom_mask_, record_word(masked[i].string_id, masked[i].om_id));
-        if (rank < 0) continue;
-        groups[kept++] = static_cast<uint32_t>(f - frames) * static_cast<uint32_t>(n_doms) + static_cast<uint32_t>(rank);
-    }
-    std::sort(groups, groups + kept);
-    B.n_masked = static_cast<uint32_t>(std::unique(groups, groups + kept) - groups);
-    return B;
+    // a masked entry's key is its group: frame rank x DOMs + DOM rank
+    const uint32_t n_doms = static_cast<uint32_t>(num_doms());
+    return prepare_series_bunch(particles, n_particles, masked, n_masked, blob, num_doms(), "frame photons", "DOMs", [&](uint32_t frame_rank, uint32_t word) -> int64_t {
+        const int64_t rank = series_dom_rank(dom_table_.data(), dom_ranks_.data(), dom_mask_, word);
+        return rank < 0 ? -1 : static_cast<int64_t>(frame_rank * n_doms + static_cast<uint32_t>(rank));
+    });
 }
 
 void FramePhotonDoms::host(const clsimhip_photon *in, size_t n, const clsimhip_mcpe_particle *particles, size_t n_particles, const clsimhip_mcpe_mask *masked,
@@ -167,13 +114,12 @@ void FramePhotonDoms::host(const clsimhip_photon *in, size_t n, const clsimhip_m
     uint8_t *blob = reinterpret_cast<uint8_t *>(aligned.data());
     const SeriesBunch B = prepare(particles, n_particles, masked, n_masked, blob);
     SeriesLookup L{};
-    L.particles = B.have_table ? reinterpret_cast<const SeriesParticle *>(blob) : nullptr;
+    set_series_lookup(L, B, blob);
     L.masked_groups = reinterpret_cast<const uint32_t *>(blob + B.masked_offset);
     L.dom_table = dom_table_.data();
     L.dom_ranks = dom_ranks_.data();
-    L.n_particles = B.n_particles; L.n_masked = B.n_masked; L.dom_mask = dom_mask_;
+    L.dom_mask = dom_mask_;
     L.n_doms = static_cast<uint32_t>(num_doms());
-    L.consecutive = B.consecutive ? 1u : 0u;
     const uint32_t *frames = reinterpret_cast<const uint32_t *>(blob + B.frames_offset);
     std::vector<Kept> kept;
     kept.reserve(n);
@@ -249,53 +195,30 @@ void FramePhotonDoms::device(int device, const void *d_photons, const void *d_co
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) throw Error(CLSIMHIP_ERR_DEVICE, "no HIP device available (the frame photons' device path has no CPU fallback)");
     if (device < 0 || device >= count) throw Error(CLSIMHIP_ERR_ARGUMENT, "device ordinal out of range");
     DeviceGuard on_device(device);
-    const size_t bytes = frame_photons_blob_bytes(n_particles, n_masked);
     // one call at a time per object prepares its bunch in the staging buffer: the previous call's copy has to be over
     std::lock_guard<std::mutex> lk(call_mutex_);
-    Stage *staged = nullptr;
-    {
-        std::lock_guard<std::mutex> state_lock(device_mutex_);
-        staged = &stages_[device];
-    }
-    Stage &stage = *staged;
-    if (stage.done.get()) hip_check(hipEventSynchronize(stage.done.get()), "frame photons: previous upload");
-    else stage.done.create_untimed("hipEventCreate");
-    if (stage.bytes < bytes) {
-        stage.buffer.reset();
-        stage.buffer.alloc(bytes, "pinned frame photons bunch");
-        stage.bytes = bytes;
-    }
-    uint8_t *blob = stage.buffer.get();
+    uint8_t *blob = staging_.acquire(device, series_blob_bytes(n_particles, n_masked), "frame photons");
     const SeriesBunch B = prepare(particles, n_particles, masked, n_masked, blob);
-    // (the event is recorded right behind the copy, in front of the kernels: the next call waits for the copy, not for the stage)
-    device_prepared(device, d_photons, d_count, capacity, B, blob, d_out, d_series, d_counts, d_workspace, workspace_bytes, stream, stage.done.get());
+    device_prepared(device, d_photons, d_count, capacity, B, blob, d_out, d_series, d_counts, d_workspace, workspace_bytes, stream, staging_.done(device));
 }
 
 void FramePhotonDoms::device_prepared(int device, const void *d_photons, const void *d_count, size_t capacity, const SeriesBunch &B, const uint8_t *h_blob,
                                       void *d_out, void *d_series, void *d_counts, void *d_workspace, size_t workspace_bytes, hipStream_t stream, hipEvent_t uploaded)
 {
-    if (!d_count || !d_counts || !d_workspace) throw Error(CLSIMHIP_ERR_ARGUMENT, "device pointers are (null)");
-    if (capacity && (!d_photons || !d_out || !d_series)) throw Error(CLSIMHIP_ERR_ARGUMENT, "d_photons / d_out / d_series is (null)");
-    if (capacity > 0xffffffffull) throw Error(CLSIMHIP_ERR_ARGUMENT, "capacity beyond 2^32 - 1 records");
-    if ((reinterpret_cast<uintptr_t>(d_photons) & 15u) || (reinterpret_cast<uintptr_t>(d_out) & 15u) || (reinterpret_cast<uintptr_t>(d_series) & 15u) ||
-        (reinterpret_cast<uintptr_t>(d_workspace) & 15u) || (reinterpret_cast<uintptr_t>(d_counts) & 3u) || (reinterpret_cast<uintptr_t>(d_count) & 3u))
-        throw Error(CLSIMHIP_ERR_ARGUMENT, "d_photons, d_out, d_series and d_workspace must be aligned to 16 bytes, d_count and d_counts to 4");
     const FramePhotonsWorkspace W(capacity, B.bytes);
-    if (workspace_bytes < W.bytes)
-        throw Error(CLSIMHIP_ERR_ARGUMENT, "the frame photons workspace holds " + std::to_string(workspace_bytes) + " bytes, " + std::to_string(W.bytes) + " are needed");
+    check_series_device_args("frame photons", "d_photons", 16u, d_photons, d_count, capacity, d_out, d_series, d_counts, d_workspace, workspace_bytes, W.bytes);
     DeviceGuard on_device(device);
     const Image im = image_on(device);
     uint8_t *ws = static_cast<uint8_t *>(d_workspace);
     hip_check(hipMemcpyAsync(ws + W.blob, h_blob, B.bytes, hipMemcpyHostToDevice, stream), "upload frame photons bunch");
     if (uploaded) hip_check(hipEventRecord(uploaded, stream), "event");
     FramePhotonsDeviceArgs A{};
-    A.lookup.particles = B.have_table ? reinterpret_cast<const SeriesParticle *>(ws + W.blob) : nullptr;
+    set_series_lookup(A.lookup, B, ws + W.blob);
     A.lookup.masked_groups = reinterpret_cast<const uint32_t *>(ws + W.blob + B.masked_offset);
     A.lookup.dom_table = im.dom_table;
     A.lookup.dom_ranks = im.dom_ranks;
-    A.lookup.n_particles = B.n_particles; A.lookup.n_masked = B.n_masked; A.lookup.dom_mask = dom_mask_;
+    A.lookup.dom_mask = dom_mask_;
     A.lookup.n_doms = static_cast<uint32_t>(num_doms());
-    A.lookup.consecutive = B.consecutive ? 1u : 0u;
     A.frames = reinterpret_cast<const uint32_t *>(ws + W.blob + B.frames_offset);
     A.in = static_cast<const clsimhip_photon *>(d_photons);
     A.in_count = static_cast<const uint32_t *>(d_count);

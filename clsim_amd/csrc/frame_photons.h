@@ -26,6 +26,7 @@
 #include "hip_resources.h"
 #include "host_model.h"
 #include "mcpe_series.h"
+#include "series_bunch.h"
 
 namespace clsimhip {
 
@@ -130,7 +131,6 @@ public:
 
 private:
     struct Image { uint64_t *dom_table = nullptr; uint32_t *dom_ranks = nullptr; };
-    struct Stage { Event done; PinnedBuffer<uint8_t> buffer; size_t bytes = 0; };
     Image image_on(int device);
     std::vector<uint64_t> dom_table_;       // record word (string ID | OM ID << 16) | 1 << 32; 0 = empty
     std::vector<uint32_t> dom_ranks_;       // beside dom_table_, slot by slot
@@ -138,7 +138,7 @@ private:
     uint32_t dom_mask_ = 0;
     std::mutex device_mutex_, call_mutex_;
     std::map<int, Image> images_;
-    std::map<int, Stage> stages_;
+    SeriesStaging staging_{&device_mutex_}; // of the stand-alone call's bunch (series_bunch.h): calls under call_mutex_, its map under device_mutex_
 };
 
 } // namespace clsimhip

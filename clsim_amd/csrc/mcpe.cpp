@@ -101,11 +101,6 @@ McpeGenerator::~McpeGenerator()
         DeviceBuffer<uint64_t> dom_table(kv.second.dom_table);
         DeviceBuffer<uint32_t> dom_ranks(kv.second.dom_ranks), dom_of_rank(kv.second.dom_of_rank);
     }
-    // (a stage exists from the first series call on a device on, whether or not that call got as far as the device's image)
-    for (auto &kv : stages_) {
-        DeviceGuard on_device(kv.first, std::nothrow);
-        kv.second = SeriesStage();
-    }
 }
 
 bool McpeGenerator::has_class(int32_t string_id, uint32_t om_id) const

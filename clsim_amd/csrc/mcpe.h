@@ -19,6 +19,7 @@
 #include "detmath.hip.h"
 #include "hip_resources.h"
 #include "host_model.h"
+#include "series_bunch.h"
 
 namespace clsimhip {
 
@@ -263,11 +264,9 @@ private:
     std::vector<uint32_t> dom_ranks_;       // beside dom_table_, slot by slot: the DOM's rank in ascending (string ID, OM ID) order
     std::vector<uint32_t> dom_of_rank_;     // record word 11 (string ID | OM ID << 16) by rank
     struct DeviceImage { double *values = nullptr; uint64_t *dom_table = nullptr; uint32_t *dom_ranks = nullptr, *dom_of_rank = nullptr; };
-    // page-locked staging of the stand-alone series call's bunch, one per device, reused once its upload has been passed
-    struct SeriesStage { Event done; PinnedBuffer<uint8_t> buffer; size_t bytes = 0; };
     std::mutex device_mutex_, series_mutex_;
     std::map<int, DeviceImage> images_;
-    std::map<int, SeriesStage> stages_;
+    SeriesStaging staging_;                 // of the stand-alone series call's bunch (series_bunch.h; under series_mutex_)
     DeviceImage image_on(int device);
 };
 

@@ -11,7 +11,9 @@ from clsim_amd import _lib
 from clsim_amd import converter as CV
 from tests import common
 from tests import frame_photons_common as F
+from tests import mcpe_merge_common as MM
 from tests import test_mcpe_gpu as G
+from tests import test_mcpe_merge_gpu as MG
 from tests import test_mcpe_series_gpu as SG
 
 pytestmark = pytest.mark.gpu
@@ -166,12 +168,13 @@ def geometry_doms(cfg):
     return CV.FramePhotonDoms(cfg["geom"]["string_ids"], cfg["geom"]["dom_ids"])
 
 
-def converter_with(cfg, keep_photons, kernel="classic", double_buffering=False, frame_photons=True, mcpe=None):
+def converter_with(cfg, keep_photons, kernel="classic", double_buffering=False, frame_photons=True, mcpe=None, mcpeMergeWindow=None):
     bias = CV.GetIceCubeDOMAcceptance()
     return CV.initializeHIP(0, CV.I3CLSimSimpleGeometry.from_dict(cfg["geom"]), cfg["med_p"], bias, common.product_generators(cfg, bias),
                             pancakeFactor=5.0, enableDoubleBuffering=double_buffering, stopDetectedPhotons=True,
                             approximateNumberOfWorkItems=N_STEPS, streams=common.streams(N_STEPS), tuning=dict(kernel=1 if kernel == "pool" else 2),
-                            mcpeGenerator=mcpe, mcpeSeries=mcpe is not None, keepPhotons=keep_photons, framePhotons=frame_photons)
+                            mcpeGenerator=mcpe, mcpeSeries=mcpe is not None, keepPhotons=keep_photons, framePhotons=frame_photons,
+                            mcpeMergeWindow=mcpeMergeWindow)
 
 
 @pytest.mark.parametrize("kernel", ["classic", "pool"])
@@ -245,6 +248,46 @@ def test_three_bunches_in_flight_each_with_its_own_table():
             else:           # the same without the photon records
                 assert len(r[1]) == 0 and (r.frame_photons.tobytes(), r.frame_photon_series.tobytes(), r.frame_photons_masked) == seen[i]
     assert len({s[1] for s in seen}) == 3 and seen[1][2] == 0 < seen[0][2]
+
+
+def test_a_caller_that_keeps_nine_results_gets_every_stage_from_pool_buffers_and_from_pageable_memory():
+    """every result pool has six buffers: of nine results held at once the last three carry photons, MCPEs, both series tables, the
+    merged series and the frame photons in pageable memory (and the input queue of five keeps more tables on their way than the
+    table pool has buffers).  Every payload is what the host twins make of the result's own photons; after the release the pools
+    serve again."""
+    cfg = common.config("mie")
+    doms, gen = geometry_doms(cfg), G.generator_for(cfg)
+    p, masked = SG.bunch_inputs(cfg)
+    window = MG.WINDOW
+    bunches = [SG.framed_steps(cfg, s) for s in range(21, 32)]
+    conv = converter_with(cfg, True, double_buffering=True, mcpe=gen, mcpeMergeWindow=window)
+
+    def check(r, k):
+        assert r[0] == k
+        view = np.array(r[1])
+        merged = (r.merged, r.merged_series, r.parents, r.parent_ranges)
+        # (or a fallback that downloads nothing would pass)
+        assert len(view) > 100 and len(r.mcpes) >= 1 and len(r.series) >= 1 and len(r.frame_photon_series) >= 1 and 1 <= len(r.merged) < len(r.mcpes), k
+        want = doms.MakeFramePhotonsHost(view, p, masked)
+        same((r.frame_photons, r.frame_photon_series, dict(want[2], masked=r.frame_photons_masked)), want)
+        want = gen.MakeSeriesHost(gen.ConvertHost(view)[0], p, masked)
+        SG.same((r.mcpes, r.series, dict(want[2], masked=r.masked)), want)
+        MM.same(merged, CV.MCPEGenerator.MergeHost(r.mcpes, r.series, window))
+
+    import threading                                    # (the input queue holds five bunches: a producer thread, like a real caller)
+    producer = threading.Thread(target=lambda: [conv.EnqueueSteps(steps, k, particles=p, masked=masked) for k, steps in enumerate(bunches[:9])])
+    producer.start()
+    held = [conv.GetConversionResultInPlace() for _ in range(9)]        # no release in between
+    producer.join()
+    for k, r in enumerate(held):
+        check(r, k)
+    for r in held:
+        r[2]()
+    for k in (9, 10):
+        conv.EnqueueSteps(bunches[k], k, particles=p, masked=masked)
+        r = conv.GetConversionResultInPlace()
+        check(r, k)
+        r[2]()
 
 
 def test_beside_the_mcpe_series_both_results_are_what_they_are_alone():
