@@ -138,6 +138,8 @@ SYMBOLS = [
     "clsimhip_frame_photon_doms_create", "clsimhip_frame_photon_doms_destroy", "clsimhip_frame_photon_doms_last_error",
     "clsimhip_frame_photons_host", "clsimhip_frame_photons_workspace_bytes", "clsimhip_frame_photons_device", "clsimhip_set_frame_photons",
     "clsimhip_get_result_frame_photons",
+    "clsimhip_cable_shadow_create", "clsimhip_cable_shadow_destroy", "clsimhip_cable_shadow_last_error", "clsimhip_cable_shadow_host",
+    "clsimhip_cable_shadow_workspace_bytes", "clsimhip_cable_shadow_device", "clsimhip_set_cable_shadow", "clsimhip_get_result_cable_shadow",
 ]
 
 # clsimhip_get_last_launch: CLSIMHIP_FAMILY_* and CLSIMHIP_LENGTHS_* by name
@@ -336,6 +338,14 @@ def load():
         "clsimhip_frame_photons_device": (i32, [vp, i32, vp, vp, sz, vp, sz, vp, sz, vp, vp, vp, vp, sz, vp]),
         "clsimhip_set_frame_photons": (i32, [vp, i32, i32]),
         "clsimhip_get_result_frame_photons": (i32, [vp, vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(u64)]),
+        "clsimhip_cable_shadow_create": (i32, [sz, vp, vp, vp, dbl, C.POINTER(vp)]),
+        "clsimhip_cable_shadow_destroy": (None, [vp]),
+        "clsimhip_cable_shadow_last_error": (C.c_char_p, [vp]),
+        "clsimhip_cable_shadow_host": (i32, [vp, vp, sz, vp, vp, C.POINTER(sz), vp]),
+        "clsimhip_cable_shadow_workspace_bytes": (sz, [sz]),
+        "clsimhip_cable_shadow_device": (i32, [vp, i32, vp, vp, sz, vp, vp, vp, vp, sz, vp]),
+        "clsimhip_set_cable_shadow": (i32, [vp, vp]),
+        "clsimhip_get_result_cable_shadow": (i32, [vp, vp, C.POINTER(vp), C.POINTER(sz), vp]),
         "clsimhip_tabulator_write_fits_file": (i32, [vp, C.c_char_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double), sz]),
     }
     for name in SYMBOLS:

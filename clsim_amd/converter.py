@@ -613,6 +613,59 @@ class FramePhotonDoms:
                                                        int(workspace_bytes), C.c_void_p(stream)))
 
 
+class CableShadow:
+    """The cylinder set of the cable shadow stage (clsimhip_cable_shadow; include/clsimhip.h: "Cable shadow"): a detected photon whose
+    last `distance` metres of path meet a solid finite cylinder is shadowed.  top, bottom: [n, 3] end points; radius: [n] or one value
+    for all.  At most CABLE_SHADOW_MAX_CYLINDERS cylinders."""
+
+    def __init__(self, top, bottom, radius, distance):
+        self._lib = _lib.load()
+        top = np.ascontiguousarray(top, dtype=np.float64).reshape(-1, 3)
+        bottom = np.ascontiguousarray(bottom, dtype=np.float64).reshape(-1, 3)
+        radius = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float64), (len(top),)))
+        if top.shape != bottom.shape:
+            raise ValueError("top and bottom: one point per cylinder each")
+        h = C.c_void_p()
+        _check(self._lib.clsimhip_cable_shadow_create(len(top), top.ctypes.data_as(C.c_void_p), bottom.ctypes.data_as(C.c_void_p),
+                                                      radius.ctypes.data_as(C.c_void_p), float(distance), C.byref(h)))
+        self._h = h
+        self.num_cylinders = len(top)
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                self._lib.clsimhip_cable_shadow_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def MakeHost(self, photons):
+        """(flags, lit, counts): the host twin.  photons: PHOTON_DTYPE; flags: one uint8 per record, 1 = shadowed; lit: the records with
+        flag 0, in input order; counts = {"tested": ..., "shadowed": ...}"""
+        photons = np.ascontiguousarray(photons, dtype=PHOTON_DTYPE)
+        flags = np.zeros(len(photons), dtype=np.uint8)
+        lit = np.zeros(len(photons), dtype=PHOTON_DTYPE)
+        n_lit, counts = C.c_size_t(), np.zeros(2, dtype=np.uint64)
+        _check(self._lib.clsimhip_cable_shadow_host(self._h, photons.ctypes.data_as(C.c_void_p), len(photons), flags.ctypes.data_as(C.c_void_p),
+                                                    lit.ctypes.data_as(C.c_void_p), C.byref(n_lit), counts.ctypes.data_as(C.c_void_p)))
+        return flags, lit[:n_lit.value], dict(zip(CABLE_SHADOW_COUNTS, (int(c) for c in counts)))
+
+    @staticmethod
+    def WorkspaceBytes(capacity):
+        return int(_lib.load().clsimhip_cable_shadow_workspace_bytes(int(capacity)))
+
+    def MakeDevice(self, d_photons, d_count, capacity, d_flags, d_lit, d_counts, d_workspace, workspace_bytes, device=0, stream=0):
+        """the kernels on device-resident photon records (addresses; d_photons, d_lit and d_workspace 16-byte aligned): min(*d_count,
+        capacity) records; d_flags: `capacity` bytes, d_lit: `capacity` records, d_counts: three uint32 (lit, tested, shadowed),
+        d_workspace: WorkspaceBytes(capacity) bytes"""
+        _check(self._lib.clsimhip_cable_shadow_device(self._h, int(device), C.c_void_p(d_photons), C.c_void_p(d_count), int(capacity), C.c_void_p(d_flags),
+                                                      C.c_void_p(d_lit), C.c_void_p(d_counts), C.c_void_p(d_workspace), int(workspace_bytes), C.c_void_p(stream)))
+
+
+CABLE_SHADOW_COUNTS = ("tested", "shadowed")
+CABLE_SHADOW_MAX_CYLINDERS = 16384
+
+
 class ConversionResult(tuple):
     """What GetConversionResult / GetConversionResultInPlace return: the tuple (identifier, photons[, histories]) / (identifier,
     photons, release), with the bunch's MCPEs (MCPE_DTYPE) as attribute `mcpes` when the converter has an MCPE generator (None
@@ -621,7 +674,10 @@ class ConversionResult(tuple):
     (MCPE_PARENT_DTYPE) and `parent_ranges` (MCPE_PARENT_RANGE_DTYPE) beside them.  With a PMT hit generator `pmt_hits` holds the bunch's hits (PMT_HIT_DTYPE);
     with the PMT series stage they are the sorted records, `pmt_series` their series table (PMT_SERIES_DTYPE) and `masked` the
     bunch's MASKED count.  With the frame photons stage `frame_photons` (FRAME_PHOTON_DTYPE), `frame_photon_series` (MCPE_SERIES_DTYPE)
-    and `frame_photons_masked`."""
+    and `frame_photons_masked`.  With the cable shadow stage `shadow_flags` (one uint8 per photon record, 1 = shadowed) and
+    `shadow_counts` ({"tested", "shadowed"}); the photons stay all detected photons, every other stage's records come from the lit ones."""
+    shadow_flags = None
+    shadow_counts = None
     frame_photons = None
     frame_photon_series = None
     frame_photons_masked = None
@@ -650,6 +706,7 @@ class I3CLSimStepToPhotonConverterHIP:
         self._pmt = None
         self._pmt_series = False
         self._frame_photons = False
+        self._shadow = None
 
     def __del__(self):
         try:
@@ -723,6 +780,12 @@ class I3CLSimStepToPhotonConverterHIP:
         records on the device.  Before Initialize() only."""
         self._call("clsimhip_set_frame_photons", int(bool(on)), int(bool(keepPhotons)))
         self._frame_photons = bool(on)
+    def SetCableShadow(self, shadow):
+        """shadow: a CableShadow or None (off, the default).  The stage runs right behind the propagation kernel; the MCPE generator, the
+        PMT hit generator, their series stages and the frame photons stage then read the lit records.  Results keep all detected
+        photons, with `shadow_flags` aligned to them and `shadow_counts`.  Before Initialize() only."""
+        self._call("clsimhip_set_cable_shadow", shadow._h if shadow is not None else None)
+        self._shadow = shadow
     def SetMCPEMerging(self, window, on=True):
         """the merging stage behind the series stage: records of a series within `window` of their group's opener become one merged
         record (result attributes `merged`, `merged_series`, `parents`, `parent_ranges`; `mcpes` and `series` stay the unmerged
@@ -810,7 +873,18 @@ class I3CLSimStepToPhotonConverterHIP:
 
     def _has_handle(self):
         """a result without photon records still has a handle to release when a hit maker is attached"""
-        return self._mcpe is not None or self._pmt is not None or self._frame_photons
+        return self._mcpe is not None or self._pmt is not None or self._frame_photons or self._shadow is not None
+
+    def GetResultCableShadow(self, ptr):
+        """copies of the cable shadow flags of the result `ptr` belongs to and its counts: (flags, {"tested", "shadowed"});
+        CLSIMHIP_ERR_STATE without SetCableShadow"""
+        fp, fn, counts = C.c_void_p(), C.c_size_t(), np.zeros(2, dtype=np.uint64)
+        self._call("clsimhip_get_result_cable_shadow", ptr, C.byref(fp), C.byref(fn), counts.ctypes.data_as(C.c_void_p))
+        return self._copy_records(fp, fn.value, np.uint8), dict(zip(CABLE_SHADOW_COUNTS, (int(c) for c in counts)))
+
+    def _attach_cable_shadow(self, result, shadow):
+        if shadow is not None:
+            result.shadow_flags, result.shadow_counts = shadow
 
     def GetResultFramePhotons(self, ptr):
         """copies of the frame photons of the result `ptr` belongs to: (records, series table, MASKED count); CLSIMHIP_ERR_STATE
@@ -859,6 +933,7 @@ class I3CLSimStepToPhotonConverterHIP:
             mcpes = self._result_mcpes(ptr)
             pmt_hits = self._result_pmt_hits(ptr)
             fp = self.GetResultFramePhotons(ptr) if self._frame_photons else None
+            shadow = self.GetResultCableShadow(ptr) if self._shadow is not None else None
         finally:
             if n.value or self._has_handle():
                 self._call("clsimhip_release_result", ptr)
@@ -866,6 +941,7 @@ class I3CLSimStepToPhotonConverterHIP:
         self._attach_mcpes(result, mcpes)
         self._attach_pmt_hits(result, pmt_hits)
         self._attach_frame_photons(result, fp)
+        self._attach_cable_shadow(result, shadow)
         return result
 
     def GetConversionResultInPlace(self):
@@ -879,6 +955,7 @@ class I3CLSimStepToPhotonConverterHIP:
             mcpes = self._result_mcpes(ptr)
             pmt_hits = self._result_pmt_hits(ptr)
             fp = self.GetResultFramePhotons(ptr) if self._frame_photons else None
+            shadow = self.GetResultCableShadow(ptr) if self._shadow is not None else None
         except Exception:
             if n.value or self._has_handle():
                 self._call("clsimhip_release_result", ptr)
@@ -895,6 +972,7 @@ class I3CLSimStepToPhotonConverterHIP:
         self._attach_mcpes(result, mcpes)
         self._attach_pmt_hits(result, pmt_hits)
         self._attach_frame_photons(result, fp)
+        self._attach_cable_shadow(result, shadow)
         return result
 
     def _attach_pmt_hits(self, result, pmt_hits):
@@ -1072,7 +1150,7 @@ def initializeHIP(device, geometry, medium, wavelengthGenerationBias, wavelength
                   saveAllPhotonsPrescale=0.01, fixedNumberOfAbsorptionLengths=float("nan"), pancakeFactor=1.0,
                   photonHistoryEntries=0, limitWorkgroupSize=0, approximateNumberOfWorkItems=262144,
                   seed=12345, streams=None, tuning=None, mcpeGenerator=None, keepPhotons=True, mcpeSeries=False, pmtHitGenerator=None, mcpeMergeWindow=None, pmtSeries=False,
-                  framePhotons=False):
+                  framePhotons=False, cableShadow=None):
     """Canonical configuration sequence, I3CLSimModuleHelper::initializeOpenCL
     (ModuleHelper.cxx:303-372).  tuning: {key: value} for clsimhip_set_tuning, applied before Compile().
     mcpeGenerator: an MCPEGenerator that turns every bunch's photons into MCPEs on the GPU (result attribute `mcpes`);
@@ -1081,7 +1159,7 @@ def initializeHIP(device, geometry, medium, wavelengthGenerationBias, wavelength
     pmtHitGenerator: a PMTHitGenerator instead, for modules with several PMTs (result attribute `pmt_hits`; keepPhotons as above);
     pmtSeries=True sorts its hits into per-frame, per-module, per-PMT series (SetPMTSeries).
     framePhotons=True files the detected photons themselves into per-frame, per-module sorted series (SetFramePhotons; keepPhotons as
-    above)."""
+    above).  cableShadow: a CableShadow whose cylinders shadow detected photons before any of those stages (SetCableShadow)."""
     conv = I3CLSimStepToPhotonConverterHIP(device)
     for key, value in (tuning or {}).items():
         conv.SetTuning(key, value)
@@ -1109,6 +1187,8 @@ def initializeHIP(device, geometry, medium, wavelengthGenerationBias, wavelength
         conv.SetPMTSeries(True)
     if framePhotons:
         conv.SetFramePhotons(True, keepPhotons)
+    if cableShadow is not None:
+        conv.SetCableShadow(cableShadow)
     conv.Compile()
     max_wg = conv.GetMaxWorkgroupSize()
     if limitWorkgroupSize:

@@ -15,6 +15,7 @@
 #include "mcpe.h"
 #include "mcpe_merge.h"
 #include "pmt_hits.h"
+#include "cable_shadow.h"
 #include "frame_photons.h"
 #include "pmt_series.h"
 
@@ -25,6 +26,7 @@ struct clsimhip_medium { MediumData data; };
 struct clsimhip_mcpe_generator { std::shared_ptr<McpeGenerator> impl; };
 struct clsimhip_pmt_generator { std::shared_ptr<PmtHitGenerator> impl; };
 struct clsimhip_frame_photon_doms { std::shared_ptr<FramePhotonDoms> impl; };
+struct clsimhip_cable_shadow { std::shared_ptr<CableShadow> impl; };
 struct clsimhip_tabulator {
     std::unique_ptr<Tabulator> impl;
 };
@@ -1207,6 +1209,42 @@ int clsimhip_get_result_frame_photons(clsimhip_converter *c, const clsimhip_phot
                                       const clsimhip_mcpe_series **series, size_t *n_series, uint64_t *n_masked)
 {
     return guarded(c, [&] { need(c, "converter"); c->impl.result_frame_photons(photons, records, n, series, n_series, n_masked); });
+}
+
+// ---- Cable shadow (cable_shadow.h) ----
+int clsimhip_cable_shadow_create(size_t n_cylinders, const double *top, const double *bottom, const double *radius, double distance, clsimhip_cable_shadow **out)
+{
+    return guarded(nullptr, [&] {
+        need(out, "out");
+        *out = new clsimhip_cable_shadow{std::make_shared<CableShadow>(n_cylinders, top, bottom, radius, distance)};
+    });
+}
+void clsimhip_cable_shadow_destroy(clsimhip_cable_shadow *s) { delete s; }
+const char *clsimhip_cable_shadow_last_error(const clsimhip_cable_shadow *s) { (void)s; return g_last_error.c_str(); }
+int clsimhip_cable_shadow_host(const clsimhip_cable_shadow *s, const clsimhip_photon *photons, size_t n, uint8_t *flags, clsimhip_photon *lit, size_t *n_lit,
+                               uint64_t counts[2])
+{
+    return guarded(nullptr, [&] {
+        need(s, "cable shadow");
+        s->impl->host(photons, n, flags, lit, n_lit, counts);
+    });
+}
+size_t clsimhip_cable_shadow_workspace_bytes(size_t capacity) { return cable_shadow_workspace_bytes(capacity); }
+int clsimhip_cable_shadow_device(clsimhip_cable_shadow *s, int device, const void *d_photons, const void *d_count, size_t capacity, void *d_flags, void *d_lit,
+                                 void *d_counts, void *d_workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return guarded(nullptr, [&] {
+        need(s, "cable shadow");
+        s->impl->device(device, d_photons, d_count, capacity, d_flags, d_lit, d_counts, d_workspace, workspace_bytes, static_cast<hipStream_t>(hip_stream));
+    });
+}
+int clsimhip_set_cable_shadow(clsimhip_converter *c, clsimhip_cable_shadow *s)
+{
+    return guarded(c, [&] { need(c, "converter"); c->impl.set_cable_shadow(s ? s->impl : nullptr); });
+}
+int clsimhip_get_result_cable_shadow(clsimhip_converter *c, const clsimhip_photon *photons, const uint8_t **flags, size_t *n, uint64_t counts[2])
+{
+    return guarded(c, [&] { need(c, "converter"); c->impl.result_cable_shadow(photons, flags, n, counts); });
 }
 
 } // extern "C"

@@ -7,6 +7,7 @@
 #include "mcpe.h"
 #include "mcpe_merge.h"
 #include "pmt_hits.h"
+#include "cable_shadow.h"
 #include "frame_photons.h"
 #include "pmt_series.h"
 
@@ -544,6 +545,14 @@ void Converter::setup_device_buffers(DeviceState &D)
             sl.fp.alloc(max_output_photons_, frame_photons_workspace_bytes(max_output_photons_, 0, 0),
                         {"frame photons workspace", "frame photons", "frame photons series table", "frame photons counts", "pinned frame photons counts"});
         }
+        if (shadow_) {
+            sl.d_lit.alloc(max_output_photons_, "lit photons");
+            sl.d_shadow_flags.alloc(max_output_photons_, "cable shadow flags");
+            sl.shadow_workspace_bytes = cable_shadow_workspace_bytes(max_output_photons_);
+            sl.d_shadow_workspace.alloc(sl.shadow_workspace_bytes, "cable shadow workspace");
+            sl.d_shadow_counts.alloc(4, "cable shadow counts");
+            sl.h_shadow_counts.alloc(4, "pinned cable shadow counts");
+        }
         if (series_)
             sl.series.alloc(max_output_photons_, mcpe_series_workspace_bytes(max_output_photons_, 0, 0),
                             {"MCPE series workspace", "sorted MCPEs", "MCPE series table", "MCPE series counts", "pinned MCPE series counts"});
@@ -717,10 +726,20 @@ void Converter::submit(Slot &s, Job &job)
         launch(blob);
         hip_check(hipMemcpyAsync(buffers.h_counts.get(), buffers.d_counts.get(), counts_bytes, hipMemcpyDeviceToHost, stream), counts_download);
     };
+    // what every stage below reads: the records the bunch stored, or -- behind the cable shadow stage, which runs right behind
+    // assemble_hits_kernel -- the lit ones among them and their count
+    const void *records = s.d_photons.get(), *record_count = s.d_hit_count.get();
+    if (shadow_) {
+        shadow_->device(device_, s.d_photons.get(), s.d_hit_count.get(), max_output_photons_, s.d_shadow_flags.get(), s.d_lit.get(), s.d_shadow_counts.get(),
+                        s.d_shadow_workspace.get(), s.shadow_workspace_bytes, stream);
+        hip_check(hipMemcpyAsync(s.h_shadow_counts.get(), s.d_shadow_counts.get(), 12, hipMemcpyDeviceToHost, stream), "download cable shadow counts");
+        records = s.d_lit.get();
+        record_count = s.d_shadow_counts.get();
+    }
     if (mcpe_) {
         // behind assemble_hits_kernel on the bunch's stream, over the records the bunch stored (min(hit counter, capacity)); outside
         // the start / stop pair: the propagation kernel's time stays what it was
-        mcpe_->convert_device(device_, s.d_photons.get(), s.d_hit_count.get(), max_output_photons_, s.d_mcpes.get(), max_output_photons_, s.d_mcpe_counters.get(), stream);
+        mcpe_->convert_device(device_, records, record_count, max_output_photons_, s.d_mcpes.get(), max_output_photons_, s.d_mcpe_counters.get(), stream);
         hip_check(hipMemcpyAsync(s.h_mcpe_counters.get(), s.d_mcpe_counters.get(), 20, hipMemcpyDeviceToHost, stream), "download MCPE counters");
     }
     if (series_)        // behind the hit maker, over the MCPEs it stored
@@ -737,7 +756,7 @@ void Converter::submit(Slot &s, Job &job)
     }
     if (pmt_) {
         // where the MCPE stage would run: behind assemble_hits_kernel on the bunch's stream, outside the start / stop pair
-        pmt_->convert_device(device_, s.d_photons.get(), s.d_hit_count.get(), max_output_photons_, s.d_pmt_hits.get(), max_output_photons_, s.d_pmt_counters.get(), stream);
+        pmt_->convert_device(device_, records, record_count, max_output_photons_, s.d_pmt_hits.get(), max_output_photons_, s.d_pmt_counters.get(), stream);
         hip_check(hipMemcpyAsync(s.h_pmt_counters.get(), s.d_pmt_counters.get(), 16, hipMemcpyDeviceToHost, stream), "download PMT hit counters");
     }
     if (pmt_series_)    // behind the PMT hit maker, over the hits it stored
@@ -747,7 +766,7 @@ void Converter::submit(Slot &s, Job &job)
         });
     if (frame_photons_) // behind assemble_hits_kernel, over the records the bunch stored; beside whatever hit maker ran above
         run_series_stage(s.fp, s.fp_bunch, job.fp_bunch, frame_photons_workspace_bytes, "pinned frame photons bunch", 24, "download frame photons counts", [&](const uint8_t *blob) {
-            fp_doms_->device_prepared(device_, s.d_photons.get(), s.d_hit_count.get(), max_output_photons_, job.fp_bunch.bunch, blob, s.fp.out.get(), s.fp.series.get(),
+            fp_doms_->device_prepared(device_, records, record_count, max_output_photons_, job.fp_bunch.bunch, blob, s.fp.out.get(), s.fp.series.get(),
                                       s.fp.d_counts.get(), s.fp.workspace.get(), s.fp.workspace_bytes, stream);
         });
     hip_check(hipEventRecord(s.counted.get(), stream), "event");
@@ -834,6 +853,11 @@ void Converter::finish(Slot &s, std::chrono::steady_clock::time_point &last_done
     Result r;
     const size_t min_records = s.result_min_records;
     clsimhip_photon *where = download(r.photons, result_pool_, s.d_photons.get(), hits, min_records, "download photons");
+    if (shadow_) {      // the flags of the records that cross; the counts always (lit, tested, shadowed on the device)
+        download(r.shadow_flags, shadow_pool_, s.d_shadow_flags.get(), hits, min_records, "download cable shadow flags");
+        r.shadow_counts[0] = s.h_shadow_counts.get()[1];
+        r.shadow_counts[1] = s.h_shadow_counts.get()[2];
+    }
     if (hits) {
         if (!r.photons.pinned) {
             // every pool buffer is with the caller (or the host refuses to page-lock more): the download goes into pageable memory,
@@ -883,7 +907,7 @@ void Converter::finish(Slot &s, std::chrono::steady_clock::time_point &last_done
         r.fp_masked = s.fp.h_counts.get()[3];
     }
     // a result with no photon records but a stage attached is known by a record of its own
-    if (!hits && (mcpe_ || pmt_ || frame_photons_)) r.handle.reset(new clsimhip_photon());
+    if (!hits && (mcpe_ || pmt_ || frame_photons_ || shadow_)) r.handle.reset(new clsimhip_photon());
     std::unique_ptr<std::vector<float>> histories;
     if (hits && history_entries_) {
         // ConvertPhotonHistories (OpenCL.cxx:940-989): unroll each ring into forward order
@@ -1071,6 +1095,29 @@ void Converter::result_frame_photons(const clsimhip_photon *photons, const clsim
 {
     result_series(photons, frame_photons_, "the frame photons stage is off (clsimhip_set_frame_photons)", &Result::fp_records, &Result::fp_series, &Result::fp_masked,
                   records, n, series, n_series, n_masked);
+}
+
+void Converter::set_cable_shadow(std::shared_ptr<CableShadow> s)
+{
+    guard();
+    compiled_ = false;
+    shadow_ = std::move(s);
+}
+
+void Converter::result_cable_shadow(const clsimhip_photon *photons, const uint8_t **flags, size_t *n, uint64_t counts[2])
+{
+    need_init();
+    if (!flags || !n || !counts) throw Error(CLSIMHIP_ERR_ARGUMENT, "output pointers are (null)");
+    if (!shadow_) throw Error(CLSIMHIP_ERR_STATE, "the cable shadow stage is off (clsimhip_set_cable_shadow)");
+    *flags = nullptr;
+    *n = 0;
+    counts[0] = 0; counts[1] = 0;
+    std::lock_guard<std::mutex> lk(results_mutex_);
+    auto it = handed_out_.find(photons);
+    if (it == handed_out_.end()) throw Error(CLSIMHIP_ERR_ARGUMENT, "not a result handed out by GetConversionResult (or already released)");
+    it->second.shadow_flags.get(flags, n);
+    counts[0] = it->second.shadow_counts[0];
+    counts[1] = it->second.shadow_counts[1];
 }
 
 void Converter::set_mcpe_merging(bool on, double window)

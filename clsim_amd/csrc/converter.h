@@ -26,6 +26,7 @@ namespace clsimhip {
 class McpeGenerator;            // mcpe.h
 class PmtHitGenerator;          // pmt_hits.h
 class FramePhotonDoms;          // frame_photons.h
+class CableShadow;              // cable_shadow.h
 struct alignas(16) SeriesParticle16 { uint8_t bytes[16]; };     // 16-byte aligned storage for a bunch's table and mask (mcpe_series.h)
 
 // RCCL gather of detected photons (comm.cpp)
@@ -317,6 +318,9 @@ public:
     // clsimhip_set_frame_photons: the sorting stage behind the propagation kernel's photon records (frame_photons.h), with the
     // geometry's DOMs as its list (Compile() makes it); beside either hit generator or none
     void set_frame_photons(bool on, bool keep_photons) { guard(); compiled_ = false; frame_photons_ = on; fp_keep_photons_ = keep_photons; }
+    // clsimhip_set_cable_shadow: the filtering stage right behind assemble_hits_kernel (cable_shadow.h; null: off); every stage above
+    // then reads the lit records where it reads the detected ones
+    void set_cable_shadow(std::shared_ptr<CableShadow> s);
 
     void compile();
     void initialize(uint64_t seed);
@@ -342,6 +346,7 @@ public:
                            uint64_t *n_masked);
     void result_frame_photons(const clsimhip_photon *photons, const clsimhip_frame_photon **records, size_t *n, const clsimhip_mcpe_series **series,
                               size_t *n_series, uint64_t *n_masked);
+    void result_cable_shadow(const clsimhip_photon *photons, const uint8_t **flags, size_t *n, uint64_t counts[2]);
     void release_result(const clsimhip_photon *photons);
     size_t queue_size() const;
     bool more_photons_available() const;
@@ -424,6 +429,9 @@ private:
         HostRecords<clsimhip_frame_photon> fp_records;
         HostRecords<clsimhip_mcpe_series> fp_series;
         uint64_t fp_masked = 0;
+        // with the cable shadow stage: one flag per photon record the result carries (1 = shadowed), records tested and shadowed
+        HostRecords<uint8_t> shadow_flags;
+        uint64_t shadow_counts[2] = {0, 0};
     };
 
     void guard() const { if (initialized_) throw Error(CLSIMHIP_ERR_STATE, "I3CLSimStepToPhotonConverterHIP already initialized!"); }
@@ -460,6 +468,7 @@ private:
     bool frame_photons_ = false;                // the frame photons stage runs behind the propagation kernel
     bool fp_keep_photons_ = true;
     std::shared_ptr<FramePhotonDoms> fp_doms_;  // the geometry's DOMs (Compile())
+    std::shared_ptr<CableShadow> shadow_;       // null: every detected photon goes on (the default)
     bool carries_photons() const { return !(mcpe_ && !keep_photons_) && !(pmt_ && !pmt_keep_photons_) && !(frame_photons_ && !fp_keep_photons_); }
 
     std::atomic<bool> compiled_{false}, initialized_{false};    // (atomic: set_tuning() reads them from any thread)
@@ -479,6 +488,7 @@ private:
     PmtSeriesPool pmt_series_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
     FramePhotonPool fp_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
     SeriesPool fp_series_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
+    BlobPool shadow_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
     // particle tables and masks of the bunches on their way (input queue depth + one per slot + the one being filled)
     BlobPool bunch_pool_{PinnedPoolPolicy{8, size_t{1} << 28, nullptr}};
     size_t result_capacity(size_t records, size_t min_records) const;
@@ -581,6 +591,13 @@ private:
         DeviceBuffer<clsimhip_mcpe_parent_range> d_ranges;
         DeviceBuffer<uint32_t> d_merge_counts;
         PinnedBuffer<uint32_t> h_merge_counts;
+        // with the cable shadow stage: the lit records (what every stage above reads), one flag per detected record, its workspace,
+        // three counts (lit, tested, shadowed)
+        DeviceBuffer<DevPhoton> d_lit;
+        DeviceBuffer<uint8_t> d_shadow_flags, d_shadow_workspace;
+        size_t shadow_workspace_bytes = 0;
+        DeviceBuffer<uint32_t> d_shadow_counts;
+        PinnedBuffer<uint32_t> h_shadow_counts;
         uint32_t id = 0;
         uint64_t generated = 0;
         size_t result_min_records = 0;          // of the tuning the bunch was launched with

@@ -218,6 +218,15 @@ public:
         lastFramePhotons_.clear();
         lastFramePhotonSeries_.clear();
         lastMaskedFramePhotons_ = 0;
+        lastShadowFlags_.clear();
+        lastShadowCounts_[0] = 0; lastShadowCounts_[1] = 0;
+        if (cableShadow_) {         // (before every other getter: whichever comes last releases a result without photon records)
+            const uint8_t *flags = nullptr;
+            size_t nf = 0;
+            check(clsimhip_get_result_cable_shadow(handle_, p, &flags, &nf, lastShadowCounts_));
+            lastShadowFlags_.assign(flags, flags + nf);
+            if (!n && !framePhotons_ && !mcpeGenerator_ && !pmtHitGenerator_) check(clsimhip_release_result(handle_, p));
+        }
         if (framePhotons_) {        // (fetched first: a result without photon records is released behind the last getter)
             const clsimhip_frame_photon *f = nullptr;
             const clsimhip_mcpe_series *s = nullptr;
@@ -302,6 +311,9 @@ public:
         std::size_t numMCPEs = 0;
         const clsimhip_pmt_hit *pmtHits = nullptr;  // with a PMT hit generator: the bunch's hits, valid as long as `photons`
         std::size_t numPMTHits = 0;
+        const uint8_t *shadowFlags = nullptr;       // with the cable shadow stage: one flag per photon record (1 = shadowed), valid as long as `photons`
+        std::size_t numShadowFlags = 0;
+        uint64_t shadowCounts[2] = {0, 0};          // records tested, records shadowed
         const I3CLSimPhoton *begin() const { return photons; }
         const I3CLSimPhoton *end() const { return photons + size; }
     };
@@ -313,6 +325,7 @@ public:
         v.photons = reinterpret_cast<const I3CLSimPhoton *>(p);
         if (mcpeGenerator_) check(clsimhip_get_result_mcpes(handle_, p, &v.mcpes, &v.numMCPEs));
         if (pmtHitGenerator_) check(clsimhip_get_result_pmt_hits(handle_, p, &v.pmtHits, &v.numPMTHits));
+        if (cableShadow_) check(clsimhip_get_result_cable_shadow(handle_, p, &v.shadowFlags, &v.numShadowFlags, v.shadowCounts));
         if (p) {
             std::shared_ptr<clsimhip_converter> keep = owner_;
             v.hold = std::shared_ptr<const void>(static_cast<const void *>(p), [keep](const void *q) { (void)clsimhip_release_result(keep.get(), static_cast<const clsimhip_photon *>(q)); });
@@ -418,6 +431,21 @@ public:
                 .assign(lastPMTHits_.begin() + s.first, lastPMTHits_.begin() + s.first + s.count);
         return frames;
     }
+
+    // ---- Cable shadow (include/clsimhip.h, "Cable shadow"): the reference's I3ShadowedPhotonRemoverModule as a stage right behind the
+    // propagation kernel.  Before Initialize(); shadow = nullptr switches it off.  The photons of a result stay ALL detected photons
+    // (PropagatedPhotons); the flags say which of them PropagatedPhotonsWithShadow would not hold, and every hit maker and series
+    // stage attached works on the lit ones.  The cylinder set is the caller's (clsimhip_cable_shadow_create); it may be destroyed
+    // once this call has returned. ----
+    void SetCableShadow(clsimhip_cable_shadow *shadow)
+    {
+        check(clsimhip_set_cable_shadow(handle_, shadow));
+        cableShadow_ = shadow != nullptr;
+    }
+    // of the last result: one flag per photon record it carried (1 = shadowed), records tested and records shadowed
+    const std::vector<uint8_t> &GetLastShadowFlags() const { return lastShadowFlags_; }
+    uint64_t GetLastShadowTested() const { return lastShadowCounts_[0]; }
+    uint64_t GetLastShadowShadowed() const { return lastShadowCounts_[1]; }
 
     // ---- Frame photons (include/clsimhip.h, "Frame photons"): the client module's PropagatedPhotons, an I3CompressedPhotonSeriesMap per
     // frame, made on the GPU from the bunch's photon records.  Before Initialize(); beside either hit generator or none.  A bunch is
@@ -542,6 +570,9 @@ private:
     std::vector<clsimhip_pmt_hit> lastPMTHits_;
     bool pmtSeries_ = false;
     bool framePhotons_ = false;
+    bool cableShadow_ = false;
+    std::vector<uint8_t> lastShadowFlags_;
+    uint64_t lastShadowCounts_[2] = {0, 0};
     std::vector<clsimhip_frame_photon> lastFramePhotons_;
     std::vector<clsimhip_mcpe_series> lastFramePhotonSeries_;
     uint64_t lastMaskedFramePhotons_ = 0;

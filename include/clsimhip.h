@@ -1203,6 +1203,89 @@ int clsimhip_set_frame_photons(clsimhip_converter *c, int on, int keep_photons);
 int clsimhip_get_result_frame_photons(clsimhip_converter *c, const clsimhip_photon *photons, const clsimhip_frame_photon **records, size_t *n,
                                       const clsimhip_mcpe_series **series, size_t *n_series, uint64_t *n_masked);
 
+/* ---- Cable shadow: drop detected photons whose last path crosses a cable ------------------------------------------------------
+ * The reference's I3ShadowedPhotonRemoverModule (private/clsim/shadow/): PropagatedPhotons -> PropagatedPhotonsWithShadow, which its
+ * photon-to-MCPE converter then reads.  I3ShadowedPhotonRemover::IsPhotonShadowed (I3ShadowedPhotonRemover.cxx:63-81) walks the
+ * whole I3CylinderMap -- one cylinder per DOM from python/shadow/AddCylinder.py:38-65 -- for every photon on one host thread; here
+ * that is a stage behind the propagation kernel.  Two things there cannot be restated, so the rule is this library's own: the
+ * cylinder test it calls (I3ExtraGeometryItemCylinder::DoesLineIntersect) lies outside the reference, and its start point computes
+ * dy with cos(azimuth) (:68; "This code is NOT functional at the moment").  The rule uses the corrected y component.
+ * Arithmetic: binary64 + - * / in the order written, never contracted, no sqrt, no fma; mcpe_sincos is the deterministic
+ * single-precision sine and cosine the hit makers use, its results widened.  It decides booleans only.
+ * Per record, with `distance` D (finite, >= 0):
+ *     P1 = ((double)x, (double)y, (double)z)
+ *     (st, ct) = mcpe_sincos(theta)
+ *     (sp, cp) = mcpe_sincos(phi)
+ *     dir = ((double)st*(double)cp, (double)st*(double)sp, (double)ct)
+ *     d   = D*dir
+ *     P0  = P1 - d
+ * P0 is the point D back along the arrival direction.  The reference's zenith and azimuth are those of -dir.
+ * Per cylinder, precomputed once on the host, in this order:
+ *     A  = bottom
+ *     a  = top - bottom
+ *     L2 = a.a
+ *     r2 = r*r
+ * Then, with m = P0 - A, and dot products taken as x*x' + y*y' + z*z' left to right:
+ *     ma = m.a;  da = d.a;  u1 = ma + da
+ *     if (ma < 0 && u1 < 0) || (ma > L2 && u1 > L2)  -> miss            (both ends beyond the same cap)
+ *     lo = 0; hi = 1
+ *     if da != 0:
+ *         ta = (0 - ma)/da;  tb = (L2 - ma)/da
+ *         if ta > tb: swap
+ *         if ta > lo: lo = ta
+ *         if tb < hi: hi = tb
+ *         if lo > hi: miss
+ *     else if !(ma >= 0 && ma <= L2): miss
+ *     dd = d.d;  mm = m.m;  md = m.d
+ *     al = dd*L2 - da*da;  be = md*L2 - ma*da;  ga = (mm - r2)*L2 - ma*ma
+ *     t = lo
+ *     if al > 0:
+ *         t = (0 - be)/al;  if t < lo: t = lo;  if t > hi: t = hi
+ *     hit  <=>  (al*t + (be + be))*t + ga <= 0
+ * This is "the segment meets the solid finite cylinder".  The radial condition is a convex quadratic in t.  Its minimum over the
+ * slab interval clipped to [0, 1] sits at the clamped vertex.
+ * A record is shadowed iff some cylinder hits.  The set's order cannot matter.
+ *   - A NaN in position or angles is never shadowed, because every comparison is false.
+ *   - D = 0 is a point-in-cylinder test.
+ *   - The position is used as stored.  With oversized DOMs it lies on the oversized sphere, and what that means is the caller's
+ *     business.
+ * The lit (not shadowed) records keep their input order, so the kernels and the host twin compare as arrays. */
+#define CLSIMHIP_CABLE_SHADOW_MAX_CYLINDERS 16384
+/* The cylinder set (host only): n_cylinders cylinders, top and bottom 3 doubles each, radius one.  CLSIMHIP_ERR_ARGUMENT for a
+ * non-finite value, a radius <= 0, a cylinder whose L2 is zero or not finite, a distance that is negative or not finite,
+ * n_cylinders = 0 and n_cylinders > CLSIMHIP_CABLE_SHADOW_MAX_CYLINDERS (which bounds the work of a launch at capacity x 16 384
+ * tests). */
+typedef struct clsimhip_cable_shadow clsimhip_cable_shadow;
+int clsimhip_cable_shadow_create(size_t n_cylinders, const double *top, const double *bottom, const double *radius, double distance,
+                                 clsimhip_cable_shadow **out);
+void clsimhip_cable_shadow_destroy(clsimhip_cable_shadow *s);
+const char *clsimhip_cable_shadow_last_error(const clsimhip_cable_shadow *s);
+/* The host twin: flags holds n bytes (1 = shadowed), lit n records (the records with flag 0, in input order; *n_lit of them);
+ * counts (may be NULL) receives records tested and records shadowed. */
+int clsimhip_cable_shadow_host(const clsimhip_cable_shadow *s, const clsimhip_photon *photons, size_t n, uint8_t *flags, clsimhip_photon *lit,
+                               size_t *n_lit, uint64_t counts[2]);
+/* bytes of device memory the kernels need beside their input and output, for up to `capacity` records */
+size_t clsimhip_cable_shadow_workspace_bytes(size_t capacity);
+/* The kernels, on photon records that live in HBM: min(*d_count, capacity) records of d_photons.  d_flags: `capacity` bytes, of
+ * which the first min(*d_count, capacity) are written; d_lit: `capacity` records; d_photons, d_lit and d_workspace
+ * (clsimhip_cable_shadow_workspace_bytes(capacity) bytes) 16-byte aligned; d_counts: three uint32 -- records lit, tested, shadowed
+ * (CLSIMHIP_ERR_ARGUMENT for a misaligned pointer or a workspace that is too small; nothing is launched then).  (d_lit, d_counts)
+ * pair with every *_device call above as (d_photons, d_count) do.  The kernels are asynchronous on hip_stream (NULL = default
+ * stream); the first call on a device copies the cylinder table there, nothing else waits for the device. */
+int clsimhip_cable_shadow_device(clsimhip_cable_shadow *s, int device, const void *d_photons, const void *d_count, size_t capacity, void *d_flags,
+                                 void *d_lit, void *d_counts, void *d_workspace, size_t workspace_bytes, void *hip_stream);
+/* The stage right behind every bunch's propagation kernel, on the bunch's stream (s = NULL: off, the default -- no launch, no
+ * allocation, no byte changes anywhere).  Before Initialize() only (CLSIMHIP_ERR_STATE after).  With it on, the MCPE generator with
+ * its series and merging, the PMT hit generator with its series and the frame photons stage read the lit records where they read the
+ * detected ones.  The 80-byte photons a result carries stay ALL detected photons -- the propagator's result, and the RNG states are
+ * untouched; the reference keeps both maps too.  The set is fixed at Initialize(), like the geometry; the object may be destroyed
+ * once this call has returned. */
+int clsimhip_set_cable_shadow(clsimhip_converter *c, clsimhip_cable_shadow *s);
+/* Flags of the result `photons` belongs to, aligned with its photon records (1 = shadowed; *n = the records the result carries, 0
+ * with them NULL when the records did not cross to the host), and counts: records tested and shadowed, always delivered.  Valid
+ * until clsimhip_release_result(c, photons).  CLSIMHIP_ERR_STATE without clsimhip_set_cable_shadow. */
+int clsimhip_get_result_cable_shadow(clsimhip_converter *c, const clsimhip_photon *photons, const uint8_t **flags, size_t *n, uint64_t counts[2]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,31 @@
+"""Cable shadow through the C++ adapter (clsim_amd/cxx/cable_shadow_adapter_test.cxx): SetCableShadow and the accessors for the last
+result's flags and counts, compiled with g++ against include/clsimhip.h and the adapter's stand-ins for the framework's types, and
+linked to libclsimhip.so."""
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CXX = os.path.join(ROOT, "clsim_amd", "cxx")
+
+
+def build(tmp_path):
+    exe = str(tmp_path / "cable_shadow_adapter_test")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-o", exe, os.path.join(CXX, "cable_shadow_adapter_test.cxx"),
+                           "-L" + os.path.join(ROOT, "clsim_amd"), "-lclsimhip", "-Wl,-rpath," + os.path.join(ROOT, "clsim_amd")])
+    return exe
+
+
+def test_adapter_takes_the_cylinder_set(tmp_path):
+    out = subprocess.check_output([build(tmp_path)], text=True)
+    assert "configured with the cable shadow stage" in out and "cable shadow adapter ok" in out
+
+
+@pytest.mark.gpu
+def test_adapter_returns_the_flags_of_its_result(tmp_path):
+    out = subprocess.check_output([build(tmp_path), "run"], text=True)
+    m = re.search(r"identifier 42 photons (\d+) shadowed (\d+) lit (\d+) equal to the host twin", out)
+    assert m and 0 < int(m.group(2)) < int(m.group(1)) and int(m.group(2)) + int(m.group(3)) == int(m.group(1)), out
+    assert out.rstrip().endswith("cable shadow adapter ok")

@@ -21,6 +21,12 @@ around clsimhip_pmt_series_device, best of --repeats; needs a GPU).
 
 --frame-photons N: the frame photons' host twin instead (clsimhip_frame_photons_host), in photon records per second, on N synthetic
 records at 5160 DOMs dealt to 1000 particles in 10 frames; --device likewise (clsimhip_frame_photons_device).
+
+--cable-shadow N: the cable shadow's host twin instead (clsimhip_cable_shadow_host), in photon records and in segment-cylinder tests
+per second, on N records against --cylinders cylinders (default 5160: one cable beside every DOM of an 86 x 60 detector, in detector
+coordinates like the reference's I3CylinderMap, so that a record can only meet the cable of its own DOM and walks the whole set
+otherwise); --device adds the device stage's time for the same input (HIP events around clsimhip_cable_shadow_device, best of
+--repeats; needs a GPU) -- the host twin then runs once, for the comparison.
 """
 import argparse
 import ctypes as C
@@ -175,6 +181,52 @@ def frame_photons_rate(args):
     print(json.dumps(line))
 
 
+def cable_shadow_rate(args):
+    n, c = args.cable_shadow, args.cylinders
+    rng = np.random.default_rng(1)
+    # an 86 x 60 detector: strings 125 m apart on a square grid, DOMs 17 m apart; the cable 20 cm beside its DOM, 1 m long, 2.3 cm thick
+    k = np.arange(c)
+    dom = np.stack([125.0 * ((k // 60) % 10) - 560.0, 125.0 * ((k // 60) // 10) - 500.0, 500.0 - 17.0 * (k % 60)], axis=1)
+    azimuth = rng.uniform(0.0, 2.0 * np.pi, c)
+    beside = dom + 0.2 * np.stack([np.cos(azimuth), np.sin(azimuth), np.zeros(c)], axis=1)
+    shadow = CV.CableShadow(beside + [0.0, 0.0, 0.5], beside - [0.0, 0.0, 0.5], 0.023, 1.0)
+    base = np.concatenate([M.fixture_photons(name) for name in M.FIXTURES if name != "lea_no_pancake"])
+    m = np.ascontiguousarray(np.tile(base, -(-n // len(base)))[:n])
+    at = rng.integers(0, c, n)
+    for i, name in enumerate("xyz"):            # the record's position on its DOM's sphere, in detector coordinates
+        m[name] = (m[name].astype(np.float64) + dom[at, i]).astype(np.float32)
+    best = float("inf")
+    for _ in range(1 if args.device else args.repeats):
+        t0 = time.perf_counter()
+        flags, lit, counts = shadow.MakeHost(m)
+        best = min(best, time.perf_counter() - t0)
+    tests = float(n) * c            # (an upper bound: a shadowed record stops at its cylinder)
+    line = {"photon_records": n, "cylinders": c, "shadowed": counts["shadowed"], "host_seconds": best, "host_records_per_s": n / best,
+            "host_ns_per_test": best / tests * 1e9, "threads": 1}
+    if args.device:
+        import torch
+        dev = torch.device("cuda", 0)
+        d_in = torch.from_numpy(m.view(np.uint8).reshape(-1, 80).copy()).to(dev)
+        d_cnt = torch.tensor([n], dtype=torch.int32, device=dev)
+        d_flags, d_lit = torch.zeros(n, dtype=torch.uint8, device=dev), torch.zeros((n, 80), dtype=torch.uint8, device=dev)
+        d_counts = torch.zeros(4, dtype=torch.int32, device=dev)
+        ws = CV.CableShadow.WorkspaceBytes(n)
+        d_ws = torch.zeros(ws, dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream().cuda_stream
+        times = []
+        for _ in range(args.repeats + 1):
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            shadow.MakeDevice(d_in.data_ptr(), d_cnt.data_ptr(), n, d_flags.data_ptr(), d_lit.data_ptr(), d_counts.data_ptr(), d_ws.data_ptr(), ws, stream=stream)
+            stop.record()
+            torch.cuda.synchronize()
+            times.append(start.elapsed_time(stop) * 1e-3)
+        assert [int(v) for v in d_counts.cpu()[:3]] == [len(lit), n, counts["shadowed"]]
+        assert d_flags.cpu().numpy().tobytes() == flags.tobytes() and d_lit.cpu().numpy()[:len(lit)].tobytes() == lit.tobytes()
+        line.update(device_seconds=min(times[1:]), device_records_per_s=n / min(times[1:]), device_ns_per_test=min(times[1:]) / tests * 1e9)
+    print(json.dumps(line))
+
+
 def merge_rate(args):
     from tests import mcpe_merge_common as MM
     from tests import mcpe_series_common as S
@@ -228,7 +280,11 @@ def main():
     ap.add_argument("--merge", action="store_true")
     ap.add_argument("--pmt-series", type=int, default=0, metavar="N")
     ap.add_argument("--frame-photons", type=int, default=0, metavar="N")
+    ap.add_argument("--cable-shadow", type=int, default=0, metavar="N")
+    ap.add_argument("--cylinders", type=int, default=5160)
     args = ap.parse_args()
+    if args.cable_shadow:
+        return cable_shadow_rate(args)
     if args.frame_photons:
         return frame_photons_rate(args)
     if args.pmt_series:

@@ -4,13 +4,15 @@ the MCPE series stage, steps dealt to 1000 particles in 10 frames: the run to pu
 the stage's kernels beside the propagation kernel.  Prints the counts and the host-side wall time of the bunch.
 
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/mcpe_series_profile.py [--steps 1048576] [--no-series] [--merge-window NS]
-                                                                                   [--pmt] [--frame-photons]
+                                                                                   [--pmt] [--frame-photons] [--cable-shadow]
 
 --merge-window NS: the MCPE merging stage behind the series stage, with that window.
 --pmt: a 31-PMT module (tests/pmt_common.py) at every DOM instead: the multi-PMT hit maker and the PMT series stage (--no-series:
 the hit maker alone).
 --frame-photons: no hit maker; the frame photons stage on the bunch's photon records, which stay on the device (--no-series: the
 propagation alone, records downloaded).
+--cable-shadow: the cable shadow stage in front of whichever stages the other options choose, with one cable beside every DOM of
+the geometry (5 160 cylinders, in the DOM's own frame: tests/cable_shadow_common.py); the line then carries its two counts.
 """
 import argparse
 import json
@@ -26,11 +28,18 @@ from tests import common                        # noqa: E402
 from tests import mcpe_common as M              # noqa: E402
 
 
+def cable_shadow_of(args, cfg):
+    if not args.cable_shadow:
+        return None
+    from tests import cable_shadow_common as S
+    return S.make_shadow(S.cylinder_set(len(cfg["geom"]["string_ids"])))
+
+
 def pmt_bunch(args, cfg, bias):
     from tests import pmt_common as PC
     conv = CV.initializeHIP(0, CV.I3CLSimSimpleGeometry.from_dict(cfg["geom"]), cfg["med_p"], bias, common.product_generators(cfg, bias), pancakeFactor=5.0,
                             stopDetectedPhotons=True, approximateNumberOfWorkItems=args.steps, pmtHitGenerator=PC.geometry_generator(cfg),
-                            keepPhotons=False, pmtSeries=not args.no_series)
+                            keepPhotons=False, pmtSeries=not args.no_series, cableShadow=cable_shadow_of(args, cfg))
     steps = common.steps_for(cfg, args.steps, seed=3).copy()
     steps["id"] = np.arange(len(steps)) % 1000
     p = np.zeros(1000, dtype=CV.MCPE_PARTICLE_DTYPE)
@@ -44,12 +53,13 @@ def pmt_bunch(args, cfg, bias):
         r = conv.GetConversionResult()
         wall = time.perf_counter() - t0
     print(json.dumps({"steps": len(steps), "photons": int(steps["num"].sum()), "pmt_hits": len(r.pmt_hits),
-                      "pmt_series": None if r.pmt_series is None else len(r.pmt_series), "wall_seconds_second_bunch": wall}))
+                      "pmt_series": None if r.pmt_series is None else len(r.pmt_series), "cable_shadow": r.shadow_counts, "wall_seconds_second_bunch": wall}))
 
 
 def frame_photons_bunch(args, cfg, bias):
     conv = CV.initializeHIP(0, CV.I3CLSimSimpleGeometry.from_dict(cfg["geom"]), cfg["med_p"], bias, common.product_generators(cfg, bias), pancakeFactor=5.0,
-                            stopDetectedPhotons=True, approximateNumberOfWorkItems=args.steps, keepPhotons=False, framePhotons=not args.no_series)
+                            stopDetectedPhotons=True, approximateNumberOfWorkItems=args.steps, keepPhotons=False, framePhotons=not args.no_series,
+                            cableShadow=cable_shadow_of(args, cfg))
     steps = common.steps_for(cfg, args.steps, seed=3).copy()
     steps["id"] = np.arange(len(steps)) % 1000
     p = np.zeros(1000, dtype=CV.MCPE_PARTICLE_DTYPE)
@@ -64,7 +74,8 @@ def frame_photons_bunch(args, cfg, bias):
         wall = time.perf_counter() - t0
     print(json.dumps({"steps": len(steps), "photons": int(steps["num"].sum()), "photon_records": len(r[1]),
                       "frame_photons": None if r.frame_photons is None else len(r.frame_photons),
-                      "frame_photon_series": None if r.frame_photon_series is None else len(r.frame_photon_series), "wall_seconds_second_bunch": wall}))
+                      "frame_photon_series": None if r.frame_photon_series is None else len(r.frame_photon_series), "cable_shadow": r.shadow_counts,
+                      "wall_seconds_second_bunch": wall}))
 
 
 def main():
@@ -74,6 +85,7 @@ def main():
     ap.add_argument("--merge-window", type=float, default=None, metavar="NS")
     ap.add_argument("--pmt", action="store_true")
     ap.add_argument("--frame-photons", action="store_true")
+    ap.add_argument("--cable-shadow", action="store_true")
     args = ap.parse_args()
     cfg = common.config("mie")
     g = cfg["geom"]
@@ -86,7 +98,7 @@ def main():
         return frame_photons_bunch(args, cfg, bias)
     conv = CV.initializeHIP(0, CV.I3CLSimSimpleGeometry.from_dict(g), cfg["med_p"], bias, common.product_generators(cfg, bias), pancakeFactor=5.0,
                             stopDetectedPhotons=True, approximateNumberOfWorkItems=args.steps, mcpeGenerator=gen, keepPhotons=False,
-                            mcpeSeries=not args.no_series, mcpeMergeWindow=args.merge_window)
+                            mcpeSeries=not args.no_series, mcpeMergeWindow=args.merge_window, cableShadow=cable_shadow_of(args, cfg))
     steps = common.steps_for(cfg, args.steps, seed=3).copy()
     steps["id"] = np.arange(len(steps)) % 1000
     p = np.zeros(1000, dtype=CV.MCPE_PARTICLE_DTYPE)
@@ -101,7 +113,8 @@ def main():
         wall = time.perf_counter() - t0
     print(json.dumps({"steps": len(steps), "photons": int(steps["num"].sum()), "mcpes": len(r.mcpes),
                       "series": None if r.series is None else len(r.series),
-                      "merged": None if r.merged is None else len(r.merged), "parents": None if r.parents is None else len(r.parents), "wall_seconds_second_bunch": wall}))
+                      "merged": None if r.merged is None else len(r.merged), "parents": None if r.parents is None else len(r.parents),
+                      "cable_shadow": r.shadow_counts, "wall_seconds_second_bunch": wall}))
 
 
 if __name__ == "__main__":
