@@ -39,6 +39,19 @@ MIN_HITS = 50                       # the bar of the existing parity tests (test
 # what Compile() reports.)
 NO_FAST_KEYS = frozenset()
 
+# (key, mode, "fast" | "generic") whose pooled kernel cannot be had compiled at run time with the configuration as literals ("baked_kernel"):
+# none.  Filled from the CPU compile of tests/test_kernel_matrix.py only (clsimhip_baked_compile: hiprtc needs no device), never from a GPU
+# run, and compared with it both ways; for an entry the GPU tests expect "fallback" with a reason -- and the same records.
+BAKED_OUT_OF_REACH = frozenset()
+BAKED_MAX_VGPRS = 80                # prop_pool_kernel.hip.h: the launcher runs the precompiled kernel instead of a module above this, or with scratch
+BAKED_MAX_SECONDS = 10.0            # the bound of tests/test_baked_kernel.py
+
+
+def baked_kernel_name(lengths, tilt, aniso, flasher, fast, keep):
+    """baked_source.cpp: baked_kernel_name, restated -- the one kernel of a run-time compiled code object"""
+    return "_ZN8clsimhip16prop_pool_kernelILi%dELb%dELb%dELb%dELb%dELb%dEEEvNS_7KParamsE" % (lengths, tilt, aniso, flasher, fast, keep)
+
+
 ANISO_FIELDS = ("has_anisotropy", "aniso_azimuth", "aniso_k1", "aniso_k2", "has_pre_transform", "pre_renormalize", "pre_matrix",
                 "has_post_transform", "post_renormalize", "post_matrix")
 TILT_FIELDS = ("has_tilt", "tilt_num_distances", "tilt_num_z", "tilt_distances", "tilt_z_coordinates", "tilt_z_corrections", "tilt_azimuth")

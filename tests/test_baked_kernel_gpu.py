@@ -1,8 +1,11 @@
 """The pooled kernel compiled at run time for one configuration (clsim_amd/csrc/baked_kernel.h) against the precompiled kernel
 and the oracle.
 
-Six keys of tests/kernel_matrix.py, chosen so that every template axis of prop_pool_kernel is compiled with its constants baked
-once: the three lengths kinds, tilt on and off, anisotropy on and off, a flasher key, one key without STOP_PHOTONS_ON_DETECTION.
+Every template instantiation runs in this form in tests/test_kernel_matrix_gpu.py, every value of a configuration switch in
+tests/test_baked_switches_gpu.py.  Here: what surrounds the kernel -- the cache of modules (two media of one instantiation in one
+process), slices, padding, the fallback without the compiler library, and the launcher's own decision with tuning untouched
+("baked_kernel" = 1: where it pays and only there) -- on six keys of tests/kernel_matrix.py: the three lengths kinds, tilt on and off,
+anisotropy on and off, a flasher key, one key without STOP_PHOTONS_ON_DETECTION.
 Per key one oracle table set, two bunches of 1 024 steps on continuing RNG streams, and two converters with the pooled kernel
 forced ("kernel" = pool): "baked_kernel" = 0 (precompiled) and 2 (run-time compiled also on small bunches).  The bar is the one of
 tests/test_parity_gpu.py: sorted 80-byte records, RNG state words and hit count equal -- between the two converters and between the
@@ -180,3 +183,45 @@ def test_without_the_compiler_library_the_precompiled_kernel_runs_and_says_so():
     assert [l[1:] for l in lines] == want
     assert "cannot load hiprtc" in child.stdout
     assert child.stderr.count("runs precompiled") == 1, child.stderr         # said once, not per launch
+
+
+# ---- the default decision: "baked_kernel" = 1, "kernel" = auto, nothing set by the caller ----
+DEFAULT_STEPS = 524288              # converter.cpp: kPooledKernelMinSteps -- from here on a bunch takes the pooled kernel unasked
+DEFAULT_LIVE = 1024                 # steps that carry photons; the rest has num = 0, so the oracle's cost is that of 1 024 steps
+
+
+@pytest.mark.parametrize("name,n,kernel,state", [
+    ("mie", DEFAULT_STEPS, "pool", "baked"),                    # IceCube lengths, tilt, FAST: bench.py's C2 -- the instantiation that gains
+    ("lea", DEFAULT_STEPS, "pool", "unused"),                   # anisotropy: pooled, but the precompiled kernel (prop_pool_kernel.hip.h: kBakedPays)
+    ("mie", DEFAULT_STEPS - 256, "classic", "unused"),          # one workgroup of steps below the threshold: the classic kernel
+], ids=["mie-at-the-threshold", "lea-at-the-threshold", "mie-below-the-threshold"])
+def test_untouched_tuning_runs_the_baked_kernel_where_it_pays_and_only_there(name, n, kernel, state):
+    """What production does by default, observed: no tuning key is set here.  Records and RNG words equal the oracle's; the words of
+    the steps without photons stay what they were."""
+    from clsim_amd import converter as CV
+    cfg = common.config(name)
+    x, a = common.streams(DEFAULT_STEPS)                        # (once per module: common.streams keeps them)
+    x, a = x[:n], a[:n]
+    steps = np.resize(common.steps_for(cfg, DEFAULT_LIVE, seed=41), n)
+    steps["num"][DEFAULT_LIVE:] = 0
+    T = common.oracle_tables(cfg)
+    ph_o, cnt_o, x_o, _ = capi.propagate(T, steps, x, a, threads=8)
+    ph_o = capi.replace_indices_with_ids(ph_o, T.geo)
+    assert cnt_o >= KM.MIN_HITS
+    bias = CV.GetIceCubeDOMAcceptance()
+    conv = CV.initializeHIP(0, CV.I3CLSimSimpleGeometry.from_dict(cfg["geom"]), cfg["med_p"], bias, common.product_generators(cfg, bias),
+                            pancakeFactor=5.0, approximateNumberOfWorkItems=n, streams=(x, a))
+    assert conv.GetTuning("kernel") == 0 and conv.GetTuning("baked_kernel") == 1 and conv.GetTuning("generic_kernels") == 0
+    assert conv.KernelForBunch(n) == kernel
+    conv.EnqueueSteps(steps, 7)
+    ident, ph_p = conv.GetConversionResult()
+    info, launched = conv.GetBakedInfo(), conv.GetLastLaunch()
+    print("%s, %d steps: %s, %s, %d photons detected" % (name, n, launched, info, cnt_o))
+    assert ident == 7 and len(ph_p) == cnt_o
+    assert launched["family"] == kernel and launched["fast"] is True, launched
+    assert info["state"] == state and info["why"] == "", info
+    assert (len(info["key"]) == 32) == (state == "baked"), info
+    assert common.sort_photons(ph_o).tobytes() == common.sort_photons(ph_p).tobytes()
+    x_p = conv.GetRNGState(n)
+    assert np.array_equal(x_p, x_o)
+    assert np.array_equal(x_p[DEFAULT_LIVE:], x[DEFAULT_LIVE:]) and not np.array_equal(x_p[:DEFAULT_LIVE], x[:DEFAULT_LIVE])
