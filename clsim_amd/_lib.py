@@ -140,6 +140,9 @@ SYMBOLS = [
     "clsimhip_get_result_frame_photons",
     "clsimhip_cable_shadow_create", "clsimhip_cable_shadow_destroy", "clsimhip_cable_shadow_last_error", "clsimhip_cable_shadow_host",
     "clsimhip_cable_shadow_workspace_bytes", "clsimhip_cable_shadow_device", "clsimhip_set_cable_shadow", "clsimhip_get_result_cable_shadow",
+    "clsimhip_event_statistics_add", "clsimhip_event_statistics_weight", "clsimhip_event_statistics_host",
+    "clsimhip_event_statistics_workspace_bytes", "clsimhip_event_statistics_device", "clsimhip_set_event_statistics",
+    "clsimhip_get_result_event_statistics",
 ]
 
 # clsimhip_get_last_launch: CLSIMHIP_FAMILY_* and CLSIMHIP_LENGTHS_* by name
@@ -346,12 +349,20 @@ def load():
         "clsimhip_cable_shadow_device": (i32, [vp, i32, vp, vp, sz, vp, vp, vp, vp, sz, vp]),
         "clsimhip_set_cable_shadow": (i32, [vp, vp]),
         "clsimhip_get_result_cable_shadow": (i32, [vp, vp, C.POINTER(vp), C.POINTER(sz), vp]),
+        "clsimhip_event_statistics_add": (i32, [vp, vp]),
+        "clsimhip_event_statistics_weight": (dbl, [vp, vp]),
+        "clsimhip_event_statistics_host": (i32, [vp, sz, vp, sz, vp, sz, vp, sz, vp, vp]),
+        "clsimhip_event_statistics_workspace_bytes": (sz, [sz, sz]),
+        "clsimhip_event_statistics_device": (i32, [i32, vp, sz, vp, vp, sz, vp, sz, vp, sz, vp, vp, vp, sz, vp]),
+        "clsimhip_set_event_statistics": (i32, [vp, i32]),
+        "clsimhip_get_result_event_statistics": (i32, [vp, vp, C.POINTER(vp), C.POINTER(sz), vp]),
         "clsimhip_tabulator_write_fits_file": (i32, [vp, C.c_char_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double), sz]),
     }
     for name in SYMBOLS:
-        # (A/B measurements load an older build through CLSIMHIP_LIB: it may lack the entries of the run-time compiled kernel, which
-        # bench.py does not call)
-        if name in ("clsimhip_baked_info", "clsimhip_baked_compile", "clsimhip_baked_set_compiler_library") and LIB_PATH != DEFAULT_LIB_PATH and not hasattr(lib, name):
+        # (A/B measurements load an older build through CLSIMHIP_LIB: it may lack the entries of the run-time compiled kernel and of the event
+        # statistics stage, which bench.py does not call)
+        newer = name in ("clsimhip_baked_info", "clsimhip_baked_compile", "clsimhip_baked_set_compiler_library") or "event_statistics" in name
+        if newer and LIB_PATH != DEFAULT_LIB_PATH and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol
         fn.restype, fn.argtypes = sig[name]

@@ -665,6 +665,64 @@ class CableShadow:
 CABLE_SHADOW_COUNTS = ("tested", "shadowed")
 CABLE_SHADOW_MAX_CYLINDERS = 16384
 
+# Event statistics (include/clsimhip.h): one record per entry of the bunch's particle table (one without a table) -- counts, and the
+# weight sums as exact integers in units of 2^-149 (six little-endian uint64 words, two's complement) with their +inf, -inf, NaN terms
+EVENT_STATISTICS_DTYPE = np.dtype([("id", "<u4"), ("frame", "<u4"), ("generatedCount", "<u8"), ("atDOMsCount", "<u8"), ("generatedSum", "<u8", (6,)),
+                                   ("atDOMsSum", "<u8", (6,)), ("generatedSpecial", "<u4", (3,)), ("atDOMsSpecial", "<u4", (3,))])
+EVENT_STATISTICS_COUNTERS = ("unknown_particle", "masked", "unknown_step_particle")
+assert EVENT_STATISTICS_DTYPE.itemsize == 144
+
+
+class EventStatistics:
+    """The event statistics stage on records (include/clsimhip.h: "Event statistics"): the client module's I3CLSimEventStatistics
+    (private/clsim/I3CLSimClientModule.cxx:513-520, 386-405) with exact integer weight sums.  Nothing to configure: static methods."""
+
+    @staticmethod
+    def MakeHost(steps, photons, particles=None, masked=None):
+        """(records, counters): the host twin.  steps: STEP_DTYPE; photons: PHOTON_DTYPE with string and OM IDs; particles:
+        MCPE_PARTICLE_DTYPE, strictly increasing in `id` (None: no table -- one record, id 0 and frame 0); masked: MCPE_MASK_DTYPE.
+        records: EVENT_STATISTICS_DTYPE, one per table entry in table order; counters = {name: count} (EVENT_STATISTICS_COUNTERS)"""
+        steps = np.ascontiguousarray(steps if steps is not None else [], dtype=STEP_DTYPE)
+        photons = np.ascontiguousarray(photons if photons is not None else [], dtype=PHOTON_DTYPE)
+        keep, pp, n_p, masked, mp, n_m = _series_inputs(particles, masked)
+        out = np.zeros(n_p if particles is not None else 1, dtype=EVENT_STATISTICS_DTYPE)
+        counters = np.zeros(3, dtype=np.uint64)
+        _check(_lib.load().clsimhip_event_statistics_host(C.c_void_p(steps.ctypes.data if len(steps) else None), len(steps),
+                                                          C.c_void_p(photons.ctypes.data if len(photons) else None), len(photons), pp, n_p, mp, n_m,
+                                                          C.c_void_p(out.ctypes.data if len(out) else None), counters.ctypes.data_as(C.c_void_p)))
+        return out, dict(zip(EVENT_STATISTICS_COUNTERS, (int(c) for c in counters)))
+
+    @staticmethod
+    def WorkspaceBytes(n_particles=0, n_masked=0):
+        return int(_lib.load().clsimhip_event_statistics_workspace_bytes(int(n_particles), int(n_masked)))
+
+    @staticmethod
+    def MakeDevice(d_steps, n_steps, d_photons, d_count, capacity, d_out, d_counters, d_workspace, workspace_bytes, particles=None, masked=None,
+                   device=0, stream=0):
+        """the kernels on device-resident steps and photon records (addresses): n_steps steps and min(*d_count, capacity) photons;
+        d_out: one EVENT_STATISTICS_DTYPE record per table entry (one without a table), d_counters: four uint32
+        (EVENT_STATISTICS_COUNTERS, then the records written), d_workspace: WorkspaceBytes(len(particles), len(masked)) bytes.
+        particles / masked are host arrays as for MakeHost."""
+        keep, pp, n_p, masked, mp, n_m = _series_inputs(particles, masked)
+        _check(_lib.load().clsimhip_event_statistics_device(int(device), C.c_void_p(d_steps), int(n_steps), C.c_void_p(d_photons), C.c_void_p(d_count),
+                                                            int(capacity), pp, n_p, mp, n_m, C.c_void_p(d_out), C.c_void_p(d_counters),
+                                                            C.c_void_p(d_workspace), int(workspace_bytes), C.c_void_p(stream)))
+
+    @staticmethod
+    def Add(acc, rec):
+        """acc + rec as a new record (clsimhip_event_statistics_add): sums with carry, counts, special counters; acc's id and frame"""
+        out = np.array(acc, dtype=EVENT_STATISTICS_DTYPE).reshape(1).copy()
+        rec = np.array(rec, dtype=EVENT_STATISTICS_DTYPE).reshape(1)
+        _check(_lib.load().clsimhip_event_statistics_add(C.c_void_p(out.ctypes.data), C.c_void_p(rec.ctypes.data)))
+        return out[0]
+
+    @staticmethod
+    def Weight(words, special):
+        """a sum as a float (clsimhip_event_statistics_weight): rounded once to nearest-even; NaN / +-inf from the special counters"""
+        words = np.ascontiguousarray(words, dtype=np.uint64).reshape(6)
+        special = np.ascontiguousarray(special, dtype=np.uint32).reshape(3)
+        return float(_lib.load().clsimhip_event_statistics_weight(C.c_void_p(words.ctypes.data), C.c_void_p(special.ctypes.data)))
+
 
 class ConversionResult(tuple):
     """What GetConversionResult / GetConversionResultInPlace return: the tuple (identifier, photons[, histories]) / (identifier,
@@ -707,6 +765,7 @@ class I3CLSimStepToPhotonConverterHIP:
         self._pmt_series = False
         self._frame_photons = False
         self._shadow = None
+        self._event_statistics = False
 
     def __del__(self):
         try:
@@ -786,6 +845,12 @@ class I3CLSimStepToPhotonConverterHIP:
         photons, with `shadow_flags` aligned to them and `shadow_counts`.  Before Initialize() only."""
         self._call("clsimhip_set_cable_shadow", shadow._h if shadow is not None else None)
         self._shadow = shadow
+    def SetEventStatistics(self, on=True):
+        """the counting stage over every bunch's steps and ALL its detected photons (also with a cable shadow bound): per particle of
+        the bunch's table, photons generated and at DOMs as counts and exact weight sums (result attributes `event_statistics`,
+        EVENT_STATISTICS_DTYPE, and `event_statistics_counters`).  Works with keepPhotons=False.  Before Initialize() only."""
+        self._call("clsimhip_set_event_statistics", int(bool(on)))
+        self._event_statistics = bool(on)
     def SetMCPEMerging(self, window, on=True):
         """the merging stage behind the series stage: records of a series within `window` of their group's opener become one merged
         record (result attributes `merged`, `merged_series`, `parents`, `parent_ranges`; `mcpes` and `series` stay the unmerged
@@ -815,8 +880,8 @@ class I3CLSimStepToPhotonConverterHIP:
     # ---- steady state ----
     def EnqueueSteps(self, steps, identifier, particles=None, masked=None):
         """particles (MCPE_PARTICLE_DTYPE, strictly increasing in `id`) and masked (MCPE_MASK_DTYPE): the bunch's particle table and
-        ignored modules for the MCPE series stage (SetMCPESeries) or the PMT series stage (SetPMTSeries); without them the bunch is
-        one frame, 0, with no shift"""
+        ignored modules for the MCPE series stage (SetMCPESeries), the PMT series stage (SetPMTSeries), the frame photons stage
+        (SetFramePhotons) or the event statistics stage (SetEventStatistics); without them the bunch is one frame, 0, with no shift"""
         if steps is None:
             raise I3CLSimStepToPhotonConverter_exception("Steps pointer is (null)!", _lib.ERR_ARGUMENT)
         steps = np.ascontiguousarray(steps, dtype=STEP_DTYPE)
@@ -873,7 +938,18 @@ class I3CLSimStepToPhotonConverterHIP:
 
     def _has_handle(self):
         """a result without photon records still has a handle to release when a hit maker is attached"""
-        return self._mcpe is not None or self._pmt is not None or self._frame_photons or self._shadow is not None
+        return self._mcpe is not None or self._pmt is not None or self._frame_photons or self._shadow is not None or self._event_statistics
+
+    def GetResultEventStatistics(self, ptr):
+        """copies of the event statistics of the result `ptr` belongs to: (records, {counter: count}); CLSIMHIP_ERR_STATE without
+        SetEventStatistics"""
+        rp, rn, counters = C.c_void_p(), C.c_size_t(), np.zeros(3, dtype=np.uint64)
+        self._call("clsimhip_get_result_event_statistics", ptr, C.byref(rp), C.byref(rn), counters.ctypes.data_as(C.c_void_p))
+        return self._copy_records(rp, rn.value, EVENT_STATISTICS_DTYPE), dict(zip(EVENT_STATISTICS_COUNTERS, (int(c) for c in counters)))
+
+    def _attach_event_statistics(self, result, es):
+        if es is not None:
+            result.event_statistics, result.event_statistics_counters = es
 
     def GetResultCableShadow(self, ptr):
         """copies of the cable shadow flags of the result `ptr` belongs to and its counts: (flags, {"tested", "shadowed"});
@@ -934,6 +1010,7 @@ class I3CLSimStepToPhotonConverterHIP:
             pmt_hits = self._result_pmt_hits(ptr)
             fp = self.GetResultFramePhotons(ptr) if self._frame_photons else None
             shadow = self.GetResultCableShadow(ptr) if self._shadow is not None else None
+            es = self.GetResultEventStatistics(ptr) if self._event_statistics else None
         finally:
             if n.value or self._has_handle():
                 self._call("clsimhip_release_result", ptr)
@@ -942,6 +1019,7 @@ class I3CLSimStepToPhotonConverterHIP:
         self._attach_pmt_hits(result, pmt_hits)
         self._attach_frame_photons(result, fp)
         self._attach_cable_shadow(result, shadow)
+        self._attach_event_statistics(result, es)
         return result
 
     def GetConversionResultInPlace(self):
@@ -956,6 +1034,7 @@ class I3CLSimStepToPhotonConverterHIP:
             pmt_hits = self._result_pmt_hits(ptr)
             fp = self.GetResultFramePhotons(ptr) if self._frame_photons else None
             shadow = self.GetResultCableShadow(ptr) if self._shadow is not None else None
+            es = self.GetResultEventStatistics(ptr) if self._event_statistics else None
         except Exception:
             if n.value or self._has_handle():
                 self._call("clsimhip_release_result", ptr)
@@ -973,6 +1052,7 @@ class I3CLSimStepToPhotonConverterHIP:
         self._attach_pmt_hits(result, pmt_hits)
         self._attach_frame_photons(result, fp)
         self._attach_cable_shadow(result, shadow)
+        self._attach_event_statistics(result, es)
         return result
 
     def _attach_pmt_hits(self, result, pmt_hits):
@@ -1150,7 +1230,7 @@ def initializeHIP(device, geometry, medium, wavelengthGenerationBias, wavelength
                   saveAllPhotonsPrescale=0.01, fixedNumberOfAbsorptionLengths=float("nan"), pancakeFactor=1.0,
                   photonHistoryEntries=0, limitWorkgroupSize=0, approximateNumberOfWorkItems=262144,
                   seed=12345, streams=None, tuning=None, mcpeGenerator=None, keepPhotons=True, mcpeSeries=False, pmtHitGenerator=None, mcpeMergeWindow=None, pmtSeries=False,
-                  framePhotons=False, cableShadow=None):
+                  framePhotons=False, cableShadow=None, eventStatistics=False):
     """Canonical configuration sequence, I3CLSimModuleHelper::initializeOpenCL
     (ModuleHelper.cxx:303-372).  tuning: {key: value} for clsimhip_set_tuning, applied before Compile().
     mcpeGenerator: an MCPEGenerator that turns every bunch's photons into MCPEs on the GPU (result attribute `mcpes`);
@@ -1159,7 +1239,8 @@ def initializeHIP(device, geometry, medium, wavelengthGenerationBias, wavelength
     pmtHitGenerator: a PMTHitGenerator instead, for modules with several PMTs (result attribute `pmt_hits`; keepPhotons as above);
     pmtSeries=True sorts its hits into per-frame, per-module, per-PMT series (SetPMTSeries).
     framePhotons=True files the detected photons themselves into per-frame, per-module sorted series (SetFramePhotons; keepPhotons as
-    above).  cableShadow: a CableShadow whose cylinders shadow detected photons before any of those stages (SetCableShadow)."""
+    above).  cableShadow: a CableShadow whose cylinders shadow detected photons before any of those stages (SetCableShadow).
+    eventStatistics=True counts photons generated and at DOMs per particle, with exact weight sums (SetEventStatistics)."""
     conv = I3CLSimStepToPhotonConverterHIP(device)
     for key, value in (tuning or {}).items():
         conv.SetTuning(key, value)
@@ -1189,6 +1270,8 @@ def initializeHIP(device, geometry, medium, wavelengthGenerationBias, wavelength
         conv.SetFramePhotons(True, keepPhotons)
     if cableShadow is not None:
         conv.SetCableShadow(cableShadow)
+    if eventStatistics:
+        conv.SetEventStatistics(True)
     conv.Compile()
     max_wg = conv.GetMaxWorkgroupSize()
     if limitWorkgroupSize:

@@ -16,6 +16,7 @@
 #include "mcpe_merge.h"
 #include "pmt_hits.h"
 #include "cable_shadow.h"
+#include "event_stats.h"
 #include "frame_photons.h"
 #include "pmt_series.h"
 
@@ -1245,6 +1246,42 @@ int clsimhip_set_cable_shadow(clsimhip_converter *c, clsimhip_cable_shadow *s)
 int clsimhip_get_result_cable_shadow(clsimhip_converter *c, const clsimhip_photon *photons, const uint8_t **flags, size_t *n, uint64_t counts[2])
 {
     return guarded(c, [&] { need(c, "converter"); c->impl.result_cable_shadow(photons, flags, n, counts); });
+}
+
+// ---- Event statistics (event_stats.h) ----
+int clsimhip_event_statistics_add(clsimhip_event_statistics *acc, const clsimhip_event_statistics *rec)
+{
+    return guarded(nullptr, [&] {
+        need(acc, "acc");
+        need(rec, "rec");
+        event_stats_add(*acc, *rec);
+    });
+}
+double clsimhip_event_statistics_weight(const uint64_t words[6], const uint32_t special[3]) { return event_stats_weight(words, special); }
+int clsimhip_event_statistics_host(const clsimhip_step *steps, size_t n_steps, const clsimhip_photon *photons, size_t n_photons,
+                                   const clsimhip_mcpe_particle *particles, size_t n_particles, const clsimhip_mcpe_mask *masked, size_t n_masked,
+                                   clsimhip_event_statistics *out, uint64_t counters[3])
+{
+    return guarded(nullptr, [&] { event_stats_host(steps, n_steps, photons, n_photons, particles, n_particles, masked, n_masked, out, counters); });
+}
+size_t clsimhip_event_statistics_workspace_bytes(size_t n_particles, size_t n_masked) { return event_stats_workspace_bytes(n_particles, n_masked); }
+int clsimhip_event_statistics_device(int device, const void *d_steps, size_t n_steps, const void *d_photons, const void *d_count, size_t capacity,
+                                     const clsimhip_mcpe_particle *particles, size_t n_particles, const clsimhip_mcpe_mask *masked, size_t n_masked,
+                                     void *d_out, void *d_counters, void *d_workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return guarded(nullptr, [&] {
+        event_stats_device(device, d_steps, n_steps, d_photons, d_count, capacity, particles, n_particles, masked, n_masked, d_out, d_counters, d_workspace,
+                           workspace_bytes, static_cast<hipStream_t>(hip_stream));
+    });
+}
+int clsimhip_set_event_statistics(clsimhip_converter *c, int on)
+{
+    return guarded(c, [&] { need(c, "converter"); c->impl.set_event_statistics(on != 0); });
+}
+int clsimhip_get_result_event_statistics(clsimhip_converter *c, const clsimhip_photon *photons, const clsimhip_event_statistics **records, size_t *n,
+                                         uint64_t counters[3])
+{
+    return guarded(c, [&] { need(c, "converter"); c->impl.result_event_statistics(photons, records, n, counters); });
 }
 
 } // extern "C"

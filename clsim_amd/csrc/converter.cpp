@@ -8,6 +8,7 @@
 #include "mcpe_merge.h"
 #include "pmt_hits.h"
 #include "cable_shadow.h"
+#include "event_stats.h"
 #include "frame_photons.h"
 #include "pmt_series.h"
 
@@ -553,6 +554,11 @@ void Converter::setup_device_buffers(DeviceState &D)
             sl.d_shadow_counts.alloc(4, "cable shadow counts");
             sl.h_shadow_counts.alloc(4, "pinned cable shadow counts");
         }
+        if (event_stats_) {
+            if (!D.id_strings) throw Error(CLSIMHIP_ERR_CONFIG, "event statistics: the geometry has no DOM");
+            sl.d_es_counters.alloc(4, "event statistics counts");
+            sl.h_es_counters.alloc(4, "pinned event statistics counts");
+        }
         if (series_)
             sl.series.alloc(max_output_photons_, mcpe_series_workspace_bytes(max_output_photons_, 0, 0),
                             {"MCPE series workspace", "sorted MCPEs", "MCPE series table", "MCPE series counts", "pinned MCPE series counts"});
@@ -653,9 +659,9 @@ void Converter::enqueue_steps(const clsimhip_step *steps, size_t n, uint32_t ide
                               const clsimhip_mcpe_mask *masked, size_t n_masked)
 {
     need_init();
-    if ((particles || n_particles || masked || n_masked) && !series_ && !pmt_series_ && !frame_photons_)
-        throw Error(CLSIMHIP_ERR_STATE, "a particle table or mask needs the MCPE series stage (clsimhip_set_mcpe_series), the PMT series stage (clsimhip_set_pmt_series) "
-                                        "or the frame photons stage (clsimhip_set_frame_photons)");
+    if ((particles || n_particles || masked || n_masked) && !series_ && !pmt_series_ && !frame_photons_ && !event_stats_)
+        throw Error(CLSIMHIP_ERR_STATE, "a particle table or mask needs the MCPE series stage (clsimhip_set_mcpe_series), the PMT series stage (clsimhip_set_pmt_series), "
+                                        "the frame photons stage (clsimhip_set_frame_photons) or the event statistics stage (clsimhip_set_event_statistics)");
     check_worker();
     if (!steps) throw Error(CLSIMHIP_ERR_ARGUMENT, "Steps pointer is (null)!");
     if (n == 0) throw Error(CLSIMHIP_ERR_ARGUMENT, "Steps are empty!");
@@ -685,6 +691,8 @@ void Converter::enqueue_steps(const clsimhip_step *steps, size_t n, uint32_t ide
         });
     if (frame_photons_)
         fill(job.fp_bunch, frame_photons_blob_bytes(n_particles, n_masked), [&](uint8_t *blob) { return fp_doms_->prepare(particles, n_particles, masked, n_masked, blob); });
+    if (event_stats_)
+        fill(job.es_bunch, event_stats_blob_bytes(n_particles, n_masked), [&](uint8_t *blob) { return event_stats_prepare(particles, n_particles, masked, n_masked, blob); });
     in_queue_->put(std::move(job));
 }
 
@@ -769,6 +777,28 @@ void Converter::submit(Slot &s, Job &job)
             fp_doms_->device_prepared(device_, records, record_count, max_output_photons_, job.fp_bunch.bunch, blob, s.fp.out.get(), s.fp.series.get(),
                                       s.fp.d_counts.get(), s.fp.workspace.get(), s.fp.workspace_bytes, stream);
         });
+    if (event_stats_) {
+        // behind the upload and behind assemble_hits_kernel: the steps as they were uploaded, and ALL detected photons -- not the lit
+        // ones: the reference takes its statistics before the shadow module runs.  (The slot is free: nothing on the device uses its
+        // workspace or its records.)
+        const SeriesBunch &B = job.es_bunch.bunch;
+        const uint8_t *blob = s.es_bunch.source(job.es_bunch, "pinned event statistics bunch");
+        const size_t need = event_stats_workspace_bytes(B.n_particles, B.n_masked) + 64;
+        if (s.es_workspace_bytes < need) {
+            s.d_es_workspace.reset();
+            s.d_es_workspace.alloc(need + need / 4, "event statistics workspace");
+            s.es_workspace_bytes = need + need / 4;
+        }
+        s.es_records = B.have_table ? B.n_particles : 1u;
+        if (s.es_capacity < s.es_records) {
+            s.d_es_out.reset();
+            s.es_capacity = s.es_records + s.es_records / 4 + 16;
+            s.d_es_out.alloc(s.es_capacity, "event statistics");
+        }
+        event_stats_device_prepared(device_, s.d_steps.get(), n, s.d_photons.get(), s.d_hit_count.get(), max_output_photons_, B, blob, s.d_es_out.get(),
+                                    s.d_es_counters.get(), s.d_es_workspace.get(), s.es_workspace_bytes, stream);
+        hip_check(hipMemcpyAsync(s.h_es_counters.get(), s.d_es_counters.get(), 16, hipMemcpyDeviceToHost, stream), "download event statistics counts");
+    }
     hip_check(hipEventRecord(s.counted.get(), stream), "event");
 }
 
@@ -847,6 +877,10 @@ void Converter::finish(Slot &s, std::chrono::steady_clock::time_point &last_done
     }
     const Kept fp = frame_photons_ ? series_counts(s.fp.h_counts.get(), {"frame photons", "photons", "DOMs the geometry", true}) : Kept{0u, 0u};
     const uint32_t n_fp = fp.records, n_fp_series = fp.series;
+    if (event_stats_ && s.h_es_counters.get()[CLSIMHIP_EVENT_STATISTICS_UNKNOWN_PARTICLE] != 0u)
+        throw Error(CLSIMHIP_ERR_DEVICE, "event statistics, bunch " + std::to_string(s.id) + ": " +
+                                             std::to_string(s.h_es_counters.get()[CLSIMHIP_EVENT_STATISTICS_UNKNOWN_PARTICLE]) +
+                                             " photons of particles the bunch's particle table does not have");
     const uint32_t detected = hits;
     if (!carries_photons()) hits = 0;                   // the records stay on the device
     // (a failure from here on drops r, whose pool buffers go back to their pools)
@@ -906,8 +940,16 @@ void Converter::finish(Slot &s, std::chrono::steady_clock::time_point &last_done
         if (n_fp) hip_check(hipStreamSynchronize(copy_stream), "download frame photons");
         r.fp_masked = s.fp.h_counts.get()[3];
     }
+    if (event_stats_) {
+        for (int k = 0; k < 3; ++k) r.es_counters[k] = s.h_es_counters.get()[k];
+        if (const size_t n = s.es_records) {
+            clsimhip_event_statistics *to = r.es_records.take(es_pool_, n, n + n / 4 + 16, device_);
+            hip_check(hipMemcpyAsync(to, s.d_es_out.get(), n * sizeof(clsimhip_event_statistics), hipMemcpyDeviceToHost, copy_stream), "download event statistics");
+            hip_check(hipStreamSynchronize(copy_stream), "download event statistics");
+        }
+    }
     // a result with no photon records but a stage attached is known by a record of its own
-    if (!hits && (mcpe_ || pmt_ || frame_photons_ || shadow_)) r.handle.reset(new clsimhip_photon());
+    if (!hits && (mcpe_ || pmt_ || frame_photons_ || shadow_ || event_stats_)) r.handle.reset(new clsimhip_photon());
     std::unique_ptr<std::vector<float>> histories;
     if (hits && history_entries_) {
         // ConvertPhotonHistories (OpenCL.cxx:940-989): unroll each ring into forward order
@@ -1118,6 +1160,20 @@ void Converter::result_cable_shadow(const clsimhip_photon *photons, const uint8_
     it->second.shadow_flags.get(flags, n);
     counts[0] = it->second.shadow_counts[0];
     counts[1] = it->second.shadow_counts[1];
+}
+
+void Converter::result_event_statistics(const clsimhip_photon *photons, const clsimhip_event_statistics **records, size_t *n, uint64_t counters[3])
+{
+    need_init();
+    if (!records || !n) throw Error(CLSIMHIP_ERR_ARGUMENT, "output pointers are (null)");
+    if (!event_stats_) throw Error(CLSIMHIP_ERR_STATE, "the event statistics stage is off (clsimhip_set_event_statistics)");
+    *records = nullptr;
+    *n = 0;
+    std::lock_guard<std::mutex> lk(results_mutex_);
+    auto it = handed_out_.find(photons);
+    if (it == handed_out_.end()) throw Error(CLSIMHIP_ERR_ARGUMENT, "not a result handed out by GetConversionResult (or already released)");
+    it->second.es_records.get(records, n);
+    if (counters) std::memcpy(counters, it->second.es_counters, sizeof it->second.es_counters);
 }
 
 void Converter::set_mcpe_merging(bool on, double window)

@@ -321,6 +321,9 @@ public:
     // clsimhip_set_cable_shadow: the filtering stage right behind assemble_hits_kernel (cable_shadow.h; null: off); every stage above
     // then reads the lit records where it reads the detected ones
     void set_cable_shadow(std::shared_ptr<CableShadow> s);
+    // clsimhip_set_event_statistics: the counting stage over the bunch's steps and ALL its detected photons (event_stats.h); beside
+    // every other stage or none
+    void set_event_statistics(bool on) { guard(); compiled_ = false; event_stats_ = on; }
 
     void compile();
     void initialize(uint64_t seed);
@@ -347,6 +350,7 @@ public:
     void result_frame_photons(const clsimhip_photon *photons, const clsimhip_frame_photon **records, size_t *n, const clsimhip_mcpe_series **series,
                               size_t *n_series, uint64_t *n_masked);
     void result_cable_shadow(const clsimhip_photon *photons, const uint8_t **flags, size_t *n, uint64_t counts[2]);
+    void result_event_statistics(const clsimhip_photon *photons, const clsimhip_event_statistics **records, size_t *n, uint64_t counters[3]);
     void release_result(const clsimhip_photon *photons);
     size_t queue_size() const;
     bool more_photons_available() const;
@@ -389,6 +393,7 @@ private:
     using PmtHitPool = PinnedPool<clsimhip_pmt_hit>;
     using PmtSeriesPool = PinnedPool<clsimhip_pmt_series>;
     using FramePhotonPool = PinnedPool<clsimhip_frame_photon>;
+    using EventStatsPool = PinnedPool<clsimhip_event_statistics>;
     using BlobPool = PinnedPool<uint8_t>;
     // A bunch on its way to the worker: the caller's steps are copied ONCE, in the caller's thread, into a page-locked buffer of the
     // step pool, which the worker uploads from (round 5; before, a vector here and a second copy into the slot's staging buffer on
@@ -396,11 +401,12 @@ private:
     // steps travel in a vector as before.
     // With the MCPE series stage the bunch's particle table and mask travel the same way, in the form the stage reads (mcpe_series.h);
     // with the PMT series stage likewise (pmt_series.h: the two stages never run in one converter).  The frame photons stage ranks the
-    // geometry's DOMs, not a generator's, so its table and mask travel in a blob of their own.
+    // geometry's DOMs, not a generator's, so its table and mask travel in a blob of their own; the event statistics stage keys its mask
+    // by module, not by rank, and has its own too.
     struct BunchTable { SeriesBunch bunch; BlobPool::Lease pinned; std::vector<SeriesParticle16> pageable; };
     struct Job {
         uint32_t id = 0; size_t n = 0; uint64_t generated = 0; StepPool::Lease pinned; std::vector<clsimhip_step> steps;
-        BunchTable bunch, fp_bunch;
+        BunchTable bunch, fp_bunch, es_bunch;
     };
     // The records of a result live in page-locked buffers of the converter's pools (back to their pool with release_result, or with
     // a result nobody fetched), or -- when a pool is exhausted because the caller holds more results than it has buffers -- in
@@ -432,6 +438,9 @@ private:
         // with the cable shadow stage: one flag per photon record the result carries (1 = shadowed), records tested and shadowed
         HostRecords<uint8_t> shadow_flags;
         uint64_t shadow_counts[2] = {0, 0};
+        // with the event statistics stage: one record per entry of the bunch's particle table (one without a table), the three counters
+        HostRecords<clsimhip_event_statistics> es_records;
+        uint64_t es_counters[3] = {0, 0, 0};
     };
 
     void guard() const { if (initialized_) throw Error(CLSIMHIP_ERR_STATE, "I3CLSimStepToPhotonConverterHIP already initialized!"); }
@@ -469,6 +478,7 @@ private:
     bool fp_keep_photons_ = true;
     std::shared_ptr<FramePhotonDoms> fp_doms_;  // the geometry's DOMs (Compile())
     std::shared_ptr<CableShadow> shadow_;       // null: every detected photon goes on (the default)
+    bool event_stats_ = false;                  // the event statistics stage runs over every bunch's steps and detected photons
     bool carries_photons() const { return !(mcpe_ && !keep_photons_) && !(pmt_ && !pmt_keep_photons_) && !(frame_photons_ && !fp_keep_photons_); }
 
     std::atomic<bool> compiled_{false}, initialized_{false};    // (atomic: set_tuning() reads them from any thread)
@@ -489,6 +499,7 @@ private:
     FramePhotonPool fp_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
     SeriesPool fp_series_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
     BlobPool shadow_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
+    EventStatsPool es_pool_{PinnedPoolPolicy{6, SIZE_MAX, nullptr}};
     // particle tables and masks of the bunches on their way (input queue depth + one per slot + the one being filled)
     BlobPool bunch_pool_{PinnedPoolPolicy{8, size_t{1} << 28, nullptr}};
     size_t result_capacity(size_t records, size_t min_records) const;
@@ -581,7 +592,7 @@ private:
         SeriesStageBuffers<clsimhip_mcpe, clsimhip_mcpe_series> series;
         SeriesStageBuffers<clsimhip_pmt_hit, clsimhip_pmt_series> pmt_series;
         SeriesStageBuffers<clsimhip_frame_photon, clsimhip_mcpe_series> fp;
-        BunchUpload bunch, fp_bunch;
+        BunchUpload bunch, fp_bunch, es_bunch;
         // with the MCPE merging stage: its workspace, merged records, merged series table, parents, ranges, two counts
         DeviceBuffer<uint8_t> d_merge_workspace;
         size_t merge_workspace_bytes = 0;
@@ -598,6 +609,14 @@ private:
         size_t shadow_workspace_bytes = 0;
         DeviceBuffer<uint32_t> d_shadow_counts;
         PinnedBuffer<uint32_t> h_shadow_counts;
+        // with the event statistics stage: its workspace and records (both grown when a bunch's table needs it), four counts (the
+        // three counters, the records written)
+        DeviceBuffer<uint8_t> d_es_workspace;
+        size_t es_workspace_bytes = 0;
+        DeviceBuffer<clsimhip_event_statistics> d_es_out;
+        size_t es_capacity = 0, es_records = 0;
+        DeviceBuffer<uint32_t> d_es_counters;
+        PinnedBuffer<uint32_t> h_es_counters;
         uint32_t id = 0;
         uint64_t generated = 0;
         size_t result_min_records = 0;          // of the tuning the bunch was launched with

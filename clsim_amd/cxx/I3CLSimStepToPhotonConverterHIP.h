@@ -220,7 +220,16 @@ public:
         lastMaskedFramePhotons_ = 0;
         lastShadowFlags_.clear();
         lastShadowCounts_[0] = 0; lastShadowCounts_[1] = 0;
-        if (cableShadow_) {         // (before every other getter: whichever comes last releases a result without photon records)
+        lastEventStatistics_.clear();
+        lastEventStatisticsCounters_[0] = 0; lastEventStatisticsCounters_[1] = 0; lastEventStatisticsCounters_[2] = 0;
+        if (eventStatistics_) {     // (before every other getter: whichever comes last releases a result without photon records)
+            const clsimhip_event_statistics *e = nullptr;
+            size_t ne = 0;
+            check(clsimhip_get_result_event_statistics(handle_, p, &e, &ne, lastEventStatisticsCounters_));
+            lastEventStatistics_.assign(e, e + ne);
+            if (!n && !cableShadow_ && !framePhotons_ && !mcpeGenerator_ && !pmtHitGenerator_) check(clsimhip_release_result(handle_, p));
+        }
+        if (cableShadow_) {         // (before every other getter but that one: whichever comes last releases a result without photon records)
             const uint8_t *flags = nullptr;
             size_t nf = 0;
             check(clsimhip_get_result_cable_shadow(handle_, p, &flags, &nf, lastShadowCounts_));
@@ -314,6 +323,9 @@ public:
         const uint8_t *shadowFlags = nullptr;       // with the cable shadow stage: one flag per photon record (1 = shadowed), valid as long as `photons`
         std::size_t numShadowFlags = 0;
         uint64_t shadowCounts[2] = {0, 0};          // records tested, records shadowed
+        const clsimhip_event_statistics *eventStatistics = nullptr;     // with the event statistics stage: its records, valid as long as `photons`
+        std::size_t numEventStatistics = 0;
+        uint64_t eventStatisticsCounters[3] = {0, 0, 0};
         const I3CLSimPhoton *begin() const { return photons; }
         const I3CLSimPhoton *end() const { return photons + size; }
     };
@@ -326,6 +338,7 @@ public:
         if (mcpeGenerator_) check(clsimhip_get_result_mcpes(handle_, p, &v.mcpes, &v.numMCPEs));
         if (pmtHitGenerator_) check(clsimhip_get_result_pmt_hits(handle_, p, &v.pmtHits, &v.numPMTHits));
         if (cableShadow_) check(clsimhip_get_result_cable_shadow(handle_, p, &v.shadowFlags, &v.numShadowFlags, v.shadowCounts));
+        if (eventStatistics_) check(clsimhip_get_result_event_statistics(handle_, p, &v.eventStatistics, &v.numEventStatistics, v.eventStatisticsCounters));
         if (p) {
             std::shared_ptr<clsimhip_converter> keep = owner_;
             v.hold = std::shared_ptr<const void>(static_cast<const void *>(p), [keep](const void *q) { (void)clsimhip_release_result(keep.get(), static_cast<const clsimhip_photon *>(q)); });
@@ -431,6 +444,20 @@ public:
                 .assign(lastPMTHits_.begin() + s.first, lastPMTHits_.begin() + s.first + s.count);
         return frames;
     }
+
+    // ---- Event statistics (include/clsimhip.h, "Event statistics"): the client module's I3CLSimEventStatistics -- per particle of the
+    // bunch's table (EnqueueSteps with particles below; without one: one record) the photons generated and the photons at DOMs, as
+    // counts and as exact integer weight sums (clsimhip_event_statistics_weight turns one into a double, rounded once;
+    // clsimhip_event_statistics_add adds two bunches' records exactly).  Before Initialize().  It sees ALL detected photons, also with a
+    // cable shadow bound, and works with keepPhotons = false. ----
+    void SetEventStatistics(bool on = true)
+    {
+        check(clsimhip_set_event_statistics(handle_, on ? 1 : 0));
+        eventStatistics_ = on;
+    }
+    // of the last result: one record per table entry in table order, and the counters (CLSIMHIP_EVENT_STATISTICS_*)
+    const std::vector<clsimhip_event_statistics> &GetLastEventStatistics() const { return lastEventStatistics_; }
+    uint64_t GetLastEventStatisticsCounter(int which) const { return which >= 0 && which < 3 ? lastEventStatisticsCounters_[which] : 0; }
 
     // ---- Cable shadow (include/clsimhip.h, "Cable shadow"): the reference's I3ShadowedPhotonRemoverModule as a stage right behind the
     // propagation kernel.  Before Initialize(); shadow = nullptr switches it off.  The photons of a result stay ALL detected photons
@@ -571,6 +598,9 @@ private:
     bool pmtSeries_ = false;
     bool framePhotons_ = false;
     bool cableShadow_ = false;
+    bool eventStatistics_ = false;
+    std::vector<clsimhip_event_statistics> lastEventStatistics_;
+    uint64_t lastEventStatisticsCounters_[3] = {0, 0, 0};
     std::vector<uint8_t> lastShadowFlags_;
     uint64_t lastShadowCounts_[2] = {0, 0};
     std::vector<clsimhip_frame_photon> lastFramePhotons_;

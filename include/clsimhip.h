@@ -885,7 +885,7 @@ int clsimhip_mcpe_series_device(clsimhip_mcpe_generator *g, int device, const vo
 int clsimhip_set_mcpe_series(clsimhip_converter *c, int on);
 /* clsimhip_enqueue_steps with the bunch's particle table and mask, which are checked and copied in the caller's thread
  * (CLSIMHIP_ERR_ARGUMENT / CLSIMHIP_ERR_CONFIG as above; CLSIMHIP_ERR_STATE with none of clsimhip_set_mcpe_series,
- * clsimhip_set_pmt_series and clsimhip_set_frame_photons).  A bunch enqueued with clsimhip_enqueue_steps has no table: one frame, 0. */
+ * clsimhip_set_pmt_series, clsimhip_set_frame_photons and clsimhip_set_event_statistics).  A bunch enqueued with clsimhip_enqueue_steps has no table: one frame, 0. */
 int clsimhip_enqueue_steps_with_particles(clsimhip_converter *c, const clsimhip_step *steps, size_t n, uint32_t identifier,
                                           const clsimhip_mcpe_particle *particles, size_t n_particles, const clsimhip_mcpe_mask *masked,
                                           size_t n_masked);
@@ -1285,6 +1285,85 @@ int clsimhip_set_cable_shadow(clsimhip_converter *c, clsimhip_cable_shadow *s);
  * with them NULL when the records did not cross to the host), and counts: records tested and shadowed, always delivered.  Valid
  * until clsimhip_release_result(c, photons).  CLSIMHIP_ERR_STATE without clsimhip_set_cable_shadow. */
 int clsimhip_get_result_cable_shadow(clsimhip_converter *c, const clsimhip_photon *photons, const uint8_t **flags, size_t *n, uint64_t counts[2]);
+
+/* ---- Event statistics: per particle, photons generated and photons at DOMs as counts and exact weight sums ------------------
+ * The reference's I3CLSimEventStatistics (the client module's StatisticsName): per particle a count and a weight sum of the photons
+ * generated, accumulated over the steps as they are enqueued (private/clsim/I3CLSimClientModule.cxx:513-520), and a count and a
+ * weight sum of the photons at DOMs, accumulated over the returned photons behind the particle lookup and the ignoreModules mask
+ * (:386-405); the module puts them into the frame at :728-740.  Its weight sums are binary64 running sums -- the generated one of
+ * (double)numPhotons * weight, rounded per step -- in arrival order, which no two runs repeat.  THE SUMS BELOW ARE THIS PROJECT'S OWN
+ * DEFINITION: exact integers, so that a result is a function of the input as a multiset -- the same bytes whatever the schedule,
+ * the wave shape or the bunch partition, from the kernels and from the host twin -- and bunches add exactly.
+ * A float weight is w = +-m * 2^(s-149): with e its biased exponent and f its 23 fraction bits, m = f for e = 0 and f | 2^23
+ * otherwise (m < 2^24), s = max(e, 1) - 1 (0 ... 253).
+ *     at-DOM term      w itself:                    +-m * 2^s                    units of 2^-149
+ *     generated term   the EXACT num_photons * w:   +-(num_photons * m) * 2^s    units of 2^-149 (a 56-bit integer, shifted; nothing
+ *                      is rounded, where the reference rounds the product to 53 bits)
+ * A sum is the integer sum of its terms in units of 2^-149, delivered as six little-endian uint64 words in two's complement.  A
+ * bunch holds at most 2^32 - 1 records, so its sum stays below 2^341: 384 bits hold the sum of 2^42 bunches.
+ * Terms that are not finite are counted, not summed, in three counters per side: +inf, -inf and NaN terms.  A weight with e = 255
+ * is +-inf for f = 0 and NaN otherwise; a generated term with a non-finite weight and num_photons = 0 is a NaN term (0 x inf),
+ * one with an infinite weight and num_photons > 0 an inf term of the weight's sign.  The counts (generated_count, at_doms_count)
+ * include the records whose terms are not finite, as the reference's do.
+ * Per step, all n enqueued steps -- dummy steps and steps the propagator's guards skip included; the reference counts before anything
+ * is sent:
+ *     its identifier is not in the particle table -> UNKNOWN_STEP_PARTICLE, ignored (the reference skips it silently, :514);
+ *     else generated_count += num_photons and the generated term is added.
+ * Per photon, in this order:
+ *     its identifier is not in the particle table -> UNKNOWN_PARTICLE, not counted (log_fatal in the reference, :388-390);
+ *     (frame, string_id, om_id) is in the mask -> MASKED, not counted (:399; not an error);
+ *     else at_doms_count += 1 and the at-DOM term is added.
+ * No DOM list is needed: a mask entry whose frame no table entry names is ignored, every other one holds for whatever module it names.
+ * With a particle table there is one record per table entry, in table order, zeros included (an empty table: no record); without
+ * one (particles = NULL) the bunch yields ONE record, identifier 0 and frame 0, every identifier belongs to it, and the mask's frame
+ * is 0. */
+typedef struct {
+    uint32_t identifier, frame;         /* the table entry's */
+    uint64_t generated_count;           /* the sum of num_photons */
+    uint64_t at_doms_count;
+    uint64_t generated_sum[6], at_doms_sum[6];              /* units of 2^-149, least significant word first, two's complement */
+    uint32_t generated_special[3], at_doms_special[3];      /* +inf, -inf, NaN terms */
+} clsimhip_event_statistics;            /* 144 bytes */
+typedef char clsimhip_event_statistics_is_144_bytes[sizeof(clsimhip_event_statistics) == 144 ? 1 : -1];
+#define CLSIMHIP_EVENT_STATISTICS_UNKNOWN_PARTICLE 0        /* index into the counters */
+#define CLSIMHIP_EVENT_STATISTICS_MASKED 1
+#define CLSIMHIP_EVENT_STATISTICS_UNKNOWN_STEP_PARTICLE 2
+/* acc += rec: the words of both sums with carry (modulo 2^384), both counts, the six special counters.  acc's identifier and frame
+ * stay.  CLSIMHIP_ERR_ARGUMENT for a null pointer. */
+int clsimhip_event_statistics_add(clsimhip_event_statistics *acc, const clsimhip_event_statistics *rec);
+/* A sum as a binary64: the canonical NaN 0x7ff8000000000000 with NaN terms or inf terms of both signs (or a null pointer), +-inf
+ * with inf terms of one sign only, else the integer rounded ONCE to nearest, ties to even, and scaled by 2^-149; zero is +0.0. */
+double clsimhip_event_statistics_weight(const uint64_t words[6], const uint32_t special[3]);
+/* The host twin.  steps / photons may be NULL with a count of 0; particles = NULL, n_particles = 0: no table; `out` holds
+ * n_particles records (one without a table); counters[3] (may be NULL) receives the three counts.  CLSIMHIP_ERR_ARGUMENT for a table
+ * that is not strictly increasing in identifier and for more than 2^32 - 1 steps, photons, particles or masked modules. */
+int clsimhip_event_statistics_host(const clsimhip_step *steps, size_t n_steps, const clsimhip_photon *photons, size_t n_photons,
+                                   const clsimhip_mcpe_particle *particles, size_t n_particles, const clsimhip_mcpe_mask *masked, size_t n_masked,
+                                   clsimhip_event_statistics *out, uint64_t counters[3]);
+/* bytes of device memory the kernels need beside their input and output, for a bunch with this table and mask */
+size_t clsimhip_event_statistics_workspace_bytes(size_t n_particles, size_t n_masked);
+/* The kernels, on steps and photon records that live in HBM: n_steps records of d_steps and min(*d_count, capacity) records of
+ * d_photons (d_steps may be NULL with n_steps = 0, d_photons with capacity = 0).  d_steps and d_photons 4-byte aligned, d_out
+ * (n_particles records, one without a table) 8-byte, d_workspace (clsimhip_event_statistics_workspace_bytes(n_particles, n_masked)
+ * bytes) 16-byte, d_count and d_counters 4-byte; d_counters: four uint32 -- the three counters, then the records written
+ * (CLSIMHIP_ERR_ARGUMENT for a null or misaligned pointer or a workspace that is too small; nothing is launched then).  The
+ * particle table and the mask are host memory: they are checked and copied before the call returns (which may wait for the previous
+ * call's copy, nothing else); the kernels are asynchronous on hip_stream (NULL = default stream) and nothing else waits for the
+ * device.  One call at a time per process prepares its bunch. */
+int clsimhip_event_statistics_device(int device, const void *d_steps, size_t n_steps, const void *d_photons, const void *d_count, size_t capacity,
+                                     const clsimhip_mcpe_particle *particles, size_t n_particles, const clsimhip_mcpe_mask *masked, size_t n_masked,
+                                     void *d_out, void *d_counters, void *d_workspace, size_t workspace_bytes, void *hip_stream);
+/* The stage behind every bunch's propagation kernel, on the bunch's stream: over the bunch's steps as they were uploaded and over
+ * ALL detected photons -- with the cable shadow stage bound too: the reference takes its statistics before the shadow module runs.
+ * Before Initialize() only (CLSIMHIP_ERR_STATE after).  on = 0 (the default): no launch, no allocation, no byte changes anywhere.
+ * With it on, clsimhip_enqueue_steps_with_particles is accepted, it works with keep_photons = 0 under any hit maker, and a bunch
+ * with UNKNOWN_PARTICLE > 0 fails as the series stages' do, with the count in the text. */
+int clsimhip_set_event_statistics(clsimhip_converter *c, int on);
+/* Records of the result `photons` belongs to (one per table entry in table order; one without a table), valid until
+ * clsimhip_release_result(c, photons); counters[3] (may be NULL) receives the three counts.  CLSIMHIP_ERR_STATE without
+ * clsimhip_set_event_statistics. */
+int clsimhip_get_result_event_statistics(clsimhip_converter *c, const clsimhip_photon *photons, const clsimhip_event_statistics **records, size_t *n,
+                                         uint64_t counters[3]);
 
 #ifdef __cplusplus
 }

@@ -27,6 +27,11 @@ per second, on N records against --cylinders cylinders (default 5160: one cable 
 coordinates like the reference's I3CylinderMap, so that a record can only meet the cable of its own DOM and walks the whole set
 otherwise); --device adds the device stage's time for the same input (HIP events around clsimhip_cable_shadow_device, best of
 --repeats; needs a GPU) -- the host twin then runs once, for the comparison.
+
+--event-statistics N: the event statistics' host twin instead (clsimhip_event_statistics_host), in records per second, on N steps and
+N photon records dealt to 1000 particles in 10 frames in runs of 4096 (a particle's steps and photons come in long runs), weights
+over twelve binades; --device adds the device stage's time for the same input (HIP events around clsimhip_event_statistics_device,
+best of --repeats; needs a GPU).
 """
 import argparse
 import ctypes as C
@@ -227,6 +232,51 @@ def cable_shadow_rate(args):
     print(json.dumps(line))
 
 
+def event_statistics_rate(args):
+    n = args.event_statistics
+    rng = np.random.default_rng(1)
+    ident = (np.arange(n) // 4096) % 1000
+    steps = np.zeros(n, dtype=CV.STEP_DTYPE)
+    steps["num"], steps["weight"], steps["id"] = rng.integers(0, 400, n), np.exp(rng.uniform(-4.0, 4.0, n)), ident
+    photons = np.zeros(n, dtype=CV.PHOTON_DTYPE)
+    photons["weight"], photons["id"] = np.exp(rng.uniform(-4.0, 4.0, n)), ident
+    photons["stringID"], photons["omID"] = rng.integers(1, 87, n), rng.integers(1, 61, n)
+    p = np.zeros(1000, dtype=CV.MCPE_PARTICLE_DTYPE)
+    p["id"], p["frame"] = np.arange(1000), np.arange(1000) % 10
+    masked = np.zeros(20, dtype=CV.MCPE_MASK_DTYPE)
+    masked["frame"], masked["stringID"], masked["omID"] = np.arange(20) % 10, 40, 30
+    best = float("inf")
+    for _ in range(args.repeats):
+        t0 = time.perf_counter()
+        want, counters = CV.EventStatistics.MakeHost(steps, photons, p, masked)
+        best = min(best, time.perf_counter() - t0)
+    line = {"steps": n, "photon_records": n, "particles": len(p), "masked": counters["masked"], "host_seconds": best, "host_records_per_s": 2 * n / best,
+            "threads": 1}
+    if args.device:
+        import torch
+        dev = torch.device("cuda", 0)
+        d_steps = torch.from_numpy(steps.view(np.uint8).reshape(-1, 48).copy()).to(dev)
+        d_photons = torch.from_numpy(photons.view(np.uint8).reshape(-1, 80).copy()).to(dev)
+        d_cnt = torch.tensor([n], dtype=torch.int32, device=dev)
+        d_out = torch.zeros((len(p), 144), dtype=torch.uint8, device=dev)
+        d_counters = torch.zeros(4, dtype=torch.int32, device=dev)
+        ws = CV.EventStatistics.WorkspaceBytes(len(p), len(masked))
+        d_ws = torch.zeros(ws, dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream().cuda_stream
+        times = []
+        for _ in range(args.repeats + 1):
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            CV.EventStatistics.MakeDevice(d_steps.data_ptr(), n, d_photons.data_ptr(), d_cnt.data_ptr(), n, d_out.data_ptr(), d_counters.data_ptr(), d_ws.data_ptr(), ws,
+                                          particles=p, masked=masked, stream=stream)
+            stop.record()
+            torch.cuda.synchronize()
+            times.append(start.elapsed_time(stop) * 1e-3)
+        assert d_out.cpu().numpy().tobytes() == want.tobytes() and [int(v) for v in d_counters.cpu()[:3]] == [counters[k] for k in CV.EVENT_STATISTICS_COUNTERS]
+        line.update(device_seconds=min(times[1:]), device_records_per_s=2 * n / min(times[1:]))
+    print(json.dumps(line))
+
+
 def merge_rate(args):
     from tests import mcpe_merge_common as MM
     from tests import mcpe_series_common as S
@@ -282,7 +332,10 @@ def main():
     ap.add_argument("--frame-photons", type=int, default=0, metavar="N")
     ap.add_argument("--cable-shadow", type=int, default=0, metavar="N")
     ap.add_argument("--cylinders", type=int, default=5160)
+    ap.add_argument("--event-statistics", type=int, default=0, metavar="N")
     args = ap.parse_args()
+    if args.event_statistics:
+        return event_statistics_rate(args)
     if args.cable_shadow:
         return cable_shadow_rate(args)
     if args.frame_photons:

@@ -5,6 +5,7 @@ the stage's kernels beside the propagation kernel.  Prints the counts and the ho
 
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/mcpe_series_profile.py [--steps 1048576] [--no-series] [--merge-window NS]
                                                                                    [--pmt] [--frame-photons] [--cable-shadow]
+                                                                                   [--event-statistics]
 
 --merge-window NS: the MCPE merging stage behind the series stage, with that window.
 --pmt: a 31-PMT module (tests/pmt_common.py) at every DOM instead: the multi-PMT hit maker and the PMT series stage (--no-series:
@@ -13,6 +14,8 @@ the hit maker alone).
 propagation alone, records downloaded).
 --cable-shadow: the cable shadow stage in front of whichever stages the other options choose, with one cable beside every DOM of
 the geometry (5 160 cylinders, in the DOM's own frame: tests/cable_shadow_common.py); the line then carries its two counts.
+--event-statistics: the event statistics stage beside whichever stages the other options choose (with --no-series the bunch has no
+particle table and yields one record); the line then carries the records, the photons at DOMs and the stage's counters.
 """
 import argparse
 import json
@@ -35,11 +38,18 @@ def cable_shadow_of(args, cfg):
     return S.make_shadow(S.cylinder_set(len(cfg["geom"]["string_ids"])))
 
 
+def event_statistics_of(r):
+    if not hasattr(r, "event_statistics"):
+        return None
+    return {"records": len(r.event_statistics), "at_doms": int(r.event_statistics["atDOMsCount"].sum()),
+            "generated": int(r.event_statistics["generatedCount"].sum()), "counters": r.event_statistics_counters}
+
+
 def pmt_bunch(args, cfg, bias):
     from tests import pmt_common as PC
     conv = CV.initializeHIP(0, CV.I3CLSimSimpleGeometry.from_dict(cfg["geom"]), cfg["med_p"], bias, common.product_generators(cfg, bias), pancakeFactor=5.0,
                             stopDetectedPhotons=True, approximateNumberOfWorkItems=args.steps, pmtHitGenerator=PC.geometry_generator(cfg),
-                            keepPhotons=False, pmtSeries=not args.no_series, cableShadow=cable_shadow_of(args, cfg))
+                            keepPhotons=False, pmtSeries=not args.no_series, cableShadow=cable_shadow_of(args, cfg), eventStatistics=args.event_statistics)
     steps = common.steps_for(cfg, args.steps, seed=3).copy()
     steps["id"] = np.arange(len(steps)) % 1000
     p = np.zeros(1000, dtype=CV.MCPE_PARTICLE_DTYPE)
@@ -53,13 +63,13 @@ def pmt_bunch(args, cfg, bias):
         r = conv.GetConversionResult()
         wall = time.perf_counter() - t0
     print(json.dumps({"steps": len(steps), "photons": int(steps["num"].sum()), "pmt_hits": len(r.pmt_hits),
-                      "pmt_series": None if r.pmt_series is None else len(r.pmt_series), "cable_shadow": r.shadow_counts, "wall_seconds_second_bunch": wall}))
+                      "pmt_series": None if r.pmt_series is None else len(r.pmt_series), "cable_shadow": r.shadow_counts, "event_statistics": event_statistics_of(r), "wall_seconds_second_bunch": wall}))
 
 
 def frame_photons_bunch(args, cfg, bias):
     conv = CV.initializeHIP(0, CV.I3CLSimSimpleGeometry.from_dict(cfg["geom"]), cfg["med_p"], bias, common.product_generators(cfg, bias), pancakeFactor=5.0,
                             stopDetectedPhotons=True, approximateNumberOfWorkItems=args.steps, keepPhotons=False, framePhotons=not args.no_series,
-                            cableShadow=cable_shadow_of(args, cfg))
+                            cableShadow=cable_shadow_of(args, cfg), eventStatistics=args.event_statistics)
     steps = common.steps_for(cfg, args.steps, seed=3).copy()
     steps["id"] = np.arange(len(steps)) % 1000
     p = np.zeros(1000, dtype=CV.MCPE_PARTICLE_DTYPE)
@@ -75,7 +85,7 @@ def frame_photons_bunch(args, cfg, bias):
     print(json.dumps({"steps": len(steps), "photons": int(steps["num"].sum()), "photon_records": len(r[1]),
                       "frame_photons": None if r.frame_photons is None else len(r.frame_photons),
                       "frame_photon_series": None if r.frame_photon_series is None else len(r.frame_photon_series), "cable_shadow": r.shadow_counts,
-                      "wall_seconds_second_bunch": wall}))
+                      "event_statistics": event_statistics_of(r), "wall_seconds_second_bunch": wall}))
 
 
 def main():
@@ -86,6 +96,7 @@ def main():
     ap.add_argument("--pmt", action="store_true")
     ap.add_argument("--frame-photons", action="store_true")
     ap.add_argument("--cable-shadow", action="store_true")
+    ap.add_argument("--event-statistics", action="store_true")
     args = ap.parse_args()
     cfg = common.config("mie")
     g = cfg["geom"]
@@ -98,7 +109,7 @@ def main():
         return frame_photons_bunch(args, cfg, bias)
     conv = CV.initializeHIP(0, CV.I3CLSimSimpleGeometry.from_dict(g), cfg["med_p"], bias, common.product_generators(cfg, bias), pancakeFactor=5.0,
                             stopDetectedPhotons=True, approximateNumberOfWorkItems=args.steps, mcpeGenerator=gen, keepPhotons=False,
-                            mcpeSeries=not args.no_series, mcpeMergeWindow=args.merge_window, cableShadow=cable_shadow_of(args, cfg))
+                            mcpeSeries=not args.no_series, mcpeMergeWindow=args.merge_window, cableShadow=cable_shadow_of(args, cfg), eventStatistics=args.event_statistics)
     steps = common.steps_for(cfg, args.steps, seed=3).copy()
     steps["id"] = np.arange(len(steps)) % 1000
     p = np.zeros(1000, dtype=CV.MCPE_PARTICLE_DTYPE)
@@ -114,7 +125,7 @@ def main():
     print(json.dumps({"steps": len(steps), "photons": int(steps["num"].sum()), "mcpes": len(r.mcpes),
                       "series": None if r.series is None else len(r.series),
                       "merged": None if r.merged is None else len(r.merged), "parents": None if r.parents is None else len(r.parents),
-                      "cable_shadow": r.shadow_counts, "wall_seconds_second_bunch": wall}))
+                      "cable_shadow": r.shadow_counts, "event_statistics": event_statistics_of(r), "wall_seconds_second_bunch": wall}))
 
 
 if __name__ == "__main__":
