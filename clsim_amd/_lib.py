@@ -58,6 +58,12 @@ class Polynomial(C.Structure):      # clsimhip_polynomial
                 ("underflow", C.c_double), ("overflow", C.c_double)]
 
 
+class PhotonHitConfig(C.Structure):     # clsimhip_photon_hit_config
+    _fields_ = [("dom_radius", C.c_double), ("oversize", C.c_double), ("pancake", C.c_double), ("default_relative_efficiency", C.c_double),
+                ("replace_efficiency_with_default", C.c_int32), ("ignore_inactive", C.c_int32), ("only_warn_off_surface", C.c_int32),
+                ("reserved", C.c_int32), ("seed", C.c_uint64)]
+
+
 class MediumDesc(C.Structure):      # clsimhip_medium_desc
     _fields_ = [("num_layers", C.c_int32), ("layers_z_start", C.c_double), ("layers_height", C.c_double),
                 ("min_wavelength", C.c_double), ("max_wavelength", C.c_double),
@@ -143,6 +149,8 @@ SYMBOLS = [
     "clsimhip_event_statistics_add", "clsimhip_event_statistics_weight", "clsimhip_event_statistics_host",
     "clsimhip_event_statistics_workspace_bytes", "clsimhip_event_statistics_device", "clsimhip_set_event_statistics",
     "clsimhip_get_result_event_statistics",
+    "clsimhip_photon_hit_maker_create", "clsimhip_photon_hit_maker_destroy", "clsimhip_photon_hit_maker_last_error",
+    "clsimhip_photon_hit_maker_efficiency", "clsimhip_photon_hits_host", "clsimhip_photon_hits_workspace_bytes", "clsimhip_photon_hits_device",
 ]
 
 # clsimhip_get_last_launch: CLSIMHIP_FAMILY_* and CLSIMHIP_LENGTHS_* by name
@@ -356,12 +364,20 @@ def load():
         "clsimhip_event_statistics_device": (i32, [i32, vp, sz, vp, vp, sz, vp, sz, vp, sz, vp, vp, vp, sz, vp]),
         "clsimhip_set_event_statistics": (i32, [vp, i32]),
         "clsimhip_get_result_event_statistics": (i32, [vp, vp, C.POINTER(vp), C.POINTER(sz), vp]),
+        "clsimhip_photon_hit_maker_create": (i32, [C.POINTER(Function), sz, C.POINTER(Polynomial), vp, sz, C.POINTER(PhotonHitConfig), C.POINTER(vp)]),
+        "clsimhip_photon_hit_maker_destroy": (None, [vp]),
+        "clsimhip_photon_hit_maker_last_error": (C.c_char_p, [vp]),
+        "clsimhip_photon_hit_maker_efficiency": (i32, [vp, C.c_int32, u32, DP]),
+        "clsimhip_photon_hits_host": (i32, [vp, vp, sz, vp, sz, vp, vp, C.POINTER(sz), C.POINTER(sz), vp]),
+        "clsimhip_photon_hits_workspace_bytes": (sz, [sz]),
+        "clsimhip_photon_hits_device": (i32, [vp, i32, vp, vp, vp, sz, vp, vp, vp, vp, sz, vp]),
         "clsimhip_tabulator_write_fits_file": (i32, [vp, C.c_char_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double), sz]),
     }
     for name in SYMBOLS:
-        # (A/B measurements load an older build through CLSIMHIP_LIB: it may lack the entries of the run-time compiled kernel and of the event
-        # statistics stage, which bench.py does not call)
-        newer = name in ("clsimhip_baked_info", "clsimhip_baked_compile", "clsimhip_baked_set_compiler_library") or "event_statistics" in name
+        # (A/B measurements load an older build through CLSIMHIP_LIB: it may lack the entries of the run-time compiled kernel, of the event
+        # statistics stage and of the photon hits stage, which bench.py does not call)
+        newer = (name in ("clsimhip_baked_info", "clsimhip_baked_compile", "clsimhip_baked_set_compiler_library") or "event_statistics" in name
+                 or "photon_hit" in name)
         if newer and LIB_PATH != DEFAULT_LIB_PATH and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol

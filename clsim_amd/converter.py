@@ -613,6 +613,84 @@ class FramePhotonDoms:
                                                        int(workspace_bytes), C.c_void_p(stream)))
 
 
+# Photon hits (include/clsimhip.h): one DOM of the maker's table; the records are FRAME_PHOTON_DTYPE in and MCPE_DTYPE out, the
+# series tables MCPE_SERIES_DTYPE
+PHOTON_HIT_DOM_DTYPE = np.dtype([("stringID", "<i4"), ("omID", "<u4"), ("classIndex", "<i4"), ("flags", "<u4"), ("relativeDOMEff", "<f8"),
+                                 ("speCompensationFactor", "<f8"), ("dir", "<f8", (3,))])
+PHOTON_HIT_HAS_STATUS, PHOTON_HIT_IN_CALIBRATION = 1, 2
+PHOTON_HIT_COUNTERS = ("uncovered", "series_mismatch", "unknown_dom", "inactive", "negative_weight", "off_surface", "probability_above_one")
+
+
+class PhotonHitMaker:
+    """Stored frame photons -> per-frame, per-DOM time-sorted MCPEs (clsimhip_photon_hit_maker): the older I3PhotonToMCPEConverter
+    (private/clsim/dom/I3PhotonToMCPEConverter.cxx:257-539) with its calibration look-ups, as a function of the records, their series
+    table and a seed -- the second step of I3CLSimMakeHitsFromPhotons.
+
+    wavelengthAcceptances, angularAcceptance: as for MCPEGenerator; doms: PHOTON_HIT_DOM_DTYPE (flags: PHOTON_HIT_HAS_STATUS,
+    PHOTON_HIT_IN_CALIBRATION); the other parameters carry the module's names."""
+
+    def __init__(self, wavelengthAcceptances, angularAcceptance, doms, DOMRadiusWithoutOversize=0.16510, DOMOversizeFactor=1.0,
+                 DOMPancakeFactor=1.0, DefaultRelativeDOMEfficiency=1.0, ReplaceRelativeDOMEfficiencyWithDefault=False,
+                 IgnoreDOMsWithoutDetectorStatusEntry=False, OnlyWarnAboutInvalidPhotonPositions=False, seed=0):
+        self._lib = _lib.load()
+        self._h = C.c_void_p()
+        self._keep = list(wavelengthAcceptances)
+        descs = (_lib.Function * max(len(self._keep), 1))(*[f._desc() for f in self._keep])
+        doms = np.ascontiguousarray(doms, dtype=PHOTON_HIT_DOM_DTYPE)
+        poly = _lib.Polynomial()
+        coeff = np.ascontiguousarray(angularAcceptance.coefficients, dtype=np.float64)
+        poly.n = len(coeff)
+        poly.coefficients = _dp(coeff)
+        poly.range_min, poly.range_max = angularAcceptance.rangemin, angularAcceptance.rangemax
+        poly.underflow, poly.overflow = angularAcceptance.underflow, angularAcceptance.overflow
+        cfg = _lib.PhotonHitConfig(float(DOMRadiusWithoutOversize), float(DOMOversizeFactor), float(DOMPancakeFactor),
+                                   float(DefaultRelativeDOMEfficiency), int(bool(ReplaceRelativeDOMEfficiencyWithDefault)),
+                                   int(bool(IgnoreDOMsWithoutDetectorStatusEntry)), int(bool(OnlyWarnAboutInvalidPhotonPositions)), 0, int(seed))
+        _check(self._lib.clsimhip_photon_hit_maker_create(descs, len(self._keep), C.byref(poly), C.c_void_p(doms.ctypes.data if len(doms) else None),
+                                                          len(doms), C.byref(cfg), C.byref(self._h)))
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                self._lib.clsimhip_photon_hit_maker_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def Efficiency(self, stringID, omID):
+        """the efficiency the maker resolved for a DOM of its table"""
+        out = C.c_double()
+        _check(self._lib.clsimhip_photon_hit_maker_efficiency(self._h, int(stringID), int(omID), C.byref(out)))
+        return out.value
+
+    def MakeHitsHost(self, records, series):
+        """(mcpes, series, counters): the host twin.  records: FRAME_PHOTON_DTYPE with their series table (MCPE_SERIES_DTYPE), as the
+        frame photons stage delivers them.  mcpes: MCPE_DTYPE ascending in (input series, time key, id); series: MCPE_SERIES_DTYPE, one
+        entry per input entry that kept a record; counters = {name: count} (PHOTON_HIT_COUNTERS)"""
+        records = np.ascontiguousarray(records, dtype=FRAME_PHOTON_DTYPE)
+        series = np.ascontiguousarray(series, dtype=MCPE_SERIES_DTYPE)
+        out = np.zeros(len(records), dtype=MCPE_DTYPE)
+        out_series = np.zeros(len(series), dtype=MCPE_SERIES_DTYPE)
+        n_kept, n_series, counters = C.c_size_t(), C.c_size_t(), np.zeros(7, dtype=np.uint64)
+        _check(self._lib.clsimhip_photon_hits_host(self._h, records.ctypes.data_as(C.c_void_p), len(records), series.ctypes.data_as(C.c_void_p),
+                                                   len(series), out.ctypes.data_as(C.c_void_p), out_series.ctypes.data_as(C.c_void_p),
+                                                   C.byref(n_kept), C.byref(n_series), counters.ctypes.data_as(C.c_void_p)))
+        return out[:n_kept.value], out_series[:n_series.value], dict(zip(PHOTON_HIT_COUNTERS, (int(c) for c in counters)))
+
+    @staticmethod
+    def WorkspaceBytes(capacity):
+        return int(_lib.load().clsimhip_photon_hits_workspace_bytes(int(capacity)))
+
+    def MakeHitsDevice(self, d_records, d_series, d_in_counts, capacity, d_out, d_out_series, d_counts, d_workspace, workspace_bytes, device=0, stream=0):
+        """the kernels on device-resident frame photons (addresses, 16-byte aligned; pairs with FramePhotonDoms.MakeFramePhotonsDevice:
+        its d_out, d_series and d_counts): min(d_in_counts[0], capacity) records, min(d_in_counts[1], capacity) series; d_out /
+        d_out_series: `capacity` entries, d_counts: nine uint32 (kept, series, then PHOTON_HIT_COUNTERS), d_workspace:
+        WorkspaceBytes(capacity) bytes"""
+        _check(self._lib.clsimhip_photon_hits_device(self._h, int(device), C.c_void_p(d_records), C.c_void_p(d_series), C.c_void_p(d_in_counts),
+                                                     int(capacity), C.c_void_p(d_out), C.c_void_p(d_out_series), C.c_void_p(d_counts),
+                                                     C.c_void_p(d_workspace), int(workspace_bytes), C.c_void_p(stream)))
+
+
 class CableShadow:
     """The cylinder set of the cable shadow stage (clsimhip_cable_shadow; include/clsimhip.h: "Cable shadow"): a detected photon whose
     last `distance` metres of path meet a solid finite cylinder is shadowed.  top, bottom: [n, 3] end points; radius: [n] or one value

@@ -19,6 +19,7 @@
 #include "event_stats.h"
 #include "frame_photons.h"
 #include "pmt_series.h"
+#include "photon_hits.h"
 
 using namespace clsimhip;
 
@@ -28,6 +29,7 @@ struct clsimhip_mcpe_generator { std::shared_ptr<McpeGenerator> impl; };
 struct clsimhip_pmt_generator { std::shared_ptr<PmtHitGenerator> impl; };
 struct clsimhip_frame_photon_doms { std::shared_ptr<FramePhotonDoms> impl; };
 struct clsimhip_cable_shadow { std::shared_ptr<CableShadow> impl; };
+struct clsimhip_photon_hit_maker { std::shared_ptr<PhotonHitMaker> impl; };
 struct clsimhip_tabulator {
     std::unique_ptr<Tabulator> impl;
 };
@@ -1282,6 +1284,46 @@ int clsimhip_get_result_event_statistics(clsimhip_converter *c, const clsimhip_p
                                          uint64_t counters[3])
 {
     return guarded(c, [&] { need(c, "converter"); c->impl.result_event_statistics(photons, records, n, counters); });
+}
+
+// ---- Photon hits (photon_hits.h) ----
+int clsimhip_photon_hit_maker_create(const clsimhip_function *classes, size_t n_classes, const clsimhip_polynomial *angular_acceptance,
+                                     const clsimhip_photon_hit_dom *doms, size_t n_doms, const clsimhip_photon_hit_config *config,
+                                     clsimhip_photon_hit_maker **out)
+{
+    return guarded(nullptr, [&] {
+        need(classes, "classes"); need(angular_acceptance, "angular_acceptance"); need(config, "config"); need(out, "out");
+        std::vector<FunctionData> fs;
+        for (size_t k = 0; k < n_classes; ++k) fs.push_back(function_from(classes + k));
+        *out = new clsimhip_photon_hit_maker{std::make_shared<PhotonHitMaker>(fs, *angular_acceptance, doms, n_doms, *config)};
+    });
+}
+void clsimhip_photon_hit_maker_destroy(clsimhip_photon_hit_maker *g) { delete g; }
+const char *clsimhip_photon_hit_maker_last_error(const clsimhip_photon_hit_maker *g) { (void)g; return g_last_error.c_str(); }
+int clsimhip_photon_hit_maker_efficiency(const clsimhip_photon_hit_maker *g, int32_t string_id, uint32_t om_id, double *out)
+{
+    return guarded(nullptr, [&] { need(g, "maker"); need(out, "out"); *out = g->impl->efficiency(string_id, om_id); });
+}
+int clsimhip_photon_hits_host(const clsimhip_photon_hit_maker *g, const clsimhip_frame_photon *records, size_t n, const clsimhip_mcpe_series *series,
+                              size_t n_series, clsimhip_mcpe *out, clsimhip_mcpe_series *out_series, size_t *n_kept, size_t *n_series_out,
+                              uint64_t counters[7])
+{
+    return guarded(nullptr, [&] {
+        need(g, "maker");
+        if (counters) std::memset(counters, 0, 7 * sizeof(uint64_t));
+        g->impl->host(records, n, series, n_series, out, out_series, n_kept, n_series_out, counters);
+    });
+}
+size_t clsimhip_photon_hits_workspace_bytes(size_t capacity) { return photon_hits_workspace_bytes(capacity); }
+int clsimhip_photon_hits_device(clsimhip_photon_hit_maker *g, int device, const void *d_records, const void *d_series, const void *d_in_counts,
+                                size_t capacity, void *d_out, void *d_out_series, void *d_counts, void *d_workspace, size_t workspace_bytes,
+                                void *hip_stream)
+{
+    return guarded(nullptr, [&] {
+        need(g, "maker");
+        g->impl->device(device, d_records, d_series, d_in_counts, capacity, d_out, d_out_series, d_counts, d_workspace, workspace_bytes,
+                        static_cast<hipStream_t>(hip_stream));
+    });
 }
 
 } // extern "C"

@@ -1365,6 +1365,103 @@ int clsimhip_set_event_statistics(clsimhip_converter *c, int on);
 int clsimhip_get_result_event_statistics(clsimhip_converter *c, const clsimhip_photon *photons, const clsimhip_event_statistics **records, size_t *n,
                                          uint64_t counters[3]);
 
+/* ---- Photon hits: stored frame photons -> per-frame, per-DOM time-sorted MCPEs, with the calibration look-ups ------------------
+ * The second half of the reference's two-step workflow (python/traysegments/I3CLSimMakeHitsFromPhotons.py): photons are propagated
+ * once and stored as PropagatedPhotons -- here clsimhip_frame_photon records with their series table, what the frame photons stage
+ * delivers, cable shadow applied if bound -- and hits are made from them as often as needed, with another DOM efficiency or angular
+ * acceptance each time.  The module that does it is the older I3PhotonToMCPEConverter (private/clsim/dom/
+ * I3PhotonToMCPEConverter.cxx:257-539); this stage restates its per-DOM and per-photon work as a function of the input arrays, a
+ * fixed configuration and a 64-bit seed.
+ * The efficiency of every DOM is fixed when the maker is made, by the reference's rule (:327-388); its log_fatals there depend on the
+ * configuration alone and are CLSIMHIP_ERR_CONFIG here, naming the DOM:
+ *     default_relative_efficiency < 0 is an error (:172);
+ *     replace_efficiency_with_default: the efficiency is the default; a NaN default is an error;
+ *     a DOM not in the calibration (flag bit 1 clear) takes the default; a NaN default is an error;
+ *     a DOM in the calibration with a NaN relative_dom_eff takes the default, WITHOUT the SPE factor; a NaN default is an error;
+ *     otherwise relative_dom_eff x (isnan(spe_compensation_factor) ? 1 : spe_compensation_factor), one binary64 product.
+ * Record i belongs to series s, the last entry of the series table with first <= i (a binary search; nothing checks that `first`
+ * ascends).  Per record, in this order:
+ *     no such entry, or i >= first + count -> UNCOVERED, no record;
+ *     the record's (string_id, om_id) differ from the entry's -> SERIES_MISMATCH, no record;
+ *     the DOM is not in the table -> UNKNOWN_DOM (log_fatal in the reference, :295-298);
+ *     ignore_inactive and the DOM's flag bit 0 is clear -> INACTIVE, no record (:288-292; not an error);
+ *     W = weight; W < 0 -> NEGATIVE_WEIGHT; W == 0 -> nothing (:397-399);
+ *     dir = (sin theta cos phi, sin theta sin phi, cos theta) from the deterministic single precision pairs of the MCPE generator,
+ *     widened; c = -(dir.x Dx + dir.y Dy + dir.z Dz), then c = c < 1 ? c : 1, c = c > -1 ? c : -1 (:409-412).  D is the DOM's
+ *     direction as given, not normalised;
+ *     only when pancake == 1: r^2 = x x + y y + z z outside [max(oversize R - 0.03, 0)^2, (oversize R + 0.03)^2], R = dom_radius
+ *     -> OFF_SURFACE: counted, and no record unless only_warn_off_surface (:417-453).  Positions are relative to the module, as the
+ *     frame photons stage stores them;
+ *     P = W x wavelength acceptance of the DOM's class, then x angular acceptance(c), then x efficiency (:466-474);
+ *     P > 1 -> PROBABILITY_ABOVE_ONE (:478-504);
+ *     u = (h >> 11) 2^-53, h = seed folded with splitmix64 over the record's six little-endian 64-bit words; P <= u -> nothing;
+ *     time = record time + ((-x) dir.x + (-y) dir.y + (-z) dir.z) x (1 - pancake / oversize) / group_velocity (:512-518); a NaN is
+ *     stored as 0x7ff8000000000000.
+ * All of it is binary64 + - x / in the order written, never contracted, so the kernels and the host twin give the same bits for every
+ * 48-byte pattern.  Comparisons with a NaN are false: a NaN weight goes on, a NaN c becomes 1, a NaN r^2 is OFF_SURFACE, a NaN P
+ * yields a record, a NaN wavelength reads its table's last bin.
+ * The kept records come out ascending in (s, tkey(time), identifier) with the MCPE series' tkey; string_id and om_id are the
+ * entry's.  The output series table has one entry per input entry that kept a record, in input order, with the entry's frame,
+ * string_id and om_id.  Records with equal keys are byte-identical: the output is a function of the input, the same bytes from run
+ * to run and from the kernels and the host twin; it has the form clsimhip_mcpe_merge_host / _device read.
+ * What differs from the reference, on purpose: the draw (no I3RandomService in arrival order; with one seed the hits made at a lower
+ * efficiency are a subset of those made at a higher one); the total order where std::sort(MCPETimeLess) leaves equal times open;
+ * CheckSanity (:455) does not apply to compressed photons; merging is the MCPE merging stage's rule, applied by the caller; the
+ * cross-checks between I3OMGeo and I3ModuleGeo (:301-325) are the caller's configuration. */
+typedef struct {
+    int32_t string_id;                  /* must fit int16 / uint16 (CLSIMHIP_ERR_ARGUMENT otherwise); a pair named twice: */
+    uint32_t om_id;                     /* CLSIMHIP_ERR_ARGUMENT */
+    int32_t class_index;                /* wavelength acceptance class */
+    uint32_t flags;                     /* bit 0: has a detector status entry with pmtHV != 0; bit 1: is in the calibration */
+    double relative_dom_eff, spe_compensation_factor;       /* the calibration's; NaN where it has none */
+    double dir_x, dir_y, dir_z;         /* I3OMGeo::GetDirection() */
+} clsimhip_photon_hit_dom;              /* 56 bytes */
+typedef struct {
+    double dom_radius, oversize, pancake;       /* positive and finite */
+    double default_relative_efficiency;         /* may be NaN: "there is no default" */
+    int32_t replace_efficiency_with_default, ignore_inactive, only_warn_off_surface, reserved;
+    uint64_t seed;
+} clsimhip_photon_hit_config;           /* 56 bytes */
+typedef char clsimhip_photon_hit_dom_is_56_bytes[sizeof(clsimhip_photon_hit_dom) == 56 ? 1 : -1];
+typedef char clsimhip_photon_hit_config_is_56_bytes[sizeof(clsimhip_photon_hit_config) == 56 ? 1 : -1];
+#define CLSIMHIP_PHOTON_HITS_FLAG_HAS_STATUS 1u
+#define CLSIMHIP_PHOTON_HITS_FLAG_IN_CALIBRATION 2u
+#define CLSIMHIP_PHOTON_HITS_UNCOVERED 0            /* index into the seven counters */
+#define CLSIMHIP_PHOTON_HITS_SERIES_MISMATCH 1
+#define CLSIMHIP_PHOTON_HITS_UNKNOWN_DOM 2
+#define CLSIMHIP_PHOTON_HITS_INACTIVE 3
+#define CLSIMHIP_PHOTON_HITS_NEGATIVE_WEIGHT 4
+#define CLSIMHIP_PHOTON_HITS_OFF_SURFACE 5
+#define CLSIMHIP_PHOTON_HITS_PROBABILITY_ABOVE_ONE 6
+typedef struct clsimhip_photon_hit_maker clsimhip_photon_hit_maker;
+/* n_classes (1 ... 8) wavelength acceptances and the angular acceptance as for clsimhip_mcpe_generator_create, with the same limits;
+ * a DOM table of up to 2^24 entries; the configuration.  Host only: no GPU is touched. */
+int clsimhip_photon_hit_maker_create(const clsimhip_function *classes, size_t n_classes, const clsimhip_polynomial *angular_acceptance,
+                                     const clsimhip_photon_hit_dom *doms, size_t n_doms, const clsimhip_photon_hit_config *config,
+                                     clsimhip_photon_hit_maker **out);
+void clsimhip_photon_hit_maker_destroy(clsimhip_photon_hit_maker *g);
+const char *clsimhip_photon_hit_maker_last_error(const clsimhip_photon_hit_maker *g);
+/* the resolved efficiency of a DOM of the table (CLSIMHIP_ERR_ARGUMENT for any other DOM) */
+int clsimhip_photon_hit_maker_efficiency(const clsimhip_photon_hit_maker *g, int32_t string_id, uint32_t om_id, double *out);
+/* The host twin: the definition with std::sort on the key, for callers without a GPU and for the tests.  out holds n entries,
+ * out_series n_series; counters[7] (may be NULL) receives the seven counts. */
+int clsimhip_photon_hits_host(const clsimhip_photon_hit_maker *g, const clsimhip_frame_photon *records, size_t n, const clsimhip_mcpe_series *series,
+                              size_t n_series, clsimhip_mcpe *out, clsimhip_mcpe_series *out_series, size_t *n_kept, size_t *n_series_out,
+                              uint64_t counters[7]);
+/* bytes of device memory the kernels need beside their input and output, for up to `capacity` records */
+size_t clsimhip_photon_hits_workspace_bytes(size_t capacity);
+/* The kernels, on frame photons that live in HBM (pairs with clsimhip_frame_photons_device: d_records = its d_out, d_series = its
+ * d_series, d_in_counts = its d_counts, whose first two words are records kept and series): min(d_in_counts[0], capacity) records,
+ * min(d_in_counts[1], capacity) series entries.  d_out and d_out_series: `capacity` entries each; d_records, d_series, d_out,
+ * d_out_series and d_workspace (clsimhip_photon_hits_workspace_bytes(capacity) bytes) 16-byte aligned, d_in_counts and d_counts
+ * 4-byte; d_counts: nine uint32 -- records kept, series, then the seven counters (CLSIMHIP_ERR_ARGUMENT for a null or misaligned
+ * pointer or a workspace that is too small; nothing is launched then).  The kernels are asynchronous on hip_stream (NULL = default
+ * stream) and read all sizes from device memory; the first call on a device copies the maker's tables there, nothing else waits for
+ * the device. */
+int clsimhip_photon_hits_device(clsimhip_photon_hit_maker *g, int device, const void *d_records, const void *d_series, const void *d_in_counts,
+                                size_t capacity, void *d_out, void *d_out_series, void *d_counts, void *d_workspace, size_t workspace_bytes,
+                                void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

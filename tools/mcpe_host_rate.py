@@ -32,6 +32,12 @@ otherwise); --device adds the device stage's time for the same input (HIP events
 N photon records dealt to 1000 particles in 10 frames in runs of 4096 (a particle's steps and photons come in long runs), weights
 over twelve binades; --device adds the device stage's time for the same input (HIP events around clsimhip_event_statistics_device,
 best of --repeats; needs a GPU).
+
+--photon-hits N: the photon hits' host twin instead (clsimhip_photon_hits_host), in frame photon records per second, on the committed
+photon records repeated to N records, dealt to 5160 DOMs and 1000 particles in 10 frames and brought into form by the frame photons'
+host twin; IceCube acceptance, efficiencies from {0.5, 1, 1.35}, pancake 2 of oversize 5 (the time correction is live); --device adds
+the device stage's time for the same input (HIP events around clsimhip_photon_hits_device, best of --repeats; needs a GPU).  The line
+names the core the host twin ran on.
 """
 import argparse
 import ctypes as C
@@ -277,6 +283,57 @@ def event_statistics_rate(args):
     print(json.dumps(line))
 
 
+def photon_hits_rate(args):
+    from tests import photon_hits_common as P
+    n = args.photon_hits
+    rng = np.random.default_rng(1)
+    s, d = np.meshgrid(np.arange(1, 87), np.arange(1, 61), indexing="ij")
+    s, d = s.reshape(-1).astype(np.int32), d.reshape(-1).astype(np.uint32)
+    base = np.concatenate([M.fixture_photons(name) for name in M.FIXTURES if name != "lea_no_pancake"])
+    m = np.ascontiguousarray(np.tile(base, -(-n // len(base)))[:n])
+    at = rng.integers(0, len(s), n)
+    m["stringID"], m["omID"], m["id"] = s[at], d[at], rng.integers(0, 1000, n)
+    m["t"] = (m["t"] + rng.uniform(0.0, 1.0e4, n)).astype(np.float32)
+    p = np.zeros(1000, dtype=CV.MCPE_PARTICLE_DTYPE)
+    p["id"], p["frame"], p["timeShift"] = np.arange(1000), np.arange(1000) % 10, rng.uniform(0.0, 1.0e6, 1000)
+    records, series, _ = CV.FramePhotonDoms(s, d).MakeFramePhotonsHost(m, p)
+    maker = P.maker_of(P.spec(P.dom_table(s, d, efficiencies=(0.5, 1.0, 1.35), spe=1.0), pancake=2.0))
+    best = float("inf")
+    for _ in range(args.repeats):
+        t0 = time.perf_counter()
+        mcpes, table, counters = maker.MakeHitsHost(records, series)
+        best = min(best, time.perf_counter() - t0)
+    assert not any(counters.values())
+    model = [line.split(":", 1)[1].strip() for line in open("/proc/cpuinfo") if line.startswith("model name")][:1]
+    line = {"frame_photons": n, "input_series": len(series), "mcpes": len(mcpes), "series": len(table), "host_seconds": best, "host_records_per_s": n / best,
+            "threads": 1, "host_core": model[0] if model else None}
+    if args.device:
+        import torch
+        dev = torch.device("cuda", 0)
+        d_records = torch.from_numpy(records.view(np.uint8).copy()).to(dev)
+        d_series = torch.zeros(n * 16, dtype=torch.uint8, device=dev)
+        d_series[:len(series) * 16] = torch.from_numpy(series.view(np.uint8).copy()).to(dev)
+        d_in = torch.tensor([n, len(series)], dtype=torch.int32, device=dev)
+        d_out, d_out_series = torch.zeros(n * 16, dtype=torch.uint8, device=dev), torch.zeros(n * 16, dtype=torch.uint8, device=dev)
+        d_counts = torch.zeros(9, dtype=torch.int32, device=dev)
+        ws = CV.PhotonHitMaker.WorkspaceBytes(n)
+        d_ws = torch.zeros(ws, dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream().cuda_stream
+        times = []
+        for _ in range(args.repeats + 1):
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            maker.MakeHitsDevice(d_records.data_ptr(), d_series.data_ptr(), d_in.data_ptr(), n, d_out.data_ptr(), d_out_series.data_ptr(), d_counts.data_ptr(),
+                                 d_ws.data_ptr(), ws, stream=stream)
+            stop.record()
+            torch.cuda.synchronize()
+            times.append(start.elapsed_time(stop) * 1e-3)
+        assert [int(c) for c in d_counts.cpu()[:2]] == [len(mcpes), len(table)]
+        assert d_out.cpu().numpy()[:len(mcpes) * 16].tobytes() == mcpes.tobytes() and d_out_series.cpu().numpy()[:len(table) * 16].tobytes() == table.tobytes()
+        line.update(device_seconds=min(times[1:]), device_records_per_s=n / min(times[1:]))
+    print(json.dumps(line))
+
+
 def merge_rate(args):
     from tests import mcpe_merge_common as MM
     from tests import mcpe_series_common as S
@@ -333,7 +390,10 @@ def main():
     ap.add_argument("--cable-shadow", type=int, default=0, metavar="N")
     ap.add_argument("--cylinders", type=int, default=5160)
     ap.add_argument("--event-statistics", type=int, default=0, metavar="N")
+    ap.add_argument("--photon-hits", type=int, default=0, metavar="N")
     args = ap.parse_args()
+    if args.photon_hits:
+        return photon_hits_rate(args)
     if args.event_statistics:
         return event_statistics_rate(args)
     if args.cable_shadow:

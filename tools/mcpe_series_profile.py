@@ -5,13 +5,16 @@ the stage's kernels beside the propagation kernel.  Prints the counts and the ho
 
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/mcpe_series_profile.py [--steps 1048576] [--no-series] [--merge-window NS]
                                                                                    [--pmt] [--frame-photons] [--cable-shadow]
-                                                                                   [--event-statistics]
+                                                                                   [--event-statistics] [--photon-hits]
 
 --merge-window NS: the MCPE merging stage behind the series stage, with that window.
 --pmt: a 31-PMT module (tests/pmt_common.py) at every DOM instead: the multi-PMT hit maker and the PMT series stage (--no-series:
 the hit maker alone).
 --frame-photons: no hit maker; the frame photons stage on the bunch's photon records, which stay on the device (--no-series: the
 propagation alone, records downloaded).
+--photon-hits: with --frame-photons: the photon hits stage (IceCube acceptance, hole-ice angular acceptance, efficiencies from {0.5, 1,
+1.35}, pancake 2 of oversize 5 so that the time correction is live) on the second bunch's frame photons, uploaded again and run
+twice on the device (the first call copies the maker's tables); the line then carries the stage's counts.
 --cable-shadow: the cable shadow stage in front of whichever stages the other options choose, with one cable beside every DOM of
 the geometry (5 160 cylinders, in the DOM's own frame: tests/cable_shadow_common.py); the line then carries its two counts.
 --event-statistics: the event statistics stage beside whichever stages the other options choose (with --no-series the bunch has no
@@ -66,6 +69,29 @@ def pmt_bunch(args, cfg, bias):
                       "pmt_series": None if r.pmt_series is None else len(r.pmt_series), "cable_shadow": r.shadow_counts, "event_statistics": event_statistics_of(r), "wall_seconds_second_bunch": wall}))
 
 
+def photon_hits_of(cfg, r):
+    """the photon hits stage on the result's frame photons, on the device; {kept, series, counters}"""
+    import torch
+    from tests import photon_hits_common as P
+    g = cfg["geom"]
+    maker = P.maker_of(P.spec(P.dom_table(np.asarray(g["string_ids"]), np.asarray(g["dom_ids"]), efficiencies=(0.5, 1.0, 1.35), spe=1.0), pancake=2.0))
+    dev = torch.device("cuda", 0)
+    n = len(r.frame_photons)
+    d_records = torch.from_numpy(r.frame_photons.view(np.uint8).copy()).to(dev)
+    d_series = torch.from_numpy(r.frame_photon_series.view(np.uint8).copy()).to(dev)
+    d_in = torch.tensor([n, len(r.frame_photon_series)], dtype=torch.int32, device=dev)
+    d_out, d_out_series = torch.empty(max(n, 1) * 16, dtype=torch.uint8, device=dev), torch.empty(max(n, 1) * 16, dtype=torch.uint8, device=dev)
+    d_counts = torch.zeros(9, dtype=torch.int32, device=dev)
+    ws_bytes = CV.PhotonHitMaker.WorkspaceBytes(n)
+    d_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    for _ in range(2):
+        maker.MakeHitsDevice(d_records.data_ptr(), d_series.data_ptr(), d_in.data_ptr(), n, d_out.data_ptr(), d_out_series.data_ptr(), d_counts.data_ptr(),
+                             d_ws.data_ptr(), ws_bytes, stream=torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+    counts = [int(c) for c in d_counts.cpu().numpy()]
+    return {"records": n, "kept": counts[0], "series": counts[1], "counters": dict(zip(CV.PHOTON_HIT_COUNTERS, counts[2:]))}
+
+
 def frame_photons_bunch(args, cfg, bias):
     conv = CV.initializeHIP(0, CV.I3CLSimSimpleGeometry.from_dict(cfg["geom"]), cfg["med_p"], bias, common.product_generators(cfg, bias), pancakeFactor=5.0,
                             stopDetectedPhotons=True, approximateNumberOfWorkItems=args.steps, keepPhotons=False, framePhotons=not args.no_series,
@@ -82,7 +108,8 @@ def frame_photons_bunch(args, cfg, bias):
             conv.EnqueueSteps(steps, bunch, particles=p)
         r = conv.GetConversionResult()
         wall = time.perf_counter() - t0
-    print(json.dumps({"steps": len(steps), "photons": int(steps["num"].sum()), "photon_records": len(r[1]),
+    hits = photon_hits_of(cfg, r) if args.photon_hits and r.frame_photons is not None else None
+    print(json.dumps({"steps": len(steps), "photons": int(steps["num"].sum()), "photon_records": len(r[1]), "photon_hits": hits,
                       "frame_photons": None if r.frame_photons is None else len(r.frame_photons),
                       "frame_photon_series": None if r.frame_photon_series is None else len(r.frame_photon_series), "cable_shadow": r.shadow_counts,
                       "event_statistics": event_statistics_of(r), "wall_seconds_second_bunch": wall}))
@@ -97,6 +124,7 @@ def main():
     ap.add_argument("--frame-photons", action="store_true")
     ap.add_argument("--cable-shadow", action="store_true")
     ap.add_argument("--event-statistics", action="store_true")
+    ap.add_argument("--photon-hits", action="store_true")
     args = ap.parse_args()
     cfg = common.config("mie")
     g = cfg["geom"]
