@@ -1375,6 +1375,11 @@ long Converter::get_table(const std::string &name, double *out, size_t cap) cons
         if (out) std::memcpy(out, values, std::min<size_t>(6, cap) * sizeof(double));
         return 6;
     }
+    if (name == "lds_image") {                          // the words every workgroup copies into LDS, as they are uploaded
+        const size_t n = tables_.lds_image.size();
+        if (out) for (size_t i = 0; i < std::min(n, cap); ++i) out[i] = tables_.lds_image[i];
+        return static_cast<long>(n);
+    }
     if (name == "dom_named") {
         const size_t n = tables_.dom_named.size();
         if (out) for (size_t i = 0; i < std::min(n, cap); ++i) out[i] = tables_.dom_named[i];

@@ -140,7 +140,8 @@ struct KParams {
     // ---- medium ----
     int32_t num_layers;
     float layer_bottom, layer_thickness, recip_thickness;
-    // 4-word records per layer.  ICECUBE: {(D*aDust+E), (1+0.01*dTau), b400, 0}; CONSTANT: {abs, 0, sca, 0}
+    // 4-word records per layer.  ICECUBE: {(D*aDust+E), (1+0.01*dTau), b400, lower}; CONSTANT: {abs, 0, sca, lower}
+    // (lower = layer * layer_thickness + layer_bottom in single precision: read by the run-time compiled kernel only)
     uint32_t off_layers;
     float neg_kappa, abs_A, neg_B, neg_alpha, ref_wlen_recip, nanometer;
     float n[5], g[5], micrometer, c_light;
@@ -160,6 +161,7 @@ struct KParams {
     float tilt_first_z, tilt_dz, tilt_lnx, tilt_lny;
     uint32_t off_tilt_dist, off_tilt_zcorr;
     // 4-word records per distance bin j = 1..nd-1 at off_tilt_bins + 4*j: {dist[j], dist[j]-dist[j-1], its reciprocal, ok}
+    // (ok: 0 = the division is not proven; else 1 | byte address of zcorr's row j - 1 in the image << 1)
     uint32_t off_tilt_bins;
     float tilt_inner_dist[6];           // dist[1..nd-2], padded with +inf (used when nd <= 8)
 

@@ -76,6 +76,26 @@ DM void lds_sincos_2pi(float x, float &s, float &c) { dm::sincos_2pi_with_(x, s,
 DM float ldsf(uint32_t i) { return __builtin_bit_cast(float, lds_words[i]); }
 DM uint32_t ldsu(uint32_t i) { return lds_words[i]; }
 DM Rec4 lds_rec4(uint32_t i) { return *reinterpret_cast<const Rec4 *>(&lds_words[i]); }   // i % 4 == 0
+#ifdef KPARAMS_BAKED
+// (run-time compiled kernel, round 9) A record of which all four words are used, as ONE ds_read_b128: the load/store vectoriser is off
+// for the pooled kernel, so the compiler leaves a Rec4 as ds_read2_b32 + ds_read_b32 and only a vector load becomes the wide read.
+// i % 4 == 0 must be visible to the caller (a literal offset): the wide read needs the 16-byte alignment its type promises.
+// Both reads below name the image by its byte address, as the math tables above are (detmath.hip.h: LdsTable): through the symbol
+// lds_words the compiler adds the symbol's address, 0, with an instruction of its own.
+DM Rec4 lds_rec4_wide(uint32_t i)
+{
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    typedef const f32x4 __attribute__((address_space(3))) *lds_vec_ptr;
+    const f32x4 v = *reinterpret_cast<lds_vec_ptr>(static_cast<uintptr_t>(4u * i));
+    return Rec4{v.x, v.y, v.z, v.w};
+}
+// a float at a BYTE address of the image
+DM float ldsf_at_byte(uint32_t byte)
+{
+    typedef const float __attribute__((address_space(3))) *lds_float_ptr;
+    return *reinterpret_cast<lds_float_ptr>(static_cast<uintptr_t>(byte));
+}
+#endif
 DM uint32_t lds_u16(uint32_t off, uint32_t i)
 {
     const uint32_t w = lds_words[off + (i >> 1)];
@@ -260,6 +280,26 @@ DM void layer_lengths(uint32_t off_layers, const float *len_table, const IceFact
         abs_len = r.a;
     }
 }
+#ifdef KPARAMS_BAKED
+// (run-time compiled kernel, round 9) layer_lengths for a record of the LDS image that the caller has read, because it also wants the
+// record's fourth word (propagate_through_layers): the same arithmetic on the same three words.
+template <int MED, bool FAST>
+DM void layer_lengths_of(const Rec4 &r, const IceFactors &f, float &sca_len, float &abs_len, float &rcp_sca, float &rcp_abs, bool fast)
+{
+    if (MED == CLSIMHIP_LENGTHS_ICECUBE) {
+        const float x_sca = r.c * f.sca_pow, x_abs = r.a * f.abs_pow + f.abs_exp * r.b;
+        sca_len = rcp_t<FAST>(x_sca, fast);
+        abs_len = rcp_t<FAST>(x_abs, fast);
+        if (FAST || fast) {
+            rcp_sca = dm::rcp_of_rcp_(sca_len, x_sca);
+            rcp_abs = dm::rcp_of_rcp_(abs_len, x_abs);
+        }
+    } else {
+        sca_len = r.c;
+        abs_len = r.a;
+    }
+}
+#endif
 // The scattering angle's ten wave-uniform constants in ONE load group (round 6): read field by field the compiler sinks each scalar load
 // to its use, and the Liu / Henyey-Greenstein choice became four groups each with its own wait in every loop trip.  The fields sit next to
 // each other in KParams (static_asserts below), so two eight-dword loads cover them.
@@ -377,25 +417,59 @@ DM float tilt_z_shift(KP P, float px, float py, float pz)
     const float z_rescaled = div_by_t<FAST>(pz - P->tilt_first_z, P->tilt_dz, P->rcp_tilt_dz, (P->div_ok & 1u) != 0);
     const int nz = P->tilt_nz, nd = P->tilt_nd;
     const uint32_t off_dist = P->off_tilt_dist;
+#ifdef KPARAMS_BAKED
+    // (run-time compiled kernel, round 9: the same index without v_floor_f32.  For z_rescaled >= 0 the truncating conversion IS the
+    // floor; for z_rescaled < 0 the floor is <= -1 and the truncation <= 0, NaN converts to 0 and values beyond the int range to its
+    // ends either way: the clamp sends both forms to the same end.)
+    const int k = clamp_index((int)z_rescaled, nz - 2);
+#else
     const int k = clamp_index((int)__builtin_floorf(z_rescaled), nz - 2);           // nz >= 2 (tables.cpp)
+#endif
     const float fraction_z_above = z_rescaled - (float)k;
     const float fraction_z_below = 1.0f - fraction_z_above;
     const float nr = P->tilt_lnx * px + P->tilt_lny * py;
     int j = 1;
     if (FAST || nd <= kTiltScalarBins + 2) {
+#ifdef KPARAMS_BAKED
+        // (run-time compiled kernel, round 9: nd is a literal, so only the nd - 2 real inner edges are compared.  The +inf padding cost
+        // a compare with +inf, a select and an add per trip, because nr could be +inf.  The same j for every finite nr and for NaN;
+        // for nr = +inf the padded count runs on to j = 7, beyond the bin records, where this one stops at the last bin, nd - 1,
+        // as the reference does.)
+#pragma unroll
+        for (int t = 0; t < kTiltScalarBins; ++t)
+            if (t < nd - 2) j += (nr >= P->tilt_inner_dist[t]) ? 1 : 0;
+#else
         // inner bin edges live in the parameter block (padded with +inf): compares against SGPRs, no LDS
 #pragma unroll
         for (int t = 0; t < kTiltScalarBins; ++t) j += (nr >= P->tilt_inner_dist[t]) ? 1 : 0;
+#endif
     } else {
         for (int t = 1; t < nd - 1; ++t) j += (nr >= ldsf(off_dist + t)) ? 1 : 0;
     }
+#ifdef KPARAMS_BAKED
+    // (round 9: all four words of the record are used below, and tables.cpp aligns the records to four words)
+    const Rec4 bin = (KParams::off_tilt_bins % 4u == 0u) ? lds_rec4_wide(P->off_tilt_bins + 4u * (uint32_t)j) : lds_rec4(P->off_tilt_bins + 4u * (uint32_t)j);
+#else
     const Rec4 bin = lds_rec4(P->off_tilt_bins + 4u * (uint32_t)j);    // dist[j], dist[j]-dist[j-1], 1/width, proven
+#endif
     const float thisDist = bin.a;
     // the proof bit differs per bin: select, the divide is only executed if some lane's bin lacks the proof
     const float q = (thisDist - nr) * bin.c;
     float frac_at_lower = dm::fma_(dm::fma_(-bin.b, q, thisDist - nr), bin.c, q);
     if (!FAST && __builtin_bit_cast(uint32_t, bin.d) == 0u) frac_at_lower = (thisDist - nr) / bin.b;
     const float frac_at_upper = 1.0f - frac_at_lower;
+#ifdef KPARAMS_BAKED
+    // (run-time compiled kernel, round 9) FAST: every bin is proven (tables.cpp: medium_proofs_complete), so the record's fourth word is
+    // 1 | byte address of the bin's correction row << 1: the address of (j - 1, k) is that row + 4 k, read instead of
+    // off_tilt_zcorr + (j - 1) * nz + k multiplied out per trip.  The same four words are read.
+    if (FAST) {
+        const uint32_t at = (__builtin_bit_cast(uint32_t, bin.d) >> 1) + 4u * (uint32_t)k;
+        const uint32_t up = 4u * (uint32_t)nz;
+        const float val_at_lower = (ldsf_at_byte(at + 4u) * fraction_z_above + ldsf_at_byte(at) * fraction_z_below);
+        const float val_at_upper = (ldsf_at_byte(at + up + 4u) * fraction_z_above + ldsf_at_byte(at + up) * fraction_z_below);
+        return (val_at_upper * frac_at_upper + val_at_lower * frac_at_lower);
+    }
+#endif
     const uint32_t lo = P->off_tilt_zcorr + (uint32_t)((j - 1) * nz + k);
     const uint32_t hi = lo + (uint32_t)nz;
     const float val_at_lower = (ldsf(lo + 1) * fraction_z_above + ldsf(lo) * fraction_z_below);
@@ -645,6 +719,18 @@ DM float propagate_through_layers(KP P, Photon &ph, uint64_t &rx, uint32_t ra)
     const float sca_step_left = -lds_log(rng_oc(rx, ra));
     float sca_len, abs_len, rcp_sca = 0.0f, rcp_abs = 0.0f;     // the current layer's lengths and, when `seeded`, RN(1 / length)
     const bool seeded = (MED == CLSIMHIP_LENGTHS_ICECUBE) && fast;
+#ifdef KPARAMS_BAKED
+    // (run-time compiled kernel, round 9) With the layer records in LDS their fourth word holds the layer's lower boundary, formed by
+    // tables.cpp with the two single precision operations above: it comes with the record that is read here anyway -- one ds_read_b128
+    // where the offset shows its alignment -- and `lower` above is dead code.  Tabulated lengths have their records in global memory:
+    // the arithmetic stays.
+    if (MED != CLSIMHIP_LENGTHS_TABLE) {
+        const uint32_t at = off_layers + 4u * (uint32_t)current_layer;
+        const Rec4 r = (KParams::off_layers % 4u == 0u) ? lds_rec4_wide(at) : lds_rec4(at);
+        layer_lengths_of<MED, FAST>(r, ph.ice, sca_len, abs_len, rcp_sca, rcp_abs, fast);
+        boundary = (dz < 0.0f) ? r.d : (r.d + thickness);
+    } else
+#endif
     layer_lengths<MED, FAST>(off_layers, len_table, ph.ice, current_layer, sca_len, abs_len, rcp_sca, rcp_abs, fast);
     const float recip_thickness = P->recip_thickness;
     // Two divides of one numerator by lengths that Compile() has bounded to (2^-50, 2^50) (`fast`): the 8-instruction exact

@@ -128,6 +128,19 @@ CompiledTables compile_tables(const MediumData &m, const GeometryInput &geometry
     }
     scalar("MEDIUM_MIN_WLEN", to_float_literal(m.min_wlen)); scalar("MEDIUM_MAX_WLEN", to_float_literal(m.max_wlen));
     C.variant.lengths = m.lengths_kind;
+    // Round 9: the fourth word of a layer's record in LDS, unread until then, holds the layer's lower boundary
+    // (mediumLayerBoundary, c.cl:78-81) -- formed with the kernel's two single precision operations, a product and then a sum
+    // (-ffp-contract=off: no fma) -- for the run-time compiled kernel, which reads it with the record instead of forming it in every
+    // loop trip (prop_device.hip.h: propagate_through_layers).  Tabulated lengths keep their records in global memory: nothing is stored.
+    auto store_lower_boundaries = [&](std::vector<float> &rec) {
+        std::vector<double> lower(rec.size() / 4);
+        for (size_t l = 0; l < lower.size(); ++l) {
+            const float rise = static_cast<float>(static_cast<int>(l)) * P.layer_thickness;
+            rec[4 * l + 3] = rise + P.layer_bottom;
+            lower[l] = rec[4 * l + 3];
+        }
+        name("layer_record_lower_boundary", lower);
+    };
     if (m.lengths_kind == CLSIMHIP_LENGTHS_TABLE) {
         // FromTable.cxx:167-300 per layer.  With 16-bit storage the generated function rebuilds
         //   convert_float(data[bin]) * ((LARGEST-SMALLEST)/65535.f) + SMALLEST
@@ -190,6 +203,7 @@ CompiledTables compile_tables(const MediumData &m, const GeometryInput &geometry
         }
         std::vector<float> rec(4 * a_dust.size(), 0.f);
         for (size_t l = 0; l < a_dust.size(); ++l) { rec[4 * l] = abs_a[l]; rec[4 * l + 1] = abs_b[l]; rec[4 * l + 2] = b400[l]; }
+        store_lower_boundaries(rec);
         P.off_layers = img.add_floats(rec);
         P.neg_kappa = -to_float_literal(m.kappa);
         P.abs_A = to_float_literal(m.A);
@@ -203,6 +217,7 @@ CompiledTables compile_tables(const MediumData &m, const GeometryInput &geometry
         const std::vector<float> abs_c = literals(m.abs_length), sca_c = literals(m.sca_length);
         std::vector<float> rec(4 * abs_c.size(), 0.f);
         for (size_t l = 0; l < abs_c.size(); ++l) { rec[4 * l] = abs_c[l]; rec[4 * l + 2] = sca_c[l]; }
+        store_lower_boundaries(rec);
         P.off_layers = img.add_floats(rec);
         name("absorptionLength", as_doubles(abs_c)); name("scatteringLength", as_doubles(sca_c));
     }
@@ -298,7 +313,14 @@ CompiledTables compile_tables(const MediumData &m, const GeometryInput &geometry
         if (division_by_reciprocal_is_exact(P.tilt_dz, P.rcp_tilt_dz)) P.div_ok |= 1u;
         for (size_t t6 = 0; t6 < 6; ++t6) P.tilt_inner_dist[t6] = (t6 + 1 < nd - 1) ? dist[t6 + 1] : INFINITY;
         {
+            // Round 9: a proven bin's fourth word also carries, above the proof bit, the BYTE address in the image of the bin's
+            // row of corrections, (j - 1, 0): 1 | 4 (off_tilt_zcorr + (j - 1) nz) << 1.  The run-time compiled FAST kernel, for which
+            // every bin is proven, forms the address of (j - 1, k) as that row + 4 k (prop_device.hip.h: tilt_z_shift); every other
+            // kernel tests the word against 0 as before.
             std::vector<uint32_t> bins(4 * nd, 0u);
+            std::vector<double> fourth(nd, 0.);
+            if (4. * (static_cast<double>(P.off_tilt_zcorr) + static_cast<double>(nd) * static_cast<double>(nz)) >= 2147483648.)
+                throw Error(CLSIMHIP_ERR_CONFIG, "the ice tilt table does not fit the image");
             for (size_t j = 1; j < nd; ++j) {
                 const float width = dist[j] - dist[j - 1];          // thisDistanceBinWidth
                 float rcp = 0.f;
@@ -306,10 +328,13 @@ CompiledTables compile_tables(const MediumData &m, const GeometryInput &geometry
                 std::memcpy(&bins[4 * j], &dist[j], 4);
                 std::memcpy(&bins[4 * j + 1], &width, 4);
                 std::memcpy(&bins[4 * j + 2], &rcp, 4);
-                bins[4 * j + 3] = ok ? 1u : 0u;
+                const uint32_t row_byte_offset = 4u * (P.off_tilt_zcorr + static_cast<uint32_t>((j - 1) * nz));
+                bins[4 * j + 3] = ok ? (1u | row_byte_offset << 1) : 0u;
+                fourth[j] = bins[4 * j + 3];
             }
             img.align(4);
             P.off_tilt_bins = img.add_words(bins);
+            name("tilt_bin_record_fourth_word", fourth);
         }
         name("getTiltZShift_data_distancesFromOriginAlongTilt", as_doubles(dist));
         name("getTiltZShift_data_zCorrections", as_doubles(corr));
