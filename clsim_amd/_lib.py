@@ -151,6 +151,7 @@ SYMBOLS = [
     "clsimhip_get_result_event_statistics",
     "clsimhip_photon_hit_maker_create", "clsimhip_photon_hit_maker_destroy", "clsimhip_photon_hit_maker_last_error",
     "clsimhip_photon_hit_maker_efficiency", "clsimhip_photon_hits_host", "clsimhip_photon_hits_workspace_bytes", "clsimhip_photon_hits_device",
+    "clsimhip_pmt_photon_hits_host", "clsimhip_pmt_photon_hits_workspace_bytes", "clsimhip_pmt_photon_hits_device",
 ]
 
 # clsimhip_get_last_launch: CLSIMHIP_FAMILY_* and CLSIMHIP_LENGTHS_* by name
@@ -371,6 +372,9 @@ def load():
         "clsimhip_photon_hits_host": (i32, [vp, vp, sz, vp, sz, vp, vp, C.POINTER(sz), C.POINTER(sz), vp]),
         "clsimhip_photon_hits_workspace_bytes": (sz, [sz]),
         "clsimhip_photon_hits_device": (i32, [vp, i32, vp, vp, vp, sz, vp, vp, vp, vp, sz, vp]),
+        "clsimhip_pmt_photon_hits_host": (i32, [vp, vp, sz, vp, sz, vp, vp, C.POINTER(sz), C.POINTER(sz), vp]),
+        "clsimhip_pmt_photon_hits_workspace_bytes": (sz, [sz]),
+        "clsimhip_pmt_photon_hits_device": (i32, [vp, i32, vp, vp, vp, sz, vp, vp, vp, vp, sz, vp]),
         "clsimhip_tabulator_write_fits_file": (i32, [vp, C.c_char_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double), sz]),
     }
     for name in SYMBOLS:

@@ -473,6 +473,9 @@ PMT_CONDITIONS = ("unknown_module", "probability_above_one", "off_surface")
 PMT_SERIES_DTYPE = np.dtype([("frame", "<u4"), ("stringID", "<i2"), ("omID", "<u2"), ("pmt", "<u4"), ("first", "<u4"), ("count", "<u4"),
                              ("reserved", "<u4")])
 PMT_SERIES_COUNTERS = ("unknown_particle", "masked", "unknown_channel")
+# PMT photon hits (include/clsimhip.h): the records are FRAME_PHOTON_DTYPE with an MCPE_SERIES_DTYPE table in, PMT_HIT_DTYPE with a
+# PMT_SERIES_DTYPE table out
+PMT_PHOTON_HIT_COUNTERS = ("uncovered", "series_mismatch", "unknown_module", "probability_above_one", "off_surface")
 
 
 class PMTHitGenerator:
@@ -549,6 +552,35 @@ class PMTHitGenerator:
         _check(self._lib.clsimhip_pmt_series_device(self._h, int(device), C.c_void_p(d_hits), C.c_void_p(d_count), int(capacity), pp, n_p, mp, n_m,
                                                     C.c_void_p(d_out), C.c_void_p(d_series), C.c_void_p(d_counts), C.c_void_p(d_workspace),
                                                     int(workspace_bytes), C.c_void_p(stream)))
+
+    def MakeHitsFromFramePhotonsHost(self, records, series):
+        """(hits, series, counters): the host twin of the PMT photon hits stage, I3PhotonToMCHitConverterForMultiPMT on stored photons.
+        records: FRAME_PHOTON_DTYPE with their series table (MCPE_SERIES_DTYPE), as the frame photons stage delivers them.  hits:
+        PMT_HIT_DTYPE ascending in (input series, pmt, time key, id), the time the record's own; series: PMT_SERIES_DTYPE, one entry per
+        non-empty (input series, PMT); counters = {name: count} (PMT_PHOTON_HIT_COUNTERS)"""
+        records = np.ascontiguousarray(records, dtype=FRAME_PHOTON_DTYPE)
+        series = np.ascontiguousarray(series, dtype=MCPE_SERIES_DTYPE)
+        out = np.zeros(len(records), dtype=PMT_HIT_DTYPE)
+        out_series = np.zeros(len(records), dtype=PMT_SERIES_DTYPE)
+        n_kept, n_series, counters = C.c_size_t(), C.c_size_t(), np.zeros(5, dtype=np.uint64)
+        _check(self._lib.clsimhip_pmt_photon_hits_host(self._h, records.ctypes.data_as(C.c_void_p), len(records), series.ctypes.data_as(C.c_void_p),
+                                                       len(series), out.ctypes.data_as(C.c_void_p), out_series.ctypes.data_as(C.c_void_p),
+                                                       C.byref(n_kept), C.byref(n_series), counters.ctypes.data_as(C.c_void_p)))
+        return out[:n_kept.value], out_series[:n_series.value], dict(zip(PMT_PHOTON_HIT_COUNTERS, (int(c) for c in counters)))
+
+    @staticmethod
+    def PMTPhotonHitsWorkspaceBytes(capacity):
+        return int(_lib.load().clsimhip_pmt_photon_hits_workspace_bytes(int(capacity)))
+
+    def MakeHitsFromFramePhotonsDevice(self, d_records, d_series, d_in_counts, capacity, d_out, d_out_series, d_counts, d_workspace, workspace_bytes,
+                                       device=0, stream=0):
+        """the kernels on device-resident frame photons (addresses, 16-byte aligned; pairs with FramePhotonDoms.MakeFramePhotonsDevice:
+        its d_out, d_series and d_counts): min(d_in_counts[0], capacity) records, min(d_in_counts[1], capacity) series; d_out /
+        d_out_series: `capacity` entries, d_counts: seven uint32 (kept, series, then PMT_PHOTON_HIT_COUNTERS), d_workspace:
+        PMTPhotonHitsWorkspaceBytes(capacity) bytes; capacity <= 2^26"""
+        _check(self._lib.clsimhip_pmt_photon_hits_device(self._h, int(device), C.c_void_p(d_records), C.c_void_p(d_series), C.c_void_p(d_in_counts),
+                                                         int(capacity), C.c_void_p(d_out), C.c_void_p(d_out_series), C.c_void_p(d_counts),
+                                                         C.c_void_p(d_workspace), int(workspace_bytes), C.c_void_p(stream)))
 
 
 # Frame photons (include/clsimhip.h): one record of the result -- an I3CompressedPhoton with the module it is filed under; the

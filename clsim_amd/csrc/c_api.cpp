@@ -20,6 +20,7 @@
 #include "frame_photons.h"
 #include "pmt_series.h"
 #include "photon_hits.h"
+#include "pmt_photon_hits.h"
 
 using namespace clsimhip;
 
@@ -1323,6 +1324,29 @@ int clsimhip_photon_hits_device(clsimhip_photon_hit_maker *g, int device, const 
         need(g, "maker");
         g->impl->device(device, d_records, d_series, d_in_counts, capacity, d_out, d_out_series, d_counts, d_workspace, workspace_bytes,
                         static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+// ---- PMT photon hits (pmt_photon_hits.h) ----
+int clsimhip_pmt_photon_hits_host(const clsimhip_pmt_generator *g, const clsimhip_frame_photon *records, size_t n, const clsimhip_mcpe_series *series,
+                                  size_t n_series, clsimhip_pmt_hit *out, clsimhip_pmt_series *out_series, size_t *n_kept, size_t *n_series_out,
+                                  uint64_t counters[5])
+{
+    return guarded(nullptr, [&] {
+        need(g, "generator");
+        if (counters) std::memset(counters, 0, 5 * sizeof(uint64_t));
+        g->impl->photon_hits_host(records, n, series, n_series, out, out_series, n_kept, n_series_out, counters);
+    });
+}
+size_t clsimhip_pmt_photon_hits_workspace_bytes(size_t capacity) { return pmt_photon_hits_workspace_bytes(capacity); }
+int clsimhip_pmt_photon_hits_device(clsimhip_pmt_generator *g, int device, const void *d_records, const void *d_series, const void *d_in_counts,
+                                    size_t capacity, void *d_out, void *d_out_series, void *d_counts, void *d_workspace, size_t workspace_bytes,
+                                    void *hip_stream)
+{
+    return guarded(nullptr, [&] {
+        need(g, "generator");
+        g->impl->photon_hits_device(device, d_records, d_series, d_in_counts, capacity, d_out, d_out_series, d_counts, d_workspace, workspace_bytes,
+                                    static_cast<hipStream_t>(hip_stream));
     });
 }
 

@@ -179,6 +179,14 @@ public:
                                 void *d_out, void *d_series, void *d_counts, void *d_workspace, size_t workspace_bytes, hipStream_t stream,
                                 hipEvent_t uploaded = nullptr);
 
+    // ---- PMT photon hits (pmt_photon_hits.h; pmt_photon_hits.cpp) ----
+    // host twin: out and out_series hold n entries each; counters[5] += the conditions met
+    void photon_hits_host(const clsimhip_frame_photon *records, size_t n, const clsimhip_mcpe_series *series, size_t n_series, clsimhip_pmt_hit *out,
+                          clsimhip_pmt_series *out_series, size_t *n_kept, size_t *n_series_out, uint64_t counters[5]) const;
+    // the kernels on `stream` of `device`, with the device image convert_device uses
+    void photon_hits_device(int device, const void *d_records, const void *d_series, const void *d_in_counts, size_t capacity, void *d_out, void *d_out_series,
+                            void *d_counts, void *d_workspace, size_t workspace_bytes, hipStream_t stream);
+
 private:
     PmtHitParams params_{};
     std::vector<double> values_;

@@ -1462,6 +1462,64 @@ int clsimhip_photon_hits_device(clsimhip_photon_hit_maker *g, int device, const 
                                 size_t capacity, void *d_out, void *d_out_series, void *d_counts, void *d_workspace, size_t workspace_bytes,
                                 void *hip_stream);
 
+/* ---- PMT photon hits: stored frame photons -> per-frame, per-module, per-PMT time-sorted hits of segmented modules ---------------
+ * The reference's hit maker for segmented modules, I3PhotonToMCHitConverterForMultiPMT::DAQ (private/clsim/dom/
+ * I3PhotonToMCHitConverterForMultiPMT.cxx:244-407), is an offline module: it reads a stored I3PhotonSeriesMap, finds for every
+ * (module, photon) the hit PMT, draws, files the hit under OMKey and PMT number and time-sorts every PMT's vector.  This stage is that
+ * module on clsimhip_frame_photon records with their series table (what the frame photons stage delivers, cable shadow applied if
+ * bound), with the tables, the module list and the seed of a clsimhip_pmt_generator: photons are propagated once, hits are made as
+ * often as needed with another quantum efficiency, collection efficiency or angular acceptance.  Stand-alone, like the photon hits
+ * stage; no converter runs it.
+ * Record i belongs to series s, the last entry of the series table with first <= i (a binary search; nothing checks that `first`
+ * ascends).  Per record, in this order:
+ *     no such entry, or i >= first + count -> UNCOVERED, no hit;
+ *     the record's (string_id, om_id) differ from the entry's -> SERIES_MISMATCH, no hit;
+ *     the module is not one of the generator's -> UNKNOWN_MODULE (log_fatal in the reference, :281-283);
+ *     the generator's geometry and probability, on the record's x, y, z (relative to the module), theta, phi, wavelength and weight:
+ *     a photon that is leaving makes no hit; r^2 outside the type's 3 cm window -> OFF_SURFACE, counted, and the record goes on; the
+ *     PMT met from the front at the shortest path, none -> no hit; P = W x G(wavelength) x Q(wavelength) ce x A(c) / c;
+ *     P > 1 -> PROBABILITY_ABOVE_ONE (log_fatal in the reference, :348-351);
+ *     u = (h >> 11) 2^-53, h = the generator's seed folded with splitmix64 over the record's six little-endian 64-bit words;
+ *     P <= u -> no hit;
+ *     hit = {identifier, string_id, om_id, pmt, reserved 0, time}: the time is the record's, bit for bit (it carries the
+ *     particle's shift already; no arithmetic, so a NaN keeps its sign and payload).
+ * All of it is binary64 + - x / in the order written, never contracted, so the kernels and the host twin give the same bits for every
+ * 48-byte pattern.  Comparisons with a NaN are false, as for the generator: a NaN direction ends on the type's last PMT, a NaN weight
+ * or P yields a hit.
+ * The kept hits come out ascending in (s, pmt, tkey(time), identifier) with the MCPE series' tkey (the key's group is s x 64 + pmt,
+ * so s must stay below 2^26).  The output series table has one clsimhip_pmt_series entry {frame, string_id, om_id, pmt, first, count,
+ * 0} per non-empty (s, pmt) in the same order, with the input entry's frame and IDs; its entries partition the hits.  Hits with equal
+ * keys are byte-identical: the output is a function of the input, the same bytes from run to run and from the kernels and the host
+ * twin.
+ * What differs from the reference, on purpose: the draw (no I3RandomService in arrival order; with one seed the hits made at a lower
+ * collection efficiency are a subset of those made at a higher one); the total order where std::sort(MCHitTimeLess) leaves equal
+ * times open; the path-length argument of the glass / gel survival is not modelled, as for the generator; the MCTree lookup
+ * (:356-360) is the caller's: the hit carries the identifier.  Not pinned against the reference's output, like the rest of the
+ * multi-PMT hit maker (I3OMTypeInfo and I3Orientation are outside it). */
+#define CLSIMHIP_PMT_PHOTON_HITS_UNCOVERED 0            /* index into the five counters */
+#define CLSIMHIP_PMT_PHOTON_HITS_SERIES_MISMATCH 1
+#define CLSIMHIP_PMT_PHOTON_HITS_UNKNOWN_MODULE 2
+#define CLSIMHIP_PMT_PHOTON_HITS_PROBABILITY_ABOVE_ONE 3
+#define CLSIMHIP_PMT_PHOTON_HITS_OFF_SURFACE 4
+/* The host twin: the definition with std::sort on the key, for callers without a GPU and for the tests.  out and out_series hold n
+ * entries each; counters[5] (may be NULL) receives the five counts.  CLSIMHIP_ERR_ARGUMENT for n_series > 2^26. */
+int clsimhip_pmt_photon_hits_host(const clsimhip_pmt_generator *g, const clsimhip_frame_photon *records, size_t n, const clsimhip_mcpe_series *series,
+                                  size_t n_series, clsimhip_pmt_hit *out, clsimhip_pmt_series *out_series, size_t *n_kept, size_t *n_series_out,
+                                  uint64_t counters[5]);
+/* bytes of device memory the kernels need beside their input and output, for up to `capacity` records */
+size_t clsimhip_pmt_photon_hits_workspace_bytes(size_t capacity);
+/* The kernels, on frame photons that live in HBM (pairs with clsimhip_frame_photons_device: d_records = its d_out, d_series = its
+ * d_series, d_in_counts = its d_counts, whose first two words are records kept and series): min(d_in_counts[0], capacity) records,
+ * min(d_in_counts[1], capacity) series entries.  d_out and d_out_series: `capacity` entries each; d_records, d_series, d_out,
+ * d_out_series and d_workspace (clsimhip_pmt_photon_hits_workspace_bytes(capacity) bytes) 16-byte aligned, d_in_counts and d_counts
+ * 4-byte; d_counts: seven uint32 -- hits kept, series, then the five counters (CLSIMHIP_ERR_ARGUMENT for a null or misaligned
+ * pointer, a workspace that is too small or capacity > 2^26; nothing is launched then).  The kernels are asynchronous on hip_stream
+ * (NULL = default stream) and read all sizes from device memory; the generator's tables on the device are those
+ * clsimhip_pmt_convert_device uses (the first of the two calls on a device copies them there), nothing else waits for the device. */
+int clsimhip_pmt_photon_hits_device(clsimhip_pmt_generator *g, int device, const void *d_records, const void *d_series, const void *d_in_counts,
+                                    size_t capacity, void *d_out, void *d_out_series, void *d_counts, void *d_workspace, size_t workspace_bytes,
+                                    void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,10 @@ photon records repeated to N records, dealt to 5160 DOMs and 1000 particles in 1
 host twin; IceCube acceptance, efficiencies from {0.5, 1, 1.35}, pancake 2 of oversize 5 (the time correction is live); --device adds
 the device stage's time for the same input (HIP events around clsimhip_photon_hits_device, best of --repeats; needs a GPU).  The line
 names the core the host twin ran on.
+
+--pmt-photon-hits N: the PMT photon hits' host twin instead (clsimhip_pmt_photon_hits_host), on the same input as --photon-hits, with a
+31-PMT module (tests/pmt_common.py) at every one of the 5160 DOMs; --device adds the device stage's time for the same input (HIP
+events around clsimhip_pmt_photon_hits_device, best of --repeats; needs a GPU).
 """
 import argparse
 import ctypes as C
@@ -283,9 +287,8 @@ def event_statistics_rate(args):
     print(json.dumps(line))
 
 
-def photon_hits_rate(args):
-    from tests import photon_hits_common as P
-    n = args.photon_hits
+def stored_photons(n):
+    """(records, series, string IDs, OM IDs): the committed photon records repeated to n, dealt to 5160 DOMs and 1000 particles in 10 frames"""
     rng = np.random.default_rng(1)
     s, d = np.meshgrid(np.arange(1, 87), np.arange(1, 61), indexing="ij")
     s, d = s.reshape(-1).astype(np.int32), d.reshape(-1).astype(np.uint32)
@@ -297,6 +300,57 @@ def photon_hits_rate(args):
     p = np.zeros(1000, dtype=CV.MCPE_PARTICLE_DTYPE)
     p["id"], p["frame"], p["timeShift"] = np.arange(1000), np.arange(1000) % 10, rng.uniform(0.0, 1.0e6, 1000)
     records, series, _ = CV.FramePhotonDoms(s, d).MakeFramePhotonsHost(m, p)
+    return records, series, s, d
+
+
+def pmt_photon_hits_rate(args):
+    from tests import pmt_common as PC
+    n = args.pmt_photon_hits
+    records, series, s, d = stored_photons(n)
+    types, pmts = PC.layout(PC.sphere_radius_of("mie"))
+    modules = np.zeros(len(s), dtype=CV.PMT_MODULE_DTYPE)
+    modules["stringID"], modules["omID"], modules["rotation"] = s, d, PC.IDENTITY.reshape(9)
+    gen = PC.make_generator(PC.standard_functions(), types, pmts, modules)
+    best = float("inf")
+    for _ in range(args.repeats):
+        t0 = time.perf_counter()
+        hits, table, counters = gen.MakeHitsFromFramePhotonsHost(records, series)
+        best = min(best, time.perf_counter() - t0)
+    assert not any(counters.values())
+    model = [line.split(":", 1)[1].strip() for line in open("/proc/cpuinfo") if line.startswith("model name")][:1]
+    line = {"frame_photons": n, "input_series": len(series), "modules": len(modules), "pmts_per_module": 31, "pmt_hits": len(hits), "series": len(table),
+            "host_seconds": best, "host_records_per_s": n / best, "threads": 1, "host_core": model[0] if model else None}
+    if args.device:
+        import torch
+        dev = torch.device("cuda", 0)
+        d_records = torch.from_numpy(records.view(np.uint8).copy()).to(dev)
+        d_series = torch.zeros(n * 16, dtype=torch.uint8, device=dev)
+        d_series[:len(series) * 16] = torch.from_numpy(series.view(np.uint8).copy()).to(dev)
+        d_in = torch.tensor([n, len(series)], dtype=torch.int32, device=dev)
+        d_out, d_out_series = torch.zeros(n * 24, dtype=torch.uint8, device=dev), torch.zeros(n * 24, dtype=torch.uint8, device=dev)
+        d_counts = torch.zeros(7, dtype=torch.int32, device=dev)
+        ws = CV.PMTHitGenerator.PMTPhotonHitsWorkspaceBytes(n)
+        d_ws = torch.zeros(ws, dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream().cuda_stream
+        times = []
+        for _ in range(args.repeats + 1):
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            gen.MakeHitsFromFramePhotonsDevice(d_records.data_ptr(), d_series.data_ptr(), d_in.data_ptr(), n, d_out.data_ptr(), d_out_series.data_ptr(),
+                                               d_counts.data_ptr(), d_ws.data_ptr(), ws, stream=stream)
+            stop.record()
+            torch.cuda.synchronize()
+            times.append(start.elapsed_time(stop) * 1e-3)
+        assert [int(c) for c in d_counts.cpu()[:2]] == [len(hits), len(table)]
+        assert d_out.cpu().numpy()[:len(hits) * 24].tobytes() == hits.tobytes() and d_out_series.cpu().numpy()[:len(table) * 24].tobytes() == table.tobytes()
+        line.update(device_seconds=min(times[1:]), device_records_per_s=n / min(times[1:]))
+    print(json.dumps(line))
+
+
+def photon_hits_rate(args):
+    from tests import photon_hits_common as P
+    n = args.photon_hits
+    records, series, s, d = stored_photons(n)
     maker = P.maker_of(P.spec(P.dom_table(s, d, efficiencies=(0.5, 1.0, 1.35), spe=1.0), pancake=2.0))
     best = float("inf")
     for _ in range(args.repeats):
@@ -391,7 +445,10 @@ def main():
     ap.add_argument("--cylinders", type=int, default=5160)
     ap.add_argument("--event-statistics", type=int, default=0, metavar="N")
     ap.add_argument("--photon-hits", type=int, default=0, metavar="N")
+    ap.add_argument("--pmt-photon-hits", type=int, default=0, metavar="N")
     args = ap.parse_args()
+    if args.pmt_photon_hits:
+        return pmt_photon_hits_rate(args)
     if args.photon_hits:
         return photon_hits_rate(args)
     if args.event_statistics:

@@ -6,6 +6,7 @@ the stage's kernels beside the propagation kernel.  Prints the counts and the ho
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/mcpe_series_profile.py [--steps 1048576] [--no-series] [--merge-window NS]
                                                                                    [--pmt] [--frame-photons] [--cable-shadow]
                                                                                    [--event-statistics] [--photon-hits]
+                                                                                   [--pmt-photon-hits]
 
 --merge-window NS: the MCPE merging stage behind the series stage, with that window.
 --pmt: a 31-PMT module (tests/pmt_common.py) at every DOM instead: the multi-PMT hit maker and the PMT series stage (--no-series:
@@ -15,6 +16,9 @@ propagation alone, records downloaded).
 --photon-hits: with --frame-photons: the photon hits stage (IceCube acceptance, hole-ice angular acceptance, efficiencies from {0.5, 1,
 1.35}, pancake 2 of oversize 5 so that the time correction is live) on the second bunch's frame photons, uploaded again and run
 twice on the device (the first call copies the maker's tables); the line then carries the stage's counts.
+--pmt-photon-hits: with --frame-photons: the PMT photon hits stage with a 31-PMT module (tests/pmt_common.py) at every DOM on the
+second bunch's frame photons, in the same way; the process then runs --pmt's two bunches as well (the online hit maker and the PMT
+series stage, a second line), so that one trace holds pmt_hits_kernel and the PMT series' kernels beside this stage's.
 --cable-shadow: the cable shadow stage in front of whichever stages the other options choose, with one cable beside every DOM of
 the geometry (5 160 cylinders, in the DOM's own frame: tests/cable_shadow_common.py); the line then carries its two counts.
 --event-statistics: the event statistics stage beside whichever stages the other options choose (with --no-series the bunch has no
@@ -92,6 +96,28 @@ def photon_hits_of(cfg, r):
     return {"records": n, "kept": counts[0], "series": counts[1], "counters": dict(zip(CV.PHOTON_HIT_COUNTERS, counts[2:]))}
 
 
+def pmt_photon_hits_of(cfg, r):
+    """the PMT photon hits stage on the result's frame photons, on the device; {kept, series, counters}"""
+    import torch
+    from tests import pmt_common as PC
+    gen = PC.geometry_generator(cfg)
+    dev = torch.device("cuda", 0)
+    n = len(r.frame_photons)
+    d_records = torch.from_numpy(r.frame_photons.view(np.uint8).copy()).to(dev)
+    d_series = torch.from_numpy(r.frame_photon_series.view(np.uint8).copy()).to(dev)
+    d_in = torch.tensor([n, len(r.frame_photon_series)], dtype=torch.int32, device=dev)
+    d_out, d_out_series = torch.empty(max(n, 1) * 24, dtype=torch.uint8, device=dev), torch.empty(max(n, 1) * 24, dtype=torch.uint8, device=dev)
+    d_counts = torch.zeros(7, dtype=torch.int32, device=dev)
+    ws_bytes = CV.PMTHitGenerator.PMTPhotonHitsWorkspaceBytes(n)
+    d_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    for _ in range(2):
+        gen.MakeHitsFromFramePhotonsDevice(d_records.data_ptr(), d_series.data_ptr(), d_in.data_ptr(), n, d_out.data_ptr(), d_out_series.data_ptr(),
+                                           d_counts.data_ptr(), d_ws.data_ptr(), ws_bytes, stream=torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+    counts = [int(c) for c in d_counts.cpu().numpy()]
+    return {"records": n, "kept": counts[0], "series": counts[1], "counters": dict(zip(CV.PMT_PHOTON_HIT_COUNTERS, counts[2:]))}
+
+
 def frame_photons_bunch(args, cfg, bias):
     conv = CV.initializeHIP(0, CV.I3CLSimSimpleGeometry.from_dict(cfg["geom"]), cfg["med_p"], bias, common.product_generators(cfg, bias), pancakeFactor=5.0,
                             stopDetectedPhotons=True, approximateNumberOfWorkItems=args.steps, keepPhotons=False, framePhotons=not args.no_series,
@@ -109,10 +135,14 @@ def frame_photons_bunch(args, cfg, bias):
         r = conv.GetConversionResult()
         wall = time.perf_counter() - t0
     hits = photon_hits_of(cfg, r) if args.photon_hits and r.frame_photons is not None else None
-    print(json.dumps({"steps": len(steps), "photons": int(steps["num"].sum()), "photon_records": len(r[1]), "photon_hits": hits,
+    pmt_hits = pmt_photon_hits_of(cfg, r) if args.pmt_photon_hits and r.frame_photons is not None else None
+    print(json.dumps({"steps": len(steps), "photons": int(steps["num"].sum()), "photon_records": len(r[1]), "photon_hits": hits, "pmt_photon_hits": pmt_hits,
                       "frame_photons": None if r.frame_photons is None else len(r.frame_photons),
                       "frame_photon_series": None if r.frame_photon_series is None else len(r.frame_photon_series), "cable_shadow": r.shadow_counts,
                       "event_statistics": event_statistics_of(r), "wall_seconds_second_bunch": wall}))
+    if pmt_hits is not None:
+        del conv, r
+        pmt_bunch(args, cfg, bias)
 
 
 def main():
@@ -125,6 +155,7 @@ def main():
     ap.add_argument("--cable-shadow", action="store_true")
     ap.add_argument("--event-statistics", action="store_true")
     ap.add_argument("--photon-hits", action="store_true")
+    ap.add_argument("--pmt-photon-hits", action="store_true")
     args = ap.parse_args()
     cfg = common.config("mie")
     g = cfg["geom"]
