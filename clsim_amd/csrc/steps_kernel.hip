@@ -57,7 +57,13 @@ DS float uniform_co(uint64_t &x)
 }
 DS float uniform_oc(uint64_t &x) { return 1.0f - uniform_co(x); }
 
-// ...ConverterUtils.h:72-105 (Weibull / Cheng, "stolen from PPC"), single precision; the rejection loops are bounded
+// ...ConverterUtils.h:72-105 (Weibull / Cheng, "stolen from PPC"), single precision; the rejection loops are bounded.
+// Two rules keep every call inside the math library's domain:
+//  - a draw that is exactly 1.0f where the formula needs it below 1 is no trial, the loop draws again (Cheng's ry:
+//    ry / (1 - ry) would be +inf, and log_ is defined on positive normal numbers only);
+//  - z^c with c = 1 / shape above 4 is exp_(c log_(z)), and 0 for z = 0: powr_ carries the second word of its logarithm
+//    (up to 0.07) times the exponent into exp unreduced, which keeps it within 1.3 ulp up to an exponent of 4 (16 ulp are
+//    its bound; tests/test_stepgen_reference.py) and loses every digit from 16 on.  Up to 4 it stays powr_(z, c).
 DS float gamma_distributed(float shape, uint64_t &x)
 {
     float v = 0.0f;
@@ -67,7 +73,7 @@ DS float gamma_distributed(float shape, uint64_t &x)
         for (int tries = 0; tries < 256; ++tries) {
             const float z = -dm::log_(uniform_oc(x));
             const float e = -dm::log_(uniform_oc(x));
-            v = dm::powr_(z, c);
+            v = (c <= 4.0f) ? dm::powr_(z, c) : ((z > 0.0f) ? dm::exp_(c * dm::log_(z)) : 0.0f);
             if (!(z + e < d + v)) break;
         }
     } else {
@@ -77,6 +83,7 @@ DS float gamma_distributed(float shape, uint64_t &x)
         for (int tries = 0; tries < 256; ++tries) {
             const float rx = uniform_oc(x);
             const float ry = uniform_oc(x);
+            if (ry == 1.0f) continue;                                 // no trial: draw again
             const float y = dm::log_(ry / (1.0f - ry)) / l;
             v = shape * dm::exp_(y);
             const float z = rx * ry * ry;
@@ -185,7 +192,10 @@ DS float sample_distribution(const clsimhip_distribution d, float parameter, uin
     }
     if (d.kind == CLSIMHIP_DIST_UNIFORM) return uniform_co(x) * (parameter - d.value) + d.value;   // Uniform.cxx:101-103
     // InterpolatedDistribution.cxx:236-336 over the pulse shape (x0 = 0, spacing 0.5 ns)
-    const float r = uniform_oc(x);
+    // the same rule as in Cheng's loop: a draw of exactly 1.0f is no draw.  It would land on the far edge of the last cell
+    // that has any density, where 1 + q below is y[k+1]^2 / b^2 = 0 and its float32 value a rounding error of either sign
+    float r = uniform_oc(x);
+    for (int tries = 0; tries < 256 && r == 1.0f; ++tries) r = uniform_oc(x);
     const float *yv = profile, *cum = profile + 240;
     int lo = 1, hi = 239;
     while (lo < hi) {

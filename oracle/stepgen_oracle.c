@@ -64,7 +64,7 @@ static float gamma_distributed(float shape, uint64_t *x)
         for (int tries = 0; tries < 256; ++tries) {
             const float z = -om_log(uniform_oc(x));
             const float e = -om_log(uniform_oc(x));
-            v = om_powr(z, c);
+            v = (c <= 4.0f) ? om_powr(z, c) : ((z > 0.0f) ? om_exp(c * om_log(z)) : 0.0f);   /* om_powr holds up to 4 */
             if (!(z + e < d + v)) break;
         }
     } else {
@@ -74,6 +74,7 @@ static float gamma_distributed(float shape, uint64_t *x)
         for (int tries = 0; tries < 256; ++tries) {
             const float rx = uniform_oc(x);
             const float ry = uniform_oc(x);
+            if (ry == 1.0f) continue;                                 /* no trial: draw again (steps_kernel.hip) */
             const float y = om_log(ry / (1.0f - ry)) / l;
             v = shape * om_exp(y);
             const float z = rx * ry * ry;
@@ -182,7 +183,8 @@ static float sample_distribution(sg_distribution d, float parameter, uint64_t *x
         return (om_sqrt(-2.0f * om_log(rnd1)) * s) * parameter + d.value;
     }
     if (d.kind == 2) return uniform_co(x) * (parameter - d.value) + d.value;
-    const float r = uniform_oc(x);
+    float r = uniform_oc(x);                                     /* a draw of exactly 1.0f is no draw (steps_kernel.hip) */
+    for (int tries = 0; tries < 256 && r == 1.0f; ++tries) r = uniform_oc(x);
     const float *yv = profile, *cum = profile + 240;
     int k = 0;                                                   /* the reference's linear scan (:262-270) */
     float this_acu = 0.0f;

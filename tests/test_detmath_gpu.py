@@ -147,3 +147,38 @@ def test_reciprocal_root_next_to_one_in_integer_arithmetic():
     renormalisation after a rotation), against the IEEE operations on the device; its range test admits exactly that window"""
     bad, args = check_exhaustive(18, 0, 0)
     assert bad == 0, "%d mismatches, first arguments %s" % (bad, args[:8])
+
+
+# ---- the step producers' domain (clsim_amd/csrc/steps_kernel.hip) ----
+def test_powr_bit_exact_on_the_step_producers_domain(oracle_lib):
+    """two-dimensional samples: z^(1/shape) for z = -log u in (0, 23] and 1/shape in [1, 64] (the Weibull branch
+    calls it up to 1/shape = 4 and takes exp_(c log_ z) above; device and oracle agree bit for bit on all of it although
+    powr loses its accuracy from an exponent of 6 on -- tests/test_stepgen_reference.py holds it to float64 up to 4); the Weibull constant
+    shape^(shape / (1 - shape)), exponents up to 1.7e7; the angular profile's inner^(1/0.39) including +-0"""
+    rng = np.random.Generator(np.random.PCG64(91))
+    x = np.exp(rng.uniform(np.log(5.9604645e-8), np.log(23.0), N)).astype(np.float32)
+    y = rng.uniform(1.0, 64.0, N).astype(np.float32)
+    x[:4], y[:4] = [23.0, 5.9604645e-8, 1.0, 16.635532], [64.0, 64.0, 1.0, 50.0]
+    assert np.array_equal(bits(device_eval(4, x, y)), bits(capi.eval_math(4, x, y)))
+    x = rng.uniform(2.0 ** -6, 1.0, N).astype(np.float32)
+    x[:N // 4] = (1.0 - np.exp(rng.uniform(np.log(2.0 ** -24), 0.0, N // 4))).astype(np.float32)       # dense next to 1
+    x = np.clip(x, np.float32(2.0 ** -6), np.float32(0.99999994))
+    x[:3] = [2.0 ** -6, 0.99999994, 0.5]
+    y = x / (np.float32(1.0) - x)
+    assert y.dtype == np.float32 and y.max() > 1.6e7
+    assert np.array_equal(bits(device_eval(4, x, y)), bits(capi.eval_math(4, x, y)))
+    x = rng.uniform(0.0, 0.6, N).astype(np.float32)
+    x[:4] = [0.0, -0.0, 0.6, 1e-10]
+    y = np.full(N, np.float32(1.0) / np.float32(0.39), dtype=np.float32)
+    got = device_eval(4, x, y)
+    assert np.array_equal(bits(got), bits(capi.eval_math(4, x, y))) and bits(got[:2]).tolist() == [0, 0]
+
+
+def test_log_bit_exact_next_to_ry_one(oracle_lib):
+    """Cheng's log(ry / (1 - ry)) for every ry = 1 - k 2^-24, k = 1 ... 2^16 (ry = 1 itself is no trial)"""
+    k = np.arange(1, (1 << 16) + 1, dtype=np.float64)
+    ry = (1.0 - k * 2.0 ** -24).astype(np.float32)
+    assert np.all(ry < 1.0) and len(np.unique(ry)) == 1 << 16
+    t = ry / (np.float32(1.0) - ry)
+    assert t.dtype == np.float32 and np.isfinite(t).all() and t.max() > 1.6e7
+    assert np.array_equal(bits(device_eval(0, t)), bits(capi.eval_math(0, t)))
