@@ -137,6 +137,11 @@ SYMBOLS = [
     "clsimhip_enqueue_steps_with_particles", "clsimhip_get_result_mcpe_series",
     "clsimhip_mcpe_merge_host", "clsimhip_mcpe_merge_workspace_bytes", "clsimhip_mcpe_merge_device", "clsimhip_set_mcpe_merging",
     "clsimhip_get_result_mcpe_merged",
+    "clsimhip_mcpe_series_union_host", "clsimhip_mcpe_series_split_host", "clsimhip_mcpe_series_union_workspace_bytes",
+    "clsimhip_mcpe_series_union_device", "clsimhip_mcpe_series_split_device",
+    "clsimhip_mcpe_frame_store_create", "clsimhip_mcpe_frame_store_destroy", "clsimhip_mcpe_frame_store_last_error",
+    "clsimhip_mcpe_frame_store_add_host", "clsimhip_mcpe_frame_store_add_device", "clsimhip_mcpe_frame_store_drain_device",
+    "clsimhip_mcpe_frame_store_drain_host", "clsimhip_mcpe_frame_store_size",
     "clsimhip_pmt_generator_create", "clsimhip_pmt_generator_destroy", "clsimhip_pmt_generator_last_error",
     "clsimhip_pmt_convert_host", "clsimhip_pmt_convert_device", "clsimhip_set_pmt_generator", "clsimhip_get_result_pmt_hits",
     "clsimhip_pmt_series_host", "clsimhip_pmt_series_workspace_bytes", "clsimhip_pmt_series_device", "clsimhip_set_pmt_series",
@@ -330,6 +335,19 @@ def load():
         "clsimhip_mcpe_merge_device": (i32, [vp, i32, vp, vp, vp, sz, C.c_double, vp, vp, vp, vp, vp, vp, sz, vp]),
         "clsimhip_set_mcpe_merging": (i32, [vp, i32, C.c_double]),
         "clsimhip_get_result_mcpe_merged": (i32, [vp, vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(vp)]),
+        "clsimhip_mcpe_series_union_host": (i32, [vp, sz, vp, sz, vp, sz, vp, sz, vp, vp, sz, C.POINTER(sz), C.POINTER(sz)]),
+        "clsimhip_mcpe_series_split_host": (i32, [vp, sz, vp, sz, u32, vp, vp, sz, C.POINTER(sz), C.POINTER(sz), vp, vp, sz, C.POINTER(sz), C.POINTER(sz)]),
+        "clsimhip_mcpe_series_union_workspace_bytes": (sz, [sz, sz]),
+        "clsimhip_mcpe_series_union_device": (i32, [i32, vp, vp, vp, sz, vp, vp, vp, sz, vp, vp, vp, sz, vp, sz, vp]),
+        "clsimhip_mcpe_series_split_device": (i32, [i32, vp, vp, vp, sz, u32, vp, vp, vp, sz, vp, vp, vp, sz, vp]),
+        "clsimhip_mcpe_frame_store_create": (i32, [i32, sz, C.POINTER(vp)]),
+        "clsimhip_mcpe_frame_store_destroy": (None, [vp]),
+        "clsimhip_mcpe_frame_store_last_error": (C.c_char_p, [vp]),
+        "clsimhip_mcpe_frame_store_add_host": (i32, [vp, vp, sz, vp, sz]),
+        "clsimhip_mcpe_frame_store_add_device": (i32, [vp, vp, vp, vp, sz, vp]),
+        "clsimhip_mcpe_frame_store_drain_device": (i32, [vp, u32, vp, vp, vp, sz, vp]),
+        "clsimhip_mcpe_frame_store_drain_host": (i32, [vp, u32, vp, vp, sz, C.POINTER(sz), C.POINTER(sz)]),
+        "clsimhip_mcpe_frame_store_size": (i32, [vp, u32, C.POINTER(sz), C.POINTER(sz)]),
         "clsimhip_pmt_generator_create": (i32, [C.POINTER(Function), sz, vp, sz, vp, sz, vp, sz, u64, C.POINTER(vp)]),
         "clsimhip_pmt_generator_destroy": (None, [vp]),
         "clsimhip_pmt_generator_last_error": (C.c_char_p, [vp]),
@@ -379,9 +397,9 @@ def load():
     }
     for name in SYMBOLS:
         # (A/B measurements load an older build through CLSIMHIP_LIB: it may lack the entries of the run-time compiled kernel, of the event
-        # statistics stage and of the photon hits stage, which bench.py does not call)
+        # statistics stage, of the photon hits stage and of the MCPE frame store, which bench.py does not call)
         newer = (name in ("clsimhip_baked_info", "clsimhip_baked_compile", "clsimhip_baked_set_compiler_library") or "event_statistics" in name
-                 or "photon_hit" in name)
+                 or "photon_hit" in name or "mcpe_series_union" in name or "mcpe_series_split" in name or "mcpe_frame_store" in name)
         if newer and LIB_PATH != DEFAULT_LIB_PATH and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol

@@ -461,6 +461,145 @@ class MCPEGenerator:
                                                     C.c_void_p(d_parents), C.c_void_p(d_ranges), C.c_void_p(d_counts), C.c_void_p(d_workspace),
                                                     int(workspace_bytes), C.c_void_p(stream)))
 
+    # ---- MCPE frame store (include/clsimhip.h): union and split of series forms ----
+    @staticmethod
+    def UnionHost(a_records, a_series, b_records, b_series, capacity=None):
+        """(records, series): the host twin of the union of two series forms (MCPE_DTYPE records with their MCPE_SERIES_DTYPE table, as
+        MakeSeriesHost returns them); capacity: of the output, len(a) + len(b) by default"""
+        a_records, b_records = (np.ascontiguousarray(r, dtype=MCPE_DTYPE) for r in (a_records, b_records))
+        a_series, b_series = (np.ascontiguousarray(s, dtype=MCPE_SERIES_DTYPE) for s in (a_series, b_series))
+        capacity = len(a_records) + len(b_records) if capacity is None else int(capacity)
+        out, series = np.zeros(capacity, dtype=MCPE_DTYPE), np.zeros(capacity, dtype=MCPE_SERIES_DTYPE)
+        n, n_series = C.c_size_t(), C.c_size_t()
+        _check(_lib.load().clsimhip_mcpe_series_union_host(a_records.ctypes.data_as(C.c_void_p), len(a_records), a_series.ctypes.data_as(C.c_void_p), len(a_series),
+                                                           b_records.ctypes.data_as(C.c_void_p), len(b_records), b_series.ctypes.data_as(C.c_void_p), len(b_series),
+                                                           out.ctypes.data_as(C.c_void_p), series.ctypes.data_as(C.c_void_p), capacity, C.byref(n), C.byref(n_series)))
+        return out[:n.value], series[:n_series.value]
+
+    @staticmethod
+    def SplitHost(records, series, last_frame, head_capacity=None, tail_capacity=None):
+        """(head_records, head_series, tail_records, tail_series): the host twin of the split -- the head holds the frames <= last_frame"""
+        records = np.ascontiguousarray(records, dtype=MCPE_DTYPE)
+        series = np.ascontiguousarray(series, dtype=MCPE_SERIES_DTYPE)
+        head_capacity = len(records) if head_capacity is None else int(head_capacity)
+        tail_capacity = len(records) if tail_capacity is None else int(tail_capacity)
+        head, head_series = np.zeros(head_capacity, dtype=MCPE_DTYPE), np.zeros(head_capacity, dtype=MCPE_SERIES_DTYPE)
+        tail, tail_series = np.zeros(tail_capacity, dtype=MCPE_DTYPE), np.zeros(tail_capacity, dtype=MCPE_SERIES_DTYPE)
+        sizes = [C.c_size_t() for _ in range(4)]
+        _check(_lib.load().clsimhip_mcpe_series_split_host(records.ctypes.data_as(C.c_void_p), len(records), series.ctypes.data_as(C.c_void_p), len(series),
+                                                           int(last_frame), head.ctypes.data_as(C.c_void_p), head_series.ctypes.data_as(C.c_void_p), head_capacity,
+                                                           C.byref(sizes[0]), C.byref(sizes[1]), tail.ctypes.data_as(C.c_void_p),
+                                                           tail_series.ctypes.data_as(C.c_void_p), tail_capacity, C.byref(sizes[2]), C.byref(sizes[3])))
+        return head[:sizes[0].value], head_series[:sizes[1].value], tail[:sizes[2].value], tail_series[:sizes[3].value]
+
+    @staticmethod
+    def UnionWorkspaceBytes(capacity_a, capacity_b):
+        return int(_lib.load().clsimhip_mcpe_series_union_workspace_bytes(int(capacity_a), int(capacity_b)))
+
+    @staticmethod
+    def UnionDevice(d_a_records, d_a_series, d_a_counts, capacity_a, d_b_records, d_b_series, d_b_counts, capacity_b, d_out_records, d_out_series,
+                    d_out_counts, out_capacity, d_workspace, workspace_bytes, device=0, stream=0):
+        """the kernels on device-resident series forms (addresses; each input pairs with MakeSeriesDevice's d_out, d_series and d_counts,
+        or with another union's output); d_out_counts: five uint32 (MCPE_UNION_COUNTS), d_workspace: UnionWorkspaceBytes(capacity_a,
+        capacity_b) bytes"""
+        _check(_lib.load().clsimhip_mcpe_series_union_device(int(device), C.c_void_p(d_a_records), C.c_void_p(d_a_series), C.c_void_p(d_a_counts), int(capacity_a),
+                                                             C.c_void_p(d_b_records), C.c_void_p(d_b_series), C.c_void_p(d_b_counts), int(capacity_b),
+                                                             C.c_void_p(d_out_records), C.c_void_p(d_out_series), C.c_void_p(d_out_counts), int(out_capacity),
+                                                             C.c_void_p(d_workspace), int(workspace_bytes), C.c_void_p(stream)))
+
+    @staticmethod
+    def SplitDevice(d_records, d_series, d_counts, capacity, last_frame, d_head_records, d_head_series, d_head_counts, head_capacity, d_tail_records,
+                    d_tail_series, d_tail_counts, tail_capacity, device=0, stream=0):
+        """the split on device-resident series (addresses); d_head_counts / d_tail_counts: five uint32 each (records, series, 0, 0, overflow)"""
+        _check(_lib.load().clsimhip_mcpe_series_split_device(int(device), C.c_void_p(d_records), C.c_void_p(d_series), C.c_void_p(d_counts), int(capacity),
+                                                             int(last_frame), C.c_void_p(d_head_records), C.c_void_p(d_head_series), C.c_void_p(d_head_counts),
+                                                             int(head_capacity), C.c_void_p(d_tail_records), C.c_void_p(d_tail_series), C.c_void_p(d_tail_counts),
+                                                             int(tail_capacity), C.c_void_p(stream)))
+
+
+# MCPE frame store (include/clsimhip.h): the five output counts of a union on the device
+MCPE_UNION_COUNTS = ("records", "series", "malformed_a", "malformed_b", "overflow")
+ALL_FRAMES = 0xFFFFFFFF
+
+
+class MCPEFrameStore:
+    """The series of several bunches accumulate per frame; finished frames leave (clsimhip_mcpe_frame_store).  device=None: a host
+    store, which needs no GPU; device=k: the state lives in HBM of GPU k.  Call Add (or AddDevice) per result and Drain with the last
+    frame no bunch in flight can still touch."""
+
+    def __init__(self, capacity, device=None):
+        self._lib = _lib.load()
+        self._h = C.c_void_p()
+        self.capacity, self.device = int(capacity), device
+        _check(self._lib.clsimhip_mcpe_frame_store_create(-1 if device is None else int(device), self.capacity, C.byref(self._h)))
+
+    def __del__(self):
+        try:
+            if self._h:
+                self._lib.clsimhip_mcpe_frame_store_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def Add(self, records, series):
+        """one bunch in host memory, a series form (MakeSeriesHost's records and series, or a result's mcpes and series)"""
+        records = np.ascontiguousarray(records, dtype=MCPE_DTYPE)
+        series = np.ascontiguousarray(series, dtype=MCPE_SERIES_DTYPE)
+        _check(self._lib.clsimhip_mcpe_frame_store_add_host(self._h, records.ctypes.data_as(C.c_void_p), len(records), series.ctypes.data_as(C.c_void_p), len(series)))
+
+    def AddDevice(self, d_records, d_series, d_series_counts, capacity, stream=0):
+        """one bunch in HBM (addresses: MakeSeriesDevice's d_out, d_series and d_counts); asynchronous on `stream`"""
+        _check(self._lib.clsimhip_mcpe_frame_store_add_device(self._h, C.c_void_p(d_records), C.c_void_p(d_series), C.c_void_p(d_series_counts), int(capacity),
+                                                              C.c_void_p(stream)))
+
+    def Size(self, last_frame=ALL_FRAMES):
+        """(records, series) a Drain up to last_frame would take; waits"""
+        n, n_series = C.c_size_t(), C.c_size_t()
+        _check(self._lib.clsimhip_mcpe_frame_store_size(self._h, int(last_frame), C.byref(n), C.byref(n_series)))
+        return n.value, n_series.value
+
+    def Drain(self, last_frame=ALL_FRAMES):
+        """(records, series) of the frames <= last_frame, which leave the store; waits"""
+        n, n_series = self.Size(last_frame)
+        records, series = np.zeros(n, dtype=MCPE_DTYPE), np.zeros(n_series, dtype=MCPE_SERIES_DTYPE)
+        got, got_series = C.c_size_t(), C.c_size_t()
+        _check(self._lib.clsimhip_mcpe_frame_store_drain_host(self._h, int(last_frame), records.ctypes.data_as(C.c_void_p), series.ctypes.data_as(C.c_void_p),
+                                                              n, C.byref(got), C.byref(got_series)))
+        return records[:got.value], series[:got_series.value]
+
+    def DrainDevice(self, last_frame, d_records, d_series, d_counts, capacity, stream=0):
+        """the frames <= last_frame move to the caller's device buffers (addresses; d_counts: five uint32, records and series first);
+        asynchronous on `stream`"""
+        _check(self._lib.clsimhip_mcpe_frame_store_drain_device(self._h, int(last_frame), C.c_void_p(d_records), C.c_void_p(d_series), C.c_void_p(d_counts),
+                                                                int(capacity), C.c_void_p(stream)))
+
+    def DrainMerged(self, last_frame, window, generator=None):
+        """(merged, merged_series, parents, parent_ranges) of the frames <= last_frame, as MCPEGenerator.MergeHost returns them.  A host
+        store: Drain -> MergeHost; a device store: DrainDevice -> generator.MergeDevice (the MCPEGenerator whose series these are) ->
+        download"""
+        if self.device is None:
+            return MCPEGenerator.MergeHost(*self.Drain(last_frame), window)
+        if generator is None:
+            raise ValueError("DrainMerged on a device store needs the MCPEGenerator whose series these are (MergeDevice is its method)")
+        import torch
+        dev = torch.device("cuda", int(self.device))
+        capacity = max(self.Size(last_frame)[0], 1)
+        sizes = (MCPE_DTYPE.itemsize, MCPE_SERIES_DTYPE.itemsize, MCPE_MERGED_DTYPE.itemsize, MCPE_SERIES_DTYPE.itemsize, MCPE_PARENT_DTYPE.itemsize,
+                 MCPE_PARENT_RANGE_DTYPE.itemsize)
+        d_records, d_series, d_merged, d_merged_series, d_parents, d_ranges = (torch.zeros(capacity * s, dtype=torch.uint8, device=dev) for s in sizes)
+        d_counts, d_merged_counts = torch.zeros(5, dtype=torch.int32, device=dev), torch.zeros(2, dtype=torch.int32, device=dev)
+        ws_bytes = MCPEGenerator.MergeWorkspaceBytes(capacity)
+        d_ws = torch.zeros(ws_bytes, dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        self.DrainDevice(last_frame, d_records.data_ptr(), d_series.data_ptr(), d_counts.data_ptr(), capacity, stream=stream)
+        generator.MergeDevice(d_records.data_ptr(), d_series.data_ptr(), d_counts.data_ptr(), capacity, window, d_merged.data_ptr(), d_merged_series.data_ptr(),
+                              d_parents.data_ptr(), d_ranges.data_ptr(), d_merged_counts.data_ptr(), d_ws.data_ptr(), ws_bytes, device=int(self.device), stream=stream)
+        n_series = int(d_counts.cpu().numpy()[1])
+        n_merged, n_parents = (int(c) for c in d_merged_counts.cpu().numpy())
+        take = lambda t, dtype, n: t.cpu().numpy()[:n * dtype.itemsize].copy().view(dtype).reshape(-1)
+        return (take(d_merged, MCPE_MERGED_DTYPE, n_merged), take(d_merged_series, MCPE_SERIES_DTYPE, n_series), take(d_parents, MCPE_PARENT_DTYPE, n_parents),
+                take(d_ranges, MCPE_PARENT_RANGE_DTYPE, n_series))
+
 
 # Multi-PMT hit generator (include/clsimhip.h): clsimhip_pmt_type, clsimhip_pmt, clsimhip_pmt_module and clsimhip_pmt_hit
 PMT_TYPE_DTYPE = np.dtype([("sphereRadius", "<f8"), ("firstPMT", "<i4"), ("numPMTs", "<i4"), ("glassGelSurvival", "<i4"), ("reserved", "<i4")])

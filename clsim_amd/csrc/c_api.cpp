@@ -14,6 +14,7 @@
 #include "flasher.h"
 #include "mcpe.h"
 #include "mcpe_merge.h"
+#include "mcpe_union.h"
 #include "pmt_hits.h"
 #include "cable_shadow.h"
 #include "event_stats.h"
@@ -31,6 +32,7 @@ struct clsimhip_pmt_generator { std::shared_ptr<PmtHitGenerator> impl; };
 struct clsimhip_frame_photon_doms { std::shared_ptr<FramePhotonDoms> impl; };
 struct clsimhip_cable_shadow { std::shared_ptr<CableShadow> impl; };
 struct clsimhip_photon_hit_maker { std::shared_ptr<PhotonHitMaker> impl; };
+struct clsimhip_mcpe_frame_store { std::unique_ptr<FrameStore> impl; };
 struct clsimhip_tabulator {
     std::unique_ptr<Tabulator> impl;
 };
@@ -1094,6 +1096,82 @@ int clsimhip_get_result_mcpe_merged(clsimhip_converter *c, const clsimhip_photon
                                     const clsimhip_mcpe_parent **parents, size_t *n_parents, const clsimhip_mcpe_parent_range **ranges)
 {
     return guarded(c, [&] { need(c, "converter"); c->impl.result_mcpe_merged(photons, merged, n_merged, series, n_series, parents, n_parents, ranges); });
+}
+
+// ---- MCPE frame store (mcpe_union.h) ----
+int clsimhip_mcpe_series_union_host(const clsimhip_mcpe *a_records, size_t n_a, const clsimhip_mcpe_series *a_series, size_t n_series_a,
+                                    const clsimhip_mcpe *b_records, size_t n_b, const clsimhip_mcpe_series *b_series, size_t n_series_b,
+                                    clsimhip_mcpe *out_records, clsimhip_mcpe_series *out_series, size_t out_capacity, size_t *n, size_t *n_series)
+{
+    return guarded(nullptr, [&] {
+        mcpe_series_union_host(a_records, n_a, a_series, n_series_a, b_records, n_b, b_series, n_series_b, out_records, out_series, out_capacity, n, n_series);
+    });
+}
+int clsimhip_mcpe_series_split_host(const clsimhip_mcpe *records, size_t n, const clsimhip_mcpe_series *series, size_t n_series, uint32_t last_frame,
+                                    clsimhip_mcpe *head_records, clsimhip_mcpe_series *head_series, size_t head_capacity, size_t *n_head,
+                                    size_t *n_series_head, clsimhip_mcpe *tail_records, clsimhip_mcpe_series *tail_series, size_t tail_capacity,
+                                    size_t *n_tail, size_t *n_series_tail)
+{
+    return guarded(nullptr, [&] {
+        mcpe_series_split_host(records, n, series, n_series, last_frame, head_records, head_series, head_capacity, n_head, n_series_head, tail_records, tail_series,
+                               tail_capacity, n_tail, n_series_tail);
+    });
+}
+size_t clsimhip_mcpe_series_union_workspace_bytes(size_t capacity_a, size_t capacity_b)
+{
+    return mcpe_union_workspace_bytes(capacity_a, capacity_b);
+}
+int clsimhip_mcpe_series_union_device(int device, const void *d_a_records, const void *d_a_series, const void *d_a_counts, size_t capacity_a,
+                                      const void *d_b_records, const void *d_b_series, const void *d_b_counts, size_t capacity_b,
+                                      void *d_out_records, void *d_out_series, void *d_out_counts, size_t out_capacity, void *d_workspace,
+                                      size_t workspace_bytes, void *hip_stream)
+{
+    return guarded(nullptr, [&] {
+        mcpe_union_device(device, d_a_records, d_a_series, d_a_counts, capacity_a, d_b_records, d_b_series, d_b_counts, capacity_b, d_out_records, d_out_series,
+                          d_out_counts, out_capacity, d_workspace, workspace_bytes, static_cast<hipStream_t>(hip_stream));
+    });
+}
+int clsimhip_mcpe_series_split_device(int device, const void *d_records, const void *d_series, const void *d_counts, size_t capacity,
+                                      uint32_t last_frame, void *d_head_records, void *d_head_series, void *d_head_counts, size_t head_capacity,
+                                      void *d_tail_records, void *d_tail_series, void *d_tail_counts, size_t tail_capacity, void *hip_stream)
+{
+    return guarded(nullptr, [&] {
+        mcpe_split_device(device, d_records, d_series, d_counts, capacity, last_frame, d_head_records, d_head_series, d_head_counts, head_capacity, d_tail_records,
+                          d_tail_series, d_tail_counts, tail_capacity, static_cast<hipStream_t>(hip_stream));
+    });
+}
+int clsimhip_mcpe_frame_store_create(int device, size_t capacity, clsimhip_mcpe_frame_store **out)
+{
+    return guarded(nullptr, [&] {
+        need(out, "out");
+        *out = new clsimhip_mcpe_frame_store{device < 0 ? make_host_frame_store(capacity) : make_device_frame_store(device, capacity)};
+    });
+}
+void clsimhip_mcpe_frame_store_destroy(clsimhip_mcpe_frame_store *s) { delete s; }
+const char *clsimhip_mcpe_frame_store_last_error(const clsimhip_mcpe_frame_store *s) { (void)s; return g_last_error.c_str(); }
+int clsimhip_mcpe_frame_store_add_host(clsimhip_mcpe_frame_store *s, const clsimhip_mcpe *records, size_t n, const clsimhip_mcpe_series *series,
+                                       size_t n_series)
+{
+    return guarded(nullptr, [&] { need(s, "store"); s->impl->add_host(records, n, series, n_series); });
+}
+int clsimhip_mcpe_frame_store_add_device(clsimhip_mcpe_frame_store *s, const void *d_records, const void *d_series, const void *d_series_counts,
+                                         size_t capacity, void *hip_stream)
+{
+    return guarded(nullptr, [&] { need(s, "store"); s->impl->add_device(d_records, d_series, d_series_counts, capacity, static_cast<hipStream_t>(hip_stream)); });
+}
+int clsimhip_mcpe_frame_store_drain_device(clsimhip_mcpe_frame_store *s, uint32_t last_frame, void *d_records, void *d_series, void *d_counts,
+                                           size_t capacity, void *hip_stream)
+{
+    return guarded(nullptr, [&] { need(s, "store"); s->impl->drain_device(last_frame, d_records, d_series, d_counts, capacity, static_cast<hipStream_t>(hip_stream)); });
+}
+int clsimhip_mcpe_frame_store_drain_host(clsimhip_mcpe_frame_store *s, uint32_t last_frame, clsimhip_mcpe *records, clsimhip_mcpe_series *series,
+                                         size_t capacity, size_t *n, size_t *n_series)
+{
+    return guarded(nullptr, [&] { need(s, "store"); s->impl->drain_host(last_frame, records, series, capacity, n, n_series); });
+}
+int clsimhip_mcpe_frame_store_size(clsimhip_mcpe_frame_store *s, uint32_t last_frame, size_t *n, size_t *n_series)
+{
+    return guarded(nullptr, [&] { need(s, "store"); s->impl->size(last_frame, n, n_series); });
 }
 
 // ---- Multi-PMT hit generator (pmt_hits.h) ----

@@ -963,6 +963,82 @@ int clsimhip_get_result_mcpe_merged(clsimhip_converter *c, const clsimhip_photon
                                     size_t *n_merged, const clsimhip_mcpe_series **series, size_t *n_series,
                                     const clsimhip_mcpe_parent **parents, size_t *n_parents, const clsimhip_mcpe_parent_range **ranges);
 
+/* ---- MCPE frame store: the series of several bunches accumulate per frame; finished frames leave ----------------------------
+ * A frame's light is rarely one bunch.  The reference's client module files every result's hits into a frame cache that lives
+ * across bunches (private/clsim/I3CLSimClientModule.cxx:359-439, frame->hits) and FlushFrameCache() commits a prefix of it, oldest
+ * frames first, up to the last frame no bunch in flight still holds work for (:686-758, framesForBunches_, lastPendingFrame).  Here:
+ * SERIES FORM: (records, table) as the series stage writes and the merging stage reads.  The table is strictly ascending in
+ *     (frame, string_id signed, om_id); every count > 0; first[0] = 0 and first[s] = first[s-1] + count[s-1]; the last entry ends
+ *     at the number of records (an empty table needs zero records); every record carries its entry's string_id and om_id; inside a
+ *     series (tkey(time), identifier) does not descend.  Each element (entry or record) that breaks one of these rules is one
+ *     MALFORMED element; the checks are local and together they imply the partition.
+ * KEY of a record: (frame of its entry, string_id signed, om_id, tkey, identifier), compared as integers.
+ * UNION(A, B): the series form of the multiset union -- records ascending in the key, the table rebuilt from the heads.  Ties take
+ *     A's record first, which changes no byte.  Equal keys are equal bytes, so the union is a function of the multiset: the same
+ *     bytes whatever order the bunches arrive in, and for any split of a bunch's MCPEs into two parts with one particle table and
+ *     mask the union of their series is the series of the whole, byte for byte.  n_a + n_b must fit the output capacity.
+ * SPLIT(X, last_frame): the head is the entries with frame <= last_frame and their records, a prefix; the tail is the rest with
+ *     `first` rebased to 0.  last_frame = 0xFFFFFFFF drains everything.
+ * The host twins (std::merge on the key; host only, no GPU is touched): malformed input or an output that does not fit is
+ * CLSIMHIP_ERR_ARGUMENT with text that names the first offending element.  out_records and out_series hold out_capacity entries. */
+int clsimhip_mcpe_series_union_host(const clsimhip_mcpe *a_records, size_t n_a, const clsimhip_mcpe_series *a_series, size_t n_series_a,
+                                    const clsimhip_mcpe *b_records, size_t n_b, const clsimhip_mcpe_series *b_series, size_t n_series_b,
+                                    clsimhip_mcpe *out_records, clsimhip_mcpe_series *out_series, size_t out_capacity, size_t *n, size_t *n_series);
+int clsimhip_mcpe_series_split_host(const clsimhip_mcpe *records, size_t n, const clsimhip_mcpe_series *series, size_t n_series, uint32_t last_frame,
+                                    clsimhip_mcpe *head_records, clsimhip_mcpe_series *head_series, size_t head_capacity, size_t *n_head,
+                                    size_t *n_series_head, clsimhip_mcpe *tail_records, clsimhip_mcpe_series *tail_series, size_t tail_capacity,
+                                    size_t *n_tail, size_t *n_series_tail);
+/* bytes of device memory the union's kernels need beside their inputs and output */
+size_t clsimhip_mcpe_series_union_workspace_bytes(size_t capacity_a, size_t capacity_b);
+/* The kernels, on series that live in HBM.  Inputs are read as clsimhip_mcpe_merge_device reads them: min(counts[0], capacity)
+ * records, min(counts[1], capacity) series.  d_out_records and d_out_series: out_capacity entries each; d_out_counts: five uint32
+ * -- records, series, MALFORMED elements in A, MALFORMED elements in B, overflow (n_a + n_b when it does not fit out_capacity, else
+ * 0); the first two follow the series stage's layout, so the output chains into another union, into the split and into
+ * clsimhip_mcpe_merge_device unchanged.  When B is malformed or the union does not fit, the output is A unchanged (nothing, should
+ * A alone not fit); when A is malformed, the output is empty.  Nothing is written beyond a capacity and every loop is bounded by
+ * one, whatever bytes the inputs hold.  The output must not overlap an input.  Records, tables and d_workspace
+ * (clsimhip_mcpe_series_union_workspace_bytes(capacity_a, capacity_b) bytes) are 16-byte aligned; capacities are at most 2^31.
+ * Asynchronous on hip_stream (NULL = default stream); nothing waits for the device.  Errors are CLSIMHIP_ERR_ARGUMENT. */
+int clsimhip_mcpe_series_union_device(int device, const void *d_a_records, const void *d_a_series, const void *d_a_counts, size_t capacity_a,
+                                      const void *d_b_records, const void *d_b_series, const void *d_b_counts, size_t capacity_b,
+                                      void *d_out_records, void *d_out_series, void *d_out_counts, size_t out_capacity, void *d_workspace,
+                                      size_t workspace_bytes, void *hip_stream);
+/* The split on the device; the input is taken as a series form and not checked again.  d_head_counts and d_tail_counts: five uint32
+ * each in the union's layout -- records, series, 0, 0, overflow.  A head that does not fit head_capacity drains nothing: the head is
+ * empty, the tail is everything, and the needed size goes into the head's overflow word.  tail_capacity >= capacity
+ * (CLSIMHIP_ERR_ARGUMENT otherwise).  Asynchronous on hip_stream. */
+int clsimhip_mcpe_series_split_device(int device, const void *d_records, const void *d_series, const void *d_counts, size_t capacity,
+                                      uint32_t last_frame, void *d_head_records, void *d_head_series, void *d_head_counts, size_t head_capacity,
+                                      void *d_tail_records, void *d_tail_series, void *d_tail_counts, size_t tail_capacity, void *hip_stream);
+/* The store owns the accumulated series form and gives up finished frames.  device < 0: a host store, which uses only the twins and
+ * needs no GPU.  A device store owns two record and table buffers of `capacity` entries, used in turn, its workspace, five sticky
+ * counters and one event; every operation waits for the event on the caller's stream and records it again, so operations issued
+ * on different streams are ordered as they were called.  capacity is at most 2^31. */
+typedef struct clsimhip_mcpe_frame_store clsimhip_mcpe_frame_store;
+int clsimhip_mcpe_frame_store_create(int device, size_t capacity, clsimhip_mcpe_frame_store **out);
+void clsimhip_mcpe_frame_store_destroy(clsimhip_mcpe_frame_store *s);
+const char *clsimhip_mcpe_frame_store_last_error(const clsimhip_mcpe_frame_store *s);
+/* One bunch in host memory: validated on the host before anything moves (CLSIMHIP_ERR_ARGUMENT leaves the store unchanged; a host
+ * store also refuses the bunch that does not fit).  A device store uploads it. */
+int clsimhip_mcpe_frame_store_add_host(clsimhip_mcpe_frame_store *s, const clsimhip_mcpe *records, size_t n, const clsimhip_mcpe_series *series,
+                                       size_t n_series);
+/* One bunch in HBM (pairs with clsimhip_mcpe_series_device: its d_out, d_series and d_counts; capacity at most the store's).  Device
+ * store only (CLSIMHIP_ERR_STATE otherwise), asynchronous on hip_stream.  A malformed bunch, or one that does not fit, is dropped
+ * whole and counted in the sticky counters; the store carries on unchanged. */
+int clsimhip_mcpe_frame_store_add_device(clsimhip_mcpe_frame_store *s, const void *d_records, const void *d_series, const void *d_series_counts,
+                                         size_t capacity, void *hip_stream);
+/* Moves the frames up to last_frame out on the device (for clsimhip_mcpe_merge_device behind it; d_counts: five uint32 as the
+ * split's head); the tail becomes the store.  Device store only, asynchronous on hip_stream. */
+int clsimhip_mcpe_frame_store_drain_device(clsimhip_mcpe_frame_store *s, uint32_t last_frame, void *d_records, void *d_series, void *d_counts,
+                                           size_t capacity, void *hip_stream);
+/* The same plus the download: the one call that waits.  With too small a capacity: CLSIMHIP_ERR_ARGUMENT, the store unchanged. */
+int clsimhip_mcpe_frame_store_drain_host(clsimhip_mcpe_frame_store *s, uint32_t last_frame, clsimhip_mcpe *records, clsimhip_mcpe_series *series,
+                                         size_t capacity, size_t *n, size_t *n_series);
+/* What a drain up to last_frame would take.  Waits.  While any sticky counter is nonzero, both drain calls and this one return
+ * CLSIMHIP_ERR_DEVICE with the counts in the text (a drain on the device learns of bunches whose union has run; its kernel looks
+ * again) and nothing is delivered: data loss is loud, as a bunch with UNKNOWN_PARTICLE is. */
+int clsimhip_mcpe_frame_store_size(clsimhip_mcpe_frame_store *s, uint32_t last_frame, size_t *n, size_t *n_series);
+
 /* ---- Multi-PMT hit generator: detected photons -> hits on the PMTs of segmented modules ---------------------------------
  * The hit maker for modules that carry several PMTs (KM3NeT-style spheres): FindHitPMT and the per-photon body of
  * I3PhotonToMCHitConverterForMultiPMT::DAQ (private/clsim/dom/I3PhotonToMCHitConverterForMultiPMT.cxx:111-227, 297-382).  A pure

@@ -12,6 +12,12 @@ for the same input (HIP events around clsimhip_mcpe_series_device, best of --rep
 particles as a long chain of groups (window 5 ns) and as one group, and on 300 000 synthetic records in 420 series (window 2 ns);
 --device adds the device stage's time for the same inputs (HIP events around clsimhip_mcpe_merge_device; needs a GPU).
 
+--union N M: the MCPE frame store's union instead (clsimhip_mcpe_series_union_host, one thread), in records per second: a store of the
+series of N synthetic MCPEs meets a bunch of the series of M more, at IceCube's 5160 DOMs dealt to 1000 particles in 10 frames;
+--one-dom puts every record on one DOM of one frame (one series across all output tiles).  --device adds the union kernels' time for
+the same input (HIP events around clsimhip_mcpe_series_union_device, best of --repeats; needs a GPU) and, as the yardstick, the
+series stage re-sorting the N + M MCPEs (clsimhip_mcpe_series_device) in the same run.
+
 --pmt: the multi-PMT hit generator's host twin instead (clsimhip_pmt_convert_host) on the same records, against the 31-PMT layout
 of tests/pmt_common.py, in photon records per second.
 
@@ -388,6 +394,73 @@ def photon_hits_rate(args):
     print(json.dumps(line))
 
 
+def union_rate(args):
+    n_a, n_b = args.union
+    n = n_a + n_b
+    rng = np.random.default_rng(1)
+    s, d = np.meshgrid(np.arange(1, 87), np.arange(1, 61), indexing="ij")
+    s, d = s.reshape(-1).astype(np.int32), d.reshape(-1).astype(np.uint32)
+    gen = M.make_generator([M.acceptance_table()], s, d, np.zeros(len(s), dtype=np.int32))
+    m = np.zeros(n, dtype=CV.MCPE_DTYPE)
+    dom = rng.integers(0, len(s), n)
+    m["stringID"], m["omID"], m["id"], m["time"] = s[dom], d[dom], rng.integers(0, 1000, n), rng.uniform(0.0, 1.0e4, n)
+    p = np.zeros(1000, dtype=CV.MCPE_PARTICLE_DTYPE)
+    p["id"], p["frame"], p["timeShift"] = np.arange(1000), np.arange(1000) % 10, rng.uniform(0.0, 1.0e6, 1000)
+    if args.one_dom:
+        m["stringID"], m["omID"], p["frame"] = 40, 30, 4
+    a, b, whole = (gen.MakeSeriesHost(part, p)[:2] for part in (m[:n_a], m[n_a:], m))
+    best = float("inf")
+    for _ in range(args.repeats):
+        t0 = time.perf_counter()
+        records, series = CV.MCPEGenerator.UnionHost(*a, *b)
+        best = min(best, time.perf_counter() - t0)
+    assert records.tobytes() == whole[0].tobytes() and series.tobytes() == whole[1].tobytes()
+    line = {"input": "one_dom" if args.one_dom else "synthetic", "store_records": n_a, "bunch_records": n_b, "series": len(series), "host_seconds": best,
+            "host_records_per_s": n / best, "threads": 1}
+    if args.device:
+        import torch
+        dev = torch.device("cuda", 0)
+        up = lambda x: torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).copy()).to(dev) if len(x) else torch.zeros(16, dtype=torch.uint8, device=dev)
+        d_a, d_b = (up(a[0]), up(a[1]), torch.tensor([n_a, len(a[1]), 0, 0, 0], dtype=torch.int32, device=dev)), \
+                   (up(b[0]), up(b[1]), torch.tensor([n_b, len(b[1]), 0, 0, 0], dtype=torch.int32, device=dev))
+        d_out, d_table = torch.zeros((max(n, 1), 16), dtype=torch.uint8, device=dev), torch.zeros((max(n, 1), 16), dtype=torch.uint8, device=dev)
+        d_counts = torch.zeros(5, dtype=torch.int32, device=dev)
+        # (the tables are as long as they are: the capacity of a table is that of its records, so the buffers are padded)
+        pad = lambda t, entries: torch.cat([t, torch.zeros(max(entries, 1) * 16 - len(t), dtype=torch.uint8, device=dev)])
+        d_a, d_b = (d_a[0], pad(d_a[1], n_a), d_a[2]), (d_b[0], pad(d_b[1], n_b), d_b[2])
+        ws = CV.MCPEGenerator.UnionWorkspaceBytes(n_a, n_b)
+        d_ws = torch.zeros(ws, dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream().cuda_stream
+        times = []
+        for _ in range(args.repeats + 1):
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            CV.MCPEGenerator.UnionDevice(d_a[0].data_ptr(), d_a[1].data_ptr(), d_a[2].data_ptr(), n_a, d_b[0].data_ptr(), d_b[1].data_ptr(), d_b[2].data_ptr(), n_b,
+                                         d_out.data_ptr(), d_table.data_ptr(), d_counts.data_ptr(), n, d_ws.data_ptr(), ws, stream=stream)
+            stop.record()
+            torch.cuda.synchronize()
+            times.append(start.elapsed_time(stop) * 1e-3)
+        assert [int(c) for c in d_counts.cpu()] == [n, len(series), 0, 0, 0]
+        assert d_out.cpu().numpy().reshape(-1)[:n * 16].tobytes() == records.tobytes() and d_table.cpu().numpy().reshape(-1)[:len(series) * 16].tobytes() == series.tobytes()
+        line.update(device_seconds=min(times[1:]), device_records_per_s=n / min(times[1:]))
+        # the yardstick: the series stage on the N + M MCPEs
+        d_in = torch.from_numpy(m.view(np.uint8).reshape(-1, 16).copy()).to(dev)
+        d_cnt = torch.tensor([n], dtype=torch.int32, device=dev)
+        ws = CV.MCPEGenerator.SeriesWorkspaceBytes(n, len(p), 0)
+        d_ws = torch.zeros(ws, dtype=torch.uint8, device=dev)
+        times = []
+        for _ in range(args.repeats + 1):
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            gen.MakeSeriesDevice(d_in.data_ptr(), d_cnt.data_ptr(), n, d_out.data_ptr(), d_table.data_ptr(), d_counts.data_ptr(), d_ws.data_ptr(), ws, p, None, stream=stream)
+            stop.record()
+            torch.cuda.synchronize()
+            times.append(start.elapsed_time(stop) * 1e-3)
+        assert int(d_counts[0]) == n and d_out.cpu().numpy().reshape(-1)[:n * 16].tobytes() == records.tobytes()
+        line.update(resort_device_seconds=min(times[1:]), union_over_resort=line["device_seconds"] / min(times[1:]))
+    print(json.dumps(line))
+
+
 def merge_rate(args):
     from tests import mcpe_merge_common as MM
     from tests import mcpe_series_common as S
@@ -439,6 +512,8 @@ def main():
     ap.add_argument("--device", action="store_true")
     ap.add_argument("--pmt", action="store_true")
     ap.add_argument("--merge", action="store_true")
+    ap.add_argument("--union", type=int, nargs=2, default=None, metavar=("N", "M"))
+    ap.add_argument("--one-dom", action="store_true")
     ap.add_argument("--pmt-series", type=int, default=0, metavar="N")
     ap.add_argument("--frame-photons", type=int, default=0, metavar="N")
     ap.add_argument("--cable-shadow", type=int, default=0, metavar="N")
@@ -447,6 +522,8 @@ def main():
     ap.add_argument("--photon-hits", type=int, default=0, metavar="N")
     ap.add_argument("--pmt-photon-hits", type=int, default=0, metavar="N")
     args = ap.parse_args()
+    if args.union:
+        return union_rate(args)
     if args.pmt_photon_hits:
         return pmt_photon_hits_rate(args)
     if args.photon_hits:

@@ -6,8 +6,10 @@ the stage's kernels beside the propagation kernel.  Prints the counts and the ho
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/mcpe_series_profile.py [--steps 1048576] [--no-series] [--merge-window NS]
                                                                                    [--pmt] [--frame-photons] [--cable-shadow]
                                                                                    [--event-statistics] [--photon-hits]
-                                                                                   [--pmt-photon-hits]
+                                                                                   [--pmt-photon-hits] [--frame-store]
 
+--frame-store: a device MCPE frame store of 2^20 records folded behind each bunch (clsimhip_mcpe_frame_store_add_host: the upload
+and the union kernels), drained at the end; the line then carries the store's sizes.
 --merge-window NS: the MCPE merging stage behind the series stage, with that window.
 --pmt: a 31-PMT module (tests/pmt_common.py) at every DOM instead: the multi-PMT hit maker and the PMT series stage (--no-series:
 the hit maker alone).
@@ -156,6 +158,7 @@ def main():
     ap.add_argument("--event-statistics", action="store_true")
     ap.add_argument("--photon-hits", action="store_true")
     ap.add_argument("--pmt-photon-hits", action="store_true")
+    ap.add_argument("--frame-store", action="store_true")
     args = ap.parse_args()
     cfg = common.config("mie")
     g = cfg["geom"]
@@ -173,6 +176,7 @@ def main():
     steps["id"] = np.arange(len(steps)) % 1000
     p = np.zeros(1000, dtype=CV.MCPE_PARTICLE_DTYPE)
     p["id"], p["frame"], p["timeShift"] = np.arange(1000), np.arange(1000) % 10, np.arange(1000) * 1000.0
+    store = CV.MCPEFrameStore(1 << 20, device=0) if args.frame_store and not args.no_series else None
     for bunch in range(2):          # the first bunch allocates the pools
         t0 = time.perf_counter()
         if args.no_series:
@@ -180,7 +184,13 @@ def main():
         else:
             conv.EnqueueSteps(steps, bunch, particles=p)
         r = conv.GetConversionResult()
+        if store is not None:
+            store.Add(r.mcpes, r.series)
         wall = time.perf_counter() - t0
+    if store is not None:
+        stored = store.Size()
+        head = store.Drain(4)
+        print(json.dumps({"frame_store_records": stored[0], "frame_store_series": stored[1], "drained_up_to_frame_4": len(head[0]), "left": store.Size()[0]}))
     print(json.dumps({"steps": len(steps), "photons": int(steps["num"].sum()), "mcpes": len(r.mcpes),
                       "series": None if r.series is None else len(r.series),
                       "merged": None if r.merged is None else len(r.merged), "parents": None if r.parents is None else len(r.parents),
