@@ -4,13 +4,12 @@ scaling, device vs host vs a Python port of PPC, 1e5 random directions, relative
 tilt, +-1200 m cube, <= 10 cm; testVectorTransforms.py -- matrix transforms vs numpy).  The same tests here, with
 clsimhip_eval_device_function / _random as the tester: the device against the oracle's function of the same name (bit for bit, both
 forms the kernels use) AND against the independent formulas the reference's tests hold (within their tolerances)."""
-import math
-
 import numpy as np
 import pytest
 
 from oracle import capi
 from tests import common
+from tests.propagation_reference import ppc_anisotropy, tilt_independent          # the independent formulas live there
 
 pytestmark = pytest.mark.gpu
 
@@ -69,25 +68,6 @@ def test_group_velocity_from_the_dispersion_device_equals_oracle():
     assert conv.KernelForBunch(1 << 20) in ("pool", "classic") and conv.GetTable("fast_variant")[0] == 0.0
 
 
-def tilt_independent(medium, pos):
-    """the tilt in double precision numpy, stated from ScalarFieldIceTiltZShift.cxx:145-213: bilinear between the dust-logger
-    profiles along the tilt direction and in z, the outermost cells extended linearly beyond the table"""
-    tl = medium["tilt"]
-    d = np.asarray(tl["distances"], dtype=np.float64)
-    zc = np.asarray(tl["zcoords"], dtype=np.float64)
-    corr = np.asarray(tl["zcorr"], dtype=np.float64).reshape(len(d), len(zc))
-    p = pos.astype(np.float64)
-    zr = (p[:, 2] - zc[0]) / ((zc[-1] - zc[0]) / (len(zc) - 1))
-    k = np.clip(np.floor(zr).astype(int), 0, len(zc) - 2)
-    fz = zr - k
-    nr = math.cos(tl["azimuth"]) * p[:, 0] + math.sin(tl["azimuth"]) * p[:, 1]
-    j = np.clip(np.searchsorted(d, nr, side="right"), 1, len(d) - 1)
-    lower = corr[j - 1, k + 1] * fz + corr[j - 1, k] * (1 - fz)
-    upper = corr[j, k + 1] * fz + corr[j, k] * (1 - fz)
-    f_lower = (d[j] - nr) / (d[j] - d[j - 1])
-    return upper * (1 - f_lower) + lower * f_lower
-
-
 @pytest.mark.parametrize("name", ["mie", "lea"])
 def test_tilt_device_equals_oracle_and_an_independent_interpolation(setups, name):
     """testScalarFieldIceTiltZShift.py: positions in a +-1200 m cube, device vs host, tolerance 10 cm"""
@@ -110,22 +90,6 @@ def test_constant_tilt(setups):
     assert np.all(conv.EvaluateOnDevice("abs_len_scaling", unit_vectors(100, 2))[:, 0] == 1.0)
     d = unit_vectors(100, 3)
     assert np.array_equal(conv.EvaluateOnDevice("pre_scatter_transform", d)[:, :3], d)
-
-
-def ppc_anisotropy(dirs, azimuth, k1, k2):
-    """the formula resources/tests/testScalarFields.py:52-91 tests the device against (its Python port of PPC), vectorised"""
-    azx, azy = math.cos(azimuth), math.sin(azimuth)
-    k1e, k2e = math.exp(k1), math.exp(k2)
-    kz = 1.0 / (k1e * k2e)
-    n = dirs.astype(np.float64)
-    s1 = (azx * n[:, 0] + azy * n[:, 1]) ** 2
-    s2 = (-azy * n[:, 0] + azx * n[:, 1]) ** 2
-    s3 = n[:, 2] ** 2
-    l1, l2, l3 = k1e * k1e, k2e * k2e, kz * kz
-    B2 = 1.0 / l1 + 1.0 / l2 + 1.0 / l3
-    nB = s1 / l1 + s2 / l2 + s3 / l3
-    An = s1 * l1 + s2 * l2 + s3 * l3
-    return 1.0 / ((B2 - nB) * An / 2.0)
 
 
 def test_anisotropy_device_equals_oracle_and_the_ppc_port(setups):

@@ -12,6 +12,7 @@ from clsim_amd import synthetic as S
 from oracle import builders as B
 from oracle import capi
 from tests import common
+from tests import propagation_reference as PR
 
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -78,21 +79,17 @@ def test_powr_accuracy_on_the_ice_model_ranges(oracle_lib):
 
 def test_ice_functions_against_host_formulas(oracle_lib):
     """Device-side restatement vs the reference's host GetValue() formulas
-    (AbsLenIceCube.cxx:63-67, ScatLenIceCube.cxx:54-58, RefIndexIceCube.cxx:84-101) in double."""
+    (AbsLenIceCube.cxx:63-67, ScatLenIceCube.cxx:54-58, RefIndexIceCube.cxx:84-101) in double: tests/propagation_reference.py
+    holds them."""
     cfg = common.config("mie")
     T = common.oracle_tables(cfg)
     m = cfg["med_o"]
     wl = np.linspace(265e-9, 675e-9, 83).astype(np.float32)
     for layer in (0, 17, 85, 170):
-        x = wl.astype(np.float64) / 1e-9
-        absl = 1.0 / ((m["D"] * m["aDust400"][layer] + m["E"]) * x ** (-m["kappa"]) + m["A"] * np.exp(-m["B"] / x) * (1.0 + 0.01 * m["deltaTau"][layer]))
-        scal = 1.0 / (m["b400"][layer] * (x / 400.0) ** (-m["alpha"]))
+        absl, scal = PR.icecube_absorption_length(m, layer, wl), PR.icecube_scattering_length(m, layer, wl)
         assert np.allclose(capi.eval_medium(T, 0, wl, layer), absl, rtol=2e-6)
         assert np.allclose(capi.eval_medium(T, 1, wl, layer), scal, rtol=2e-6)
-    xm = wl.astype(np.float64) / 1e-6
-    n, g = m["n"], m["g"]
-    nphase = n[0] + xm * (n[1] + xm * (n[2] + xm * (n[3] + xm * n[4])))
-    ngroup = nphase * (g[0] + xm * (g[1] + xm * (g[2] + xm * (g[3] + xm * g[4]))))
+    nphase, ngroup = PR.icecube_phase_index(m["n"], wl), PR.icecube_group_index(m["n"], m["g"], wl)
     assert np.allclose(capi.eval_medium(T, 2, wl), nphase, rtol=1e-6)
     assert np.allclose(capi.eval_medium(T, 3, wl), 0.299792458 / ngroup, rtol=1e-6)
 
