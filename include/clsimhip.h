@@ -1279,6 +1279,62 @@ int clsimhip_set_frame_photons(clsimhip_converter *c, int on, int keep_photons);
 int clsimhip_get_result_frame_photons(clsimhip_converter *c, const clsimhip_photon *photons, const clsimhip_frame_photon **records, size_t *n,
                                       const clsimhip_mcpe_series **series, size_t *n_series, uint64_t *n_masked);
 
+/* ---- Frame photon store: the frame photons of several bunches accumulate per frame; finished frames leave --------------------
+ * Frame photons, continued: what the MCPE frame store is for MCPEs, for clsimhip_frame_photon records with their clsimhip_mcpe_series
+ * table -- the reference files every result's photons into (*frame->photons)[ModuleKey] of a frame cache that lives across bunches
+ * (private/clsim/I3CLSimClientModule.cxx:359-439, :407-415) and FlushFrameCache() commits the oldest frames (:686-758).
+ * SERIES FORM OF FRAME PHOTONS: the table rules are the MCPE frame store's; every record carries its entry's string_id and
+ *     om_id; inside a series the 12-word suffix (tkey(time) high, low, identifier, h, w0 ... w7) does not descend, h and w as the
+ *     frame photons stage defines them.  Each element (entry or record) that breaks a rule is one MALFORMED element.
+ * KEY of a record: 14 words -- frame of its entry, module (string_id signed, om_id), tkey high, tkey low, identifier, h, w0 ... w7 --
+ *     compared word by word as unsigned integers.  Equal keys are equal bytes.  The time travels as its bit pattern (tkey is an
+ *     inversion on the bits), so a signalling NaN keeps its payload.
+ * UNION(A, B): the multiset union ascending in the key, ties A first, the table rebuilt from the heads.  The comparison is the full
+ *     key, so there is NO TIE BOUND: a run equal in (frame, module, tkey, identifier, h) of any length and any contents is ordered,
+ *     also where the frame photons stage on the whole bunch would report TIE_OVERFLOW.  For any split of a bunch's photons into two
+ *     parts with one particle table and mask, the union of their frame photons is the frame photons of the whole, byte for byte,
+ *     wherever the whole has TIE_OVERFLOW = 0.
+ * SPLIT(X, last_frame): the head is the entries with frame <= last_frame and their records; the tail is the rest, rebased.
+ * Failure rules, the five output counts (records, series, MALFORMED elements in A, in B, overflow), capacities, alignment and
+ * asynchrony are the MCPE frame store's, call for call: B malformed or an output that does not fit -> the output is A unchanged; A
+ * malformed -> the output is empty; a head that does not fit drains nothing.  The counts keep (records, series) first, so a union's
+ * output or a drain chains unchanged into clsimhip_photon_hits_device, clsimhip_pmt_photon_hits_device and another union. */
+int clsimhip_frame_photons_union_host(const clsimhip_frame_photon *a_records, size_t n_a, const clsimhip_mcpe_series *a_series, size_t n_series_a,
+                                      const clsimhip_frame_photon *b_records, size_t n_b, const clsimhip_mcpe_series *b_series, size_t n_series_b,
+                                      clsimhip_frame_photon *out_records, clsimhip_mcpe_series *out_series, size_t out_capacity, size_t *n, size_t *n_series);
+int clsimhip_frame_photons_split_host(const clsimhip_frame_photon *records, size_t n, const clsimhip_mcpe_series *series, size_t n_series, uint32_t last_frame,
+                                      clsimhip_frame_photon *head_records, clsimhip_mcpe_series *head_series, size_t head_capacity, size_t *n_head,
+                                      size_t *n_series_head, clsimhip_frame_photon *tail_records, clsimhip_mcpe_series *tail_series, size_t tail_capacity,
+                                      size_t *n_tail, size_t *n_series_tail);
+size_t clsimhip_frame_photons_union_workspace_bytes(size_t capacity_a, size_t capacity_b);
+int clsimhip_frame_photons_union_device(int device, const void *d_a_records, const void *d_a_series, const void *d_a_counts, size_t capacity_a,
+                                        const void *d_b_records, const void *d_b_series, const void *d_b_counts, size_t capacity_b,
+                                        void *d_out_records, void *d_out_series, void *d_out_counts, size_t out_capacity, void *d_workspace,
+                                        size_t workspace_bytes, void *hip_stream);
+int clsimhip_frame_photons_split_device(int device, const void *d_records, const void *d_series, const void *d_counts, size_t capacity,
+                                        uint32_t last_frame, void *d_head_records, void *d_head_series, void *d_head_counts, size_t head_capacity,
+                                        void *d_tail_records, void *d_tail_series, void *d_tail_counts, size_t tail_capacity, void *hip_stream);
+/* The store, as clsimhip_mcpe_frame_store: device < 0 is a host store on the twins; a device store owns two record and two table
+ * buffers used in turn, a workspace, five sticky counters in page-locked memory and one event that every operation waits for and
+ * records again.  add_device pairs with clsimhip_frame_photons_device (its d_out, d_series, d_counts).  A bunch dropped on the
+ * device makes every later drain and _size return CLSIMHIP_ERR_DEVICE with the counts in the text -- once the host can see it:
+ * _size and drain_host wait for the store's event first and always see it; drain_device does not wait, so while the add_device that
+ * drops the bunch is still in flight it returns CLSIMHIP_OK, its kernel looks at the counters again on the device and delivers an
+ * EMPTY head (records = series = 0 in d_counts, the store unchanged), and the error is raised by the next call that waits. */
+typedef struct clsimhip_frame_photon_store clsimhip_frame_photon_store;
+int clsimhip_frame_photon_store_create(int device, size_t capacity, clsimhip_frame_photon_store **out);
+void clsimhip_frame_photon_store_destroy(clsimhip_frame_photon_store *s);
+const char *clsimhip_frame_photon_store_last_error(const clsimhip_frame_photon_store *s);
+int clsimhip_frame_photon_store_add_host(clsimhip_frame_photon_store *s, const clsimhip_frame_photon *records, size_t n, const clsimhip_mcpe_series *series,
+                                         size_t n_series);
+int clsimhip_frame_photon_store_add_device(clsimhip_frame_photon_store *s, const void *d_records, const void *d_series, const void *d_series_counts,
+                                           size_t capacity, void *hip_stream);
+int clsimhip_frame_photon_store_drain_device(clsimhip_frame_photon_store *s, uint32_t last_frame, void *d_records, void *d_series, void *d_counts,
+                                             size_t capacity, void *hip_stream);
+int clsimhip_frame_photon_store_drain_host(clsimhip_frame_photon_store *s, uint32_t last_frame, clsimhip_frame_photon *records, clsimhip_mcpe_series *series,
+                                           size_t capacity, size_t *n, size_t *n_series);
+int clsimhip_frame_photon_store_size(clsimhip_frame_photon_store *s, uint32_t last_frame, size_t *n, size_t *n_series);
+
 /* ---- Cable shadow: drop detected photons whose last path crosses a cable ------------------------------------------------------
  * The reference's I3ShadowedPhotonRemoverModule (private/clsim/shadow/): PropagatedPhotons -> PropagatedPhotonsWithShadow, which its
  * photon-to-MCPE converter then reads.  I3ShadowedPhotonRemover::IsPhotonShadowed (I3ShadowedPhotonRemover.cxx:63-81) walks the

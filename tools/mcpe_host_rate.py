@@ -18,6 +18,12 @@ series of N synthetic MCPEs meets a bunch of the series of M more, at IceCube's 
 the same input (HIP events around clsimhip_mcpe_series_union_device, best of --repeats; needs a GPU) and, as the yardstick, the
 series stage re-sorting the N + M MCPEs (clsimhip_mcpe_series_device) in the same run.
 
+--frame-photon-union N M: the frame photon store's union instead (clsimhip_frame_photons_union_host, one thread), in records per
+second: a store of the frame photons of N synthetic photon records meets a bunch of the frame photons of M more, at 5160 DOMs dealt
+to 1000 particles in 10 frames; --one-dom puts every record on one module of one frame.  --device adds the union kernels' time for the
+same input (HIP events around clsimhip_frame_photons_union_device, best of --repeats; needs a GPU) and, as the yardstick, the frame
+photons stage re-sorting the N + M source photons (clsimhip_frame_photons_device) in the same run.
+
 --pmt: the multi-PMT hit generator's host twin instead (clsimhip_pmt_convert_host) on the same records, against the 31-PMT layout
 of tests/pmt_common.py, in photon records per second.
 
@@ -461,6 +467,80 @@ def union_rate(args):
     print(json.dumps(line))
 
 
+def frame_photon_union_rate(args):
+    n_a, n_b = args.frame_photon_union
+    n = n_a + n_b
+    rng = np.random.default_rng(1)
+    s, d = np.meshgrid(np.arange(1, 87), np.arange(1, 61), indexing="ij")
+    s, d = s.reshape(-1).astype(np.int32), d.reshape(-1).astype(np.uint32)
+    doms = CV.FramePhotonDoms(s, d)
+    m = np.zeros(n, dtype=CV.PHOTON_DTYPE)
+    at = rng.integers(0, len(s), n)
+    m["stringID"], m["omID"], m["id"], m["t"] = s[at], d[at], rng.integers(0, 1000, n), rng.uniform(0.0, 1.0e4, n)
+    for name in ("x", "y", "z", "theta", "phi", "wavelength", "weight", "groupVelocity"):
+        m[name] = rng.uniform(0.1, 1.0, n)
+    p = np.zeros(1000, dtype=CV.MCPE_PARTICLE_DTYPE)
+    p["id"], p["frame"], p["timeShift"] = np.arange(1000), np.arange(1000) % 10, rng.uniform(0.0, 1.0e6, 1000)
+    if args.one_dom:
+        m["stringID"], m["omID"], p["frame"] = 40, 30, 4
+    a, b, whole = (doms.MakeFramePhotonsHost(part, p)[:2] for part in (m[:n_a], m[n_a:], m))
+    best = float("inf")
+    for _ in range(args.repeats):
+        t0 = time.perf_counter()
+        records, series = CV.FramePhotonStore.UnionHost(*a, *b)
+        best = min(best, time.perf_counter() - t0)
+    assert records.tobytes() == whole[0].tobytes() and series.tobytes() == whole[1].tobytes()
+    line = {"input": "one_dom" if args.one_dom else "synthetic", "store_records": n_a, "bunch_records": n_b, "series": len(series), "host_seconds": best,
+            "host_records_per_s": n / best, "threads": 1}
+    if args.device:
+        import torch
+        dev = torch.device("cuda", 0)
+
+        def up(form, capacity):          # (the capacity of a table is that of its records: both buffers are padded to it)
+            out = []
+            for x, size in zip(form, (48, 16)):
+                t = torch.zeros(max(capacity, 1) * size, dtype=torch.uint8, device=dev)
+                if len(x):
+                    t[:len(x) * size] = torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).copy()).to(dev)
+                out.append(t)
+            return out + [torch.tensor([len(form[0]), len(form[1]), 0, 0, 0], dtype=torch.int32, device=dev)]
+        d_a, d_b = up(a, n_a), up(b, n_b)
+        d_out, d_table = torch.zeros((max(n, 1), 48), dtype=torch.uint8, device=dev), torch.zeros((max(n, 1), 16), dtype=torch.uint8, device=dev)
+        d_counts = torch.zeros(6, dtype=torch.int32, device=dev)
+        ws = CV.FramePhotonStore.UnionWorkspaceBytes(n_a, n_b)
+        d_ws = torch.zeros(ws, dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream().cuda_stream
+        times = []
+        for _ in range(args.repeats + 1):
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            CV.FramePhotonStore.UnionDevice(d_a[0].data_ptr(), d_a[1].data_ptr(), d_a[2].data_ptr(), n_a, d_b[0].data_ptr(), d_b[1].data_ptr(), d_b[2].data_ptr(), n_b,
+                                            d_out.data_ptr(), d_table.data_ptr(), d_counts.data_ptr(), n, d_ws.data_ptr(), ws, stream=stream)
+            stop.record()
+            torch.cuda.synchronize()
+            times.append(start.elapsed_time(stop) * 1e-3)
+        assert [int(c) for c in d_counts.cpu()[:5]] == [n, len(series), 0, 0, 0]
+        assert d_out.cpu().numpy().reshape(-1)[:n * 48].tobytes() == records.tobytes() and d_table.cpu().numpy().reshape(-1)[:len(series) * 16].tobytes() == series.tobytes()
+        line.update(device_seconds=min(times[1:]), device_records_per_s=n / min(times[1:]))
+        # the yardstick: the frame photons stage re-sorting the N + M source photons
+        d_in = torch.from_numpy(m.view(np.uint8).reshape(-1, 80).copy()).to(dev)
+        d_cnt = torch.tensor([n], dtype=torch.int32, device=dev)
+        ws = CV.FramePhotonDoms.WorkspaceBytes(n, len(p), 0)
+        d_ws = torch.zeros(ws, dtype=torch.uint8, device=dev)
+        times = []
+        for _ in range(args.repeats + 1):
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            doms.MakeFramePhotonsDevice(d_in.data_ptr(), d_cnt.data_ptr(), n, d_out.data_ptr(), d_table.data_ptr(), d_counts.data_ptr(), d_ws.data_ptr(), ws, p, None,
+                                        stream=stream)
+            stop.record()
+            torch.cuda.synchronize()
+            times.append(start.elapsed_time(stop) * 1e-3)
+        assert int(d_counts[0]) == n and d_out.cpu().numpy().reshape(-1)[:n * 48].tobytes() == records.tobytes()
+        line.update(resort_device_seconds=min(times[1:]), union_over_resort=line["device_seconds"] / min(times[1:]))
+    print(json.dumps(line))
+
+
 def merge_rate(args):
     from tests import mcpe_merge_common as MM
     from tests import mcpe_series_common as S
@@ -513,6 +593,7 @@ def main():
     ap.add_argument("--pmt", action="store_true")
     ap.add_argument("--merge", action="store_true")
     ap.add_argument("--union", type=int, nargs=2, default=None, metavar=("N", "M"))
+    ap.add_argument("--frame-photon-union", type=int, nargs=2, default=None, metavar=("N", "M"))
     ap.add_argument("--one-dom", action="store_true")
     ap.add_argument("--pmt-series", type=int, default=0, metavar="N")
     ap.add_argument("--frame-photons", type=int, default=0, metavar="N")
@@ -524,6 +605,8 @@ def main():
     args = ap.parse_args()
     if args.union:
         return union_rate(args)
+    if args.frame_photon_union:
+        return frame_photon_union_rate(args)
     if args.pmt_photon_hits:
         return pmt_photon_hits_rate(args)
     if args.photon_hits:

@@ -7,9 +7,13 @@ the stage's kernels beside the propagation kernel.  Prints the counts and the ho
                                                                                    [--pmt] [--frame-photons] [--cable-shadow]
                                                                                    [--event-statistics] [--photon-hits]
                                                                                    [--pmt-photon-hits] [--frame-store]
+                                                                                   [--frame-photon-store]
 
 --frame-store: a device MCPE frame store of 2^20 records folded behind each bunch (clsimhip_mcpe_frame_store_add_host: the upload
 and the union kernels), drained at the end; the line then carries the store's sizes.
+--frame-photon-store: with --frame-photons: a device frame photon store of 2^20 records folded behind each bunch
+(clsimhip_frame_photon_store_add_host: the upload and the union kernels), drained up to frame 4 at the end; a second line carries the
+store's sizes.
 --merge-window NS: the MCPE merging stage behind the series stage, with that window.
 --pmt: a 31-PMT module (tests/pmt_common.py) at every DOM instead: the multi-PMT hit maker and the PMT series stage (--no-series:
 the hit maker alone).
@@ -128,6 +132,7 @@ def frame_photons_bunch(args, cfg, bias):
     steps["id"] = np.arange(len(steps)) % 1000
     p = np.zeros(1000, dtype=CV.MCPE_PARTICLE_DTYPE)
     p["id"], p["frame"], p["timeShift"] = np.arange(1000), np.arange(1000) % 10, np.arange(1000) * 1000.0
+    store = CV.FramePhotonStore(1 << 20, device=0) if args.frame_photon_store and not args.no_series else None
     for bunch in range(2):          # the first bunch allocates the pools
         t0 = time.perf_counter()
         if args.no_series:
@@ -135,7 +140,13 @@ def frame_photons_bunch(args, cfg, bias):
         else:
             conv.EnqueueSteps(steps, bunch, particles=p)
         r = conv.GetConversionResult()
+        if store is not None:
+            store.Add(r.frame_photons, r.frame_photon_series)
         wall = time.perf_counter() - t0
+    if store is not None:
+        stored = store.Size()
+        head = store.Drain(4)
+        print(json.dumps({"frame_photon_store_records": stored[0], "frame_photon_store_series": stored[1], "drained_up_to_frame_4": len(head[0]), "left": store.Size()[0]}))
     hits = photon_hits_of(cfg, r) if args.photon_hits and r.frame_photons is not None else None
     pmt_hits = pmt_photon_hits_of(cfg, r) if args.pmt_photon_hits and r.frame_photons is not None else None
     print(json.dumps({"steps": len(steps), "photons": int(steps["num"].sum()), "photon_records": len(r[1]), "photon_hits": hits, "pmt_photon_hits": pmt_hits,
@@ -159,7 +170,10 @@ def main():
     ap.add_argument("--photon-hits", action="store_true")
     ap.add_argument("--pmt-photon-hits", action="store_true")
     ap.add_argument("--frame-store", action="store_true")
+    ap.add_argument("--frame-photon-store", action="store_true")
     args = ap.parse_args()
+    if args.frame_photon_store and (not args.frame_photons or args.no_series or args.pmt):
+        ap.error("--frame-photon-store needs --frame-photons with the stage on (no --no-series, no --pmt): there would be nothing to store")
     cfg = common.config("mie")
     g = cfg["geom"]
     s, d = np.asarray(g["string_ids"]), np.asarray(g["dom_ids"])
