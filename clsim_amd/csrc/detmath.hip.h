@@ -126,6 +126,22 @@ DM float rsqrt_unit_(float x)
     const uint32_t below = 0x3f800000u + ((uint32_t)(3 - d) >> 2);     // d < 0: ceil(ceil(j / 2) / 2) = (j + 3) >> 2, j = -d
     return u2f((d < 0) ? below : above);
 }
+// clamp_index_of<HI>(f) = clampi((int)f, 0, HI) for a table dimension HI >= 0 that is a constant (round 10, the run-time compiled kernel): a
+// table index from a float in TWO instructions.  v_cvt_i32_f32 + v_med3_i32 is three, because VOP3 takes no 32-bit literal and the bound
+// (0x1ff, 0xa8, 0xaa ...) needs a v_mov_b32 of its own; VOP2 does take one.  The unsigned conversion truncates as the signed one does,
+// sends everything below 1 -- negative values, -inf, NaN -- to 0 and saturates above (2^32 - 1 where the signed one stops at 2^31 - 1: both
+// beyond any HI), so the minimum with HI is the clamped index.  The conversions are the hardware's, so this is not argued, it is TESTED:
+// all 2^32 bit patterns x six bounds on the device, against the spelled-out form (clsimhip_check_math_exhaustive(20),
+// tests/test_index_clamp_gpu.py).
+template <int HI>
+DM int clamp_index_of(float f)
+{
+    if (HI < 0) { const int v = (int)f, lo = (v > 0) ? v : 0; return (lo < HI) ? lo : HI; }       // (an absent table: the spelled-out form)
+    uint32_t r;
+    asm("v_cvt_u32_f32_e32 %0, %1\n\t"
+        "v_min_u32_e32 %0, %2, %0" : "=v"(r) : "v"(f), "n"((uint32_t)HI));
+    return (int)r;
+}
 
 // the tables: words [0, 128) of an LDS image = 32 log rows {INV, H, L, 0}; words [128, 194) = 33 sincos rows {S, C}; padded to 196
 constexpr uint32_t kMathLogWords = 4u * MT_LOG_ROWS, kMathScWords = 2u * MT_SC_ROWS, kMathTableWords = (kMathLogWords + kMathScWords + 3u) & ~3u;

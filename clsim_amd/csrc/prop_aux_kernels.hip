@@ -239,6 +239,7 @@ hipError_t launch_assemble_hits(const KParams &P, bool flasher, hipStream_t stre
 
 hipError_t launch_check_math(int what, int exp_lo, int exp_hi, uint32_t *result, uint32_t result_cap, hipStream_t stream)
 {
+    if (what == 20) return launch_check_index_clamp(result, result_cap, stream);        // (index_clamp_check_kernel.hip)
     hipLaunchKernelGGL(check_math_kernel, dim3((1u << 23) / 256), dim3(256), 0, stream, what, exp_lo, exp_hi, result, result_cap);
     return hipGetLastError();
 }

@@ -89,6 +89,20 @@ DM Rec4 lds_rec4_wide(uint32_t i)
     const f32x4 v = *reinterpret_cast<lds_vec_ptr>(static_cast<uintptr_t>(4u * i));
     return Rec4{v.x, v.y, v.z, v.w};
 }
+// (round 10) the same for a record named by its BYTE address, byte % 16 == 0 visible to the caller; and the three-word read of lds_rec4
+// by byte address, for records that are not aligned (byte % 4 == 0)
+DM Rec4 lds_rec4_wide_at_byte(uint32_t byte)
+{
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    typedef const f32x4 __attribute__((address_space(3))) *lds_vec_ptr;
+    const f32x4 v = *reinterpret_cast<lds_vec_ptr>(static_cast<uintptr_t>(byte));
+    return Rec4{v.x, v.y, v.z, v.w};
+}
+DM Rec4 lds_rec4_at_byte(uint32_t byte)
+{
+    typedef const Rec4 __attribute__((address_space(3))) *lds_rec_ptr;
+    return *reinterpret_cast<lds_rec_ptr>(static_cast<uintptr_t>(byte));
+}
 // a float at a BYTE address of the image
 DM float ldsf_at_byte(uint32_t byte)
 {
@@ -421,7 +435,8 @@ DM float tilt_z_shift(KP P, float px, float py, float pz)
     // (run-time compiled kernel, round 9: the same index without v_floor_f32.  For z_rescaled >= 0 the truncating conversion IS the
     // floor; for z_rescaled < 0 the floor is <= -1 and the truncation <= 0, NaN converts to 0 and values beyond the int range to its
     // ends either way: the clamp sends both forms to the same end.)
-    const int k = clamp_index((int)z_rescaled, nz - 2);
+    // (round 10: the same index in two instructions, dm::clamp_index_of)
+    const int k = dm::clamp_index_of<KParams::tilt_nz - 2>(z_rescaled);
 #else
     const int k = clamp_index((int)__builtin_floorf(z_rescaled), nz - 2);           // nz >= 2 (tables.cpp)
 #endif
@@ -705,7 +720,12 @@ DM float propagate_through_layers(KP P, Photon &ph, uint64_t &rx, uint32_t ra)
     int current_layer;
     if (TILT) {
         effective_z = ph.pz - tilt_z_shift<FAST>(P, ph.px, ph.py, ph.pz);
+#ifdef KPARAMS_BAKED
+        // (run-time compiled kernel, round 10: two instructions, dm::clamp_index_of)
+        current_layer = dm::clamp_index_of<KParams::num_layers - 1>(div_by_t<FAST>(effective_z - bottom, thickness, P->rcp_layer_thickness, (P->div_ok & 2u) != 0));
+#else
         current_layer = clamp_index((int)div_by_t<FAST>(effective_z - bottom, thickness, P->rcp_layer_thickness, (P->div_ok & 2u) != 0), num_layers - 1);
+#endif
     } else {
         effective_z = ph.pz - P->tilt_const;
         current_layer = ph.layer;
@@ -747,6 +767,58 @@ DM float propagate_through_layers(KP P, Photon &ph, uint64_t &rx, uint32_t ra)
     }
     float ais = (dz * sca_step_left - over_sca) * recip_thickness;
     float aia = (dz * ph.abs_lens_left - over_abs) * recip_thickness;
+#ifdef KPARAMS_BAKED
+    // (run-time compiled kernel, round 10) The same walk with what every wave pays per crossed layer cut to the reference's arithmetic.
+    //  * Signed sums.  S_s = sgn * ais and S_a = sgn * aia are carried instead of ais and aia: the two products the loop's first test
+    //    forms anyway.  A product with sgn = +-1 is exact and round-to-nearest is symmetric in sign, so
+    //    sgn * RN(ais - sgn * r) = RN(sgn * ais - r): S -= r keeps S == sgn * ais at every iteration, bit for bit -- with one exception
+    //    that changes nothing: an exact cancellation gives +0 in both forms, so S is +0 where sgn * ais would be -0 (sgn = -1).  Either
+    //    zero fails (S > 0) and ends the loop, and below it the product with the zero is a zero that is ADDED to `boundary`, which is
+    //    never -0 (a single precision sum that cancels is +0): the sum is `boundary` either way.  So the test (sgn * ais > 0) is
+    //    (S > 0), and the four multiplications by sgn per crossed layer are gone.  Below the loop (sgn * S) * t and S * (sgn * t) are
+    //    the same rounded product with the same sign, so the crossing branch takes S * signed_thickness where it took ais * thickness.
+    //    A NaN in ais or aia makes the comparison false in both forms: the loop is not entered or is left, and the branch below
+    //    multiplies a NaN either way.
+    //  * One induction variable: the walk's place is `at`, the record's byte offset from the first layer's record (the layer index for
+    //    tabulated lengths, whose records are in global memory), and the last layer is named in the same unit.  The layer index j,
+    //    its add, and the copies of current_layer into it are gone; (current_layer == j), "no layer was crossed", is the loop's own
+    //    entry condition, which the wave holds as a lane mask anyway: the walk only moves away from where it started.
+    //  * The crossed layer's record comes as one ds_read_b128 where the records are aligned (lds_rec4_wide_at_byte), as in the read above.
+    const bool down = (dz < 0.0f);
+    const float sgn = down ? -1.0f : 1.0f;
+    const float signed_thickness = sgn * thickness;
+    float S_s = sgn * ais, S_a = sgn * aia;
+    constexpr bool kRecordsInLds = (MED != CLSIMHIP_LENGTHS_TABLE);
+    constexpr uint32_t kAtUnit = kRecordsInLds ? 16u : 1u;
+    const uint32_t at_start = kAtUnit * (uint32_t)current_layer;
+    const uint32_t at_step = down ? (0u - kAtUnit) : kAtUnit;
+    const uint32_t at_last = down ? 0u : kAtUnit * (uint32_t)(num_layers - 1);
+    uint32_t at = at_start;
+    const bool crossing = (at != at_last) && (S_s > 0.0f) && (S_a > 0.0f);
+    if (crossing) do {
+        CENSUS_REGION(P, kCensusCrossing);
+        at += at_step;
+        boundary += signed_thickness;
+        if (kRecordsInLds) {
+            const Rec4 r = (KParams::off_layers % 4u == 0u) ? lds_rec4_wide_at_byte(4u * off_layers + at) : lds_rec4_at_byte(4u * off_layers + at);
+            layer_lengths_of<MED, FAST>(r, ph.ice, sca_len, abs_len, rcp_sca, rcp_abs, fast);
+        } else {
+            layer_lengths<MED, FAST>(off_layers, len_table, ph.ice, (int)at, sca_len, abs_len, rcp_sca, rcp_abs, fast);
+        }
+        S_s -= seeded ? rcp_sca : rcp_t<FAST>(sca_len, fast);
+        S_a -= seeded ? rcp_abs : rcp_t<FAST>(abs_len, fast);
+    } while ((at != at_last) && (S_s > 0.0f) && (S_a > 0.0f));
+    float distance, to_absorption;
+    if (!crossing || (__builtin_fabsf(dz) < kEpsilon)) {
+        distance = sca_step_left * sca_len;
+        to_absorption = ph.abs_lens_left * abs_len;
+    } else {
+        const float recip_dz = dm::rcp_(dz);            // 1e-5 <= |dz| <= 1 on this branch
+        distance = (S_s * signed_thickness * sca_len + boundary - effective_z) * recip_dz;
+        to_absorption = (S_a * signed_thickness * abs_len + boundary - effective_z) * recip_dz;
+    }
+    if (!TILT) ph.layer = (int)(at / kAtUnit);
+#else
     int j = current_layer;
     {
         // c.cl:643-668 has one loop for photons going down and one for photons going up; a wave holds both kinds, so the
@@ -776,6 +848,7 @@ DM float propagate_through_layers(KP P, Photon &ph, uint64_t &rx, uint32_t ra)
         to_absorption = (aia * thickness * abs_len + boundary - effective_z) * recip_dz;
     }
     if (!TILT) ph.layer = j;
+#endif
     if (to_absorption < distance) {
         distance = to_absorption;
         ph.abs_lens_left = 0.0f;
@@ -860,8 +933,14 @@ DM void collide_with_string(KP P, const Detector &D, uint32_t s, float dir_len_x
 DM uint32_t free_flight_bound(KP P, float x, float y)
 {
     const int n = P->prox_n;
+#ifdef KPARAMS_BAKED
+    // (run-time compiled kernel, round 10: two instructions per index, dm::clamp_index_of)
+    const int ix = dm::clamp_index_of<KParams::prox_n - 1>((x - P->prox_x0) * P->prox_inv_cell);
+    const int iy = dm::clamp_index_of<KParams::prox_n - 1>((y - P->prox_y0) * P->prox_inv_cell);
+#else
     const int ix = clamp_index((int)((x - P->prox_x0) * P->prox_inv_cell), n - 1);
     const int iy = clamp_index((int)((y - P->prox_y0) * P->prox_inv_cell), n - 1);
+#endif
     // (24-bit multiplies -- full rate where the 32-bit one is a quarter -- in this and the two other index computations of the loop: measured
     // 0.4 % SLOWER, profiles/r04/ab_quarter_rate.txt: v_mad_u64_u32 forms the product and the sum in one instruction)
     return P->prox_map[(uint32_t)iy * (uint32_t)n + (uint32_t)ix];
@@ -915,9 +994,16 @@ DM uint32_t dom_search_needed(KP P, const Photon &ph, float len)
     CENSUS_REGION(P, kCensusFilter);
     const float inv = P->dprox_inv_cell;
     const int ny = P->dprox_ny, nz = P->dprox_nz;
+#ifdef KPARAMS_BAKED
+    // (run-time compiled kernel, round 10: two instructions per index, dm::clamp_index_of)
+    const int ix = dm::clamp_index_of<KParams::dprox_nx - 1>((ph.px - P->dprox_x0) * inv);
+    const int iy = dm::clamp_index_of<KParams::dprox_ny - 1>((ph.py - P->dprox_y0) * inv);
+    const int iz = dm::clamp_index_of<KParams::dprox_nz - 1>((ph.pz - P->dprox_z0) * inv);
+#else
     const int ix = clamp_index((int)((ph.px - P->dprox_x0) * inv), P->dprox_nx - 1);
     const int iy = clamp_index((int)((ph.py - P->dprox_y0) * inv), ny - 1);
     const int iz = clamp_index((int)((ph.pz - P->dprox_z0) * inv), nz - 1);
+#endif
     // the cell: {word, centre of the DOM it names} in one 16-byte load (z runs fastest; at most 2^24 cells)
     const uint4 cell = P->dom_cells[((uint32_t)ix * (uint32_t)ny + (uint32_t)iy) * (uint32_t)nz + (uint32_t)iz];
     const uint32_t w = cell.x;

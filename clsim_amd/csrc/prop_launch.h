@@ -33,6 +33,8 @@ hipError_t launch_scan_steps(const KParams &P, hipStream_t stream);
 hipError_t launch_assemble_hits(const KParams &P, bool flasher, hipStream_t stream);
 hipError_t launch_eval_math(int what, const float *xs, const float *ys, uint32_t n, float *out, hipStream_t stream);
 hipError_t launch_check_math(int what, int exp_lo, int exp_hi, uint32_t *result, uint32_t result_cap, hipStream_t stream);
+// ---- index_clamp_check_kernel.hip: launch_check_math's what = 20 ----
+hipError_t launch_check_index_clamp(uint32_t *result, uint32_t result_cap, hipStream_t stream);
 // ---- prop_eval_kernel.hip: single functions of the propagator ----
 hipError_t launch_eval_function(const KParams &P, int lengths_kind, bool has_tilt, bool fast, int what, int layer, const float4 *in, uint32_t n, float4 *out,
                                 hipStream_t stream);

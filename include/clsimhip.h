@@ -461,7 +461,9 @@ int clsimhip_eval_device_random(clsimhip_converter *c, int what, int generator, 
  * divisor signs x 40 numerators each (random and adversarial, exponents -40 ... 60); result[1..] = (numerator, divisor)
  * pairs of the first mismatches.  what = 17 / 18: the reciprocal of a reciprocal, the reciprocal root next to one (detmath.hip.h).
  * what = 19: the table maker's axis bin (floor, saturating conversion, clamp: Axis.cxx:45-60) as the kernel forms it against the
- * spelled-out conversion on ALL 2^32 bit patterns x five bin counts (exp_lo / exp_hi do not apply). */
+ * spelled-out conversion on ALL 2^32 bit patterns x five bin counts (exp_lo / exp_hi do not apply).
+ * what = 20: the run-time compiled kernel's table index from a float (unsigned conversion + minimum with the literal bound) against
+ * clamp((int)f, 0, bound) on ALL 2^32 bit patterns x the bounds 0, 1, 0xa8, 0xaa, 0x1ff, 0x3fff (exp_lo / exp_hi do not apply). */
 int clsimhip_check_math_exhaustive(int device_ordinal, int what, int exp_lo, int exp_hi, uint32_t *result, size_t result_cap);
 
 const char *clsimhip_version(void);
