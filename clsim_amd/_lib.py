@@ -154,6 +154,11 @@ SYMBOLS = [
     "clsimhip_frame_photon_store_create", "clsimhip_frame_photon_store_destroy", "clsimhip_frame_photon_store_last_error",
     "clsimhip_frame_photon_store_add_host", "clsimhip_frame_photon_store_add_device", "clsimhip_frame_photon_store_drain_device",
     "clsimhip_frame_photon_store_drain_host", "clsimhip_frame_photon_store_size",
+    "clsimhip_pmt_hits_union_host", "clsimhip_pmt_hits_split_host", "clsimhip_pmt_hits_union_workspace_bytes",
+    "clsimhip_pmt_hits_union_device", "clsimhip_pmt_hits_split_device",
+    "clsimhip_pmt_hit_store_create", "clsimhip_pmt_hit_store_destroy", "clsimhip_pmt_hit_store_last_error",
+    "clsimhip_pmt_hit_store_add_host", "clsimhip_pmt_hit_store_add_device", "clsimhip_pmt_hit_store_drain_device",
+    "clsimhip_pmt_hit_store_drain_host", "clsimhip_pmt_hit_store_size",
     "clsimhip_cable_shadow_create", "clsimhip_cable_shadow_destroy", "clsimhip_cable_shadow_last_error", "clsimhip_cable_shadow_host",
     "clsimhip_cable_shadow_workspace_bytes", "clsimhip_cable_shadow_device", "clsimhip_set_cable_shadow", "clsimhip_get_result_cable_shadow",
     "clsimhip_event_statistics_add", "clsimhip_event_statistics_weight", "clsimhip_event_statistics_host",
@@ -386,6 +391,19 @@ def load():
         "clsimhip_frame_photon_store_drain_device": (i32, [vp, u32, vp, vp, vp, sz, vp]),
         "clsimhip_frame_photon_store_drain_host": (i32, [vp, u32, vp, vp, sz, C.POINTER(sz), C.POINTER(sz)]),
         "clsimhip_frame_photon_store_size": (i32, [vp, u32, C.POINTER(sz), C.POINTER(sz)]),
+        "clsimhip_pmt_hits_union_host": (i32, [vp, sz, vp, sz, vp, sz, vp, sz, vp, vp, sz, C.POINTER(sz), C.POINTER(sz)]),
+        "clsimhip_pmt_hits_split_host": (i32, [vp, sz, vp, sz, u32, vp, vp, sz, C.POINTER(sz), C.POINTER(sz), vp, vp, sz, C.POINTER(sz), C.POINTER(sz)]),
+        "clsimhip_pmt_hits_union_workspace_bytes": (sz, [sz, sz]),
+        "clsimhip_pmt_hits_union_device": (i32, [i32, vp, vp, vp, sz, vp, vp, vp, sz, vp, vp, vp, sz, vp, sz, vp]),
+        "clsimhip_pmt_hits_split_device": (i32, [i32, vp, vp, vp, sz, u32, vp, vp, vp, sz, vp, vp, vp, sz, vp]),
+        "clsimhip_pmt_hit_store_create": (i32, [i32, sz, C.POINTER(vp)]),
+        "clsimhip_pmt_hit_store_destroy": (None, [vp]),
+        "clsimhip_pmt_hit_store_last_error": (C.c_char_p, [vp]),
+        "clsimhip_pmt_hit_store_add_host": (i32, [vp, vp, sz, vp, sz]),
+        "clsimhip_pmt_hit_store_add_device": (i32, [vp, vp, vp, vp, sz, vp]),
+        "clsimhip_pmt_hit_store_drain_device": (i32, [vp, u32, vp, vp, vp, sz, vp]),
+        "clsimhip_pmt_hit_store_drain_host": (i32, [vp, u32, vp, vp, sz, C.POINTER(sz), C.POINTER(sz)]),
+        "clsimhip_pmt_hit_store_size": (i32, [vp, u32, C.POINTER(sz), C.POINTER(sz)]),
         "clsimhip_cable_shadow_create": (i32, [sz, vp, vp, vp, dbl, C.POINTER(vp)]),
         "clsimhip_cable_shadow_destroy": (None, [vp]),
         "clsimhip_cable_shadow_last_error": (C.c_char_p, [vp]),
@@ -418,7 +436,8 @@ def load():
         # statistics stage, of the photon hits stage and of the two frame stores, which bench.py does not call)
         newer = (name in ("clsimhip_baked_info", "clsimhip_baked_compile", "clsimhip_baked_set_compiler_library") or "event_statistics" in name
                  or "photon_hit" in name or "mcpe_series_union" in name or "mcpe_series_split" in name or "mcpe_frame_store" in name
-                 or "frame_photons_union" in name or "frame_photons_split" in name or "frame_photon_store" in name)
+                 or "frame_photons_union" in name or "frame_photons_split" in name or "frame_photon_store" in name
+                 or "pmt_hits_union" in name or "pmt_hits_split" in name or "pmt_hit_store" in name)
         if newer and LIB_PATH != DEFAULT_LIB_PATH and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol

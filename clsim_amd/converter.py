@@ -997,6 +997,117 @@ class FramePhotonStore:
                                                                int(tail_capacity), C.c_void_p(stream)))
 
 
+def _pmt_hit_form(records, series):
+    return np.ascontiguousarray(records, dtype=PMT_HIT_DTYPE), np.ascontiguousarray(series, dtype=PMT_SERIES_DTYPE)
+
+
+class PMTHitFrameStore:
+    """The PMT hit series of several bunches accumulate per frame; finished frames leave (clsimhip_pmt_hit_store): what MCPEFrameStore
+    is for MCPEs and FramePhotonStore for frame photons, for PMT_HIT_DTYPE records with their PMT_SERIES_DTYPE table.  device=None: a
+    host store, which needs no GPU; device=k: the state lives in HBM of GPU k.  Call Add (or AddDevice) per result and Drain with the
+    last frame no bunch in flight can still touch."""
+
+    def __init__(self, capacity, device=None):
+        self._lib = _lib.load()
+        self._h = C.c_void_p()
+        self.capacity, self.device = int(capacity), device
+        _check(self._lib.clsimhip_pmt_hit_store_create(-1 if device is None else int(device), self.capacity, C.byref(self._h)))
+
+    def __del__(self):
+        try:
+            if self._h:
+                self._lib.clsimhip_pmt_hit_store_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def Add(self, records, series):
+        """one bunch in host memory, a series form of PMT hits (MakeSeriesHost's or MakeHitsFromFramePhotonsHost's records and series,
+        or a result's PMT series)"""
+        records, series = _pmt_hit_form(records, series)
+        _check(self._lib.clsimhip_pmt_hit_store_add_host(self._h, records.ctypes.data_as(C.c_void_p), len(records), series.ctypes.data_as(C.c_void_p), len(series)))
+
+    def AddDevice(self, d_records, d_series, d_series_counts, capacity, stream=0):
+        """one bunch in HBM (addresses: MakeSeriesDevice's or MakeHitsFromFramePhotonsDevice's d_out, d_series and d_counts);
+        asynchronous on `stream`"""
+        _check(self._lib.clsimhip_pmt_hit_store_add_device(self._h, C.c_void_p(d_records), C.c_void_p(d_series), C.c_void_p(d_series_counts), int(capacity),
+                                                           C.c_void_p(stream)))
+
+    def Size(self, last_frame=ALL_FRAMES):
+        """(records, series) a Drain up to last_frame would take; waits"""
+        n, n_series = C.c_size_t(), C.c_size_t()
+        _check(self._lib.clsimhip_pmt_hit_store_size(self._h, int(last_frame), C.byref(n), C.byref(n_series)))
+        return n.value, n_series.value
+
+    def Drain(self, last_frame=ALL_FRAMES):
+        """(records, series) of the frames <= last_frame, which leave the store; waits"""
+        n, n_series = self.Size(last_frame)
+        records, series = np.zeros(n, dtype=PMT_HIT_DTYPE), np.zeros(n_series, dtype=PMT_SERIES_DTYPE)
+        got, got_series = C.c_size_t(), C.c_size_t()
+        _check(self._lib.clsimhip_pmt_hit_store_drain_host(self._h, int(last_frame), records.ctypes.data_as(C.c_void_p), series.ctypes.data_as(C.c_void_p),
+                                                           n, C.byref(got), C.byref(got_series)))
+        return records[:got.value], series[:got_series.value]
+
+    def DrainDevice(self, last_frame, d_records, d_series, d_counts, capacity, stream=0):
+        """the frames <= last_frame move to the caller's device buffers (addresses; d_counts: five uint32, records and series first);
+        asynchronous on `stream`"""
+        _check(self._lib.clsimhip_pmt_hit_store_drain_device(self._h, int(last_frame), C.c_void_p(d_records), C.c_void_p(d_series), C.c_void_p(d_counts),
+                                                             int(capacity), C.c_void_p(stream)))
+
+    @staticmethod
+    def UnionHost(a_records, a_series, b_records, b_series, capacity=None):
+        """(records, series): the host twin of the union of two series forms of PMT hits; capacity: of the output, len(a) + len(b) by
+        default"""
+        a_records, a_series = _pmt_hit_form(a_records, a_series)
+        b_records, b_series = _pmt_hit_form(b_records, b_series)
+        capacity = len(a_records) + len(b_records) if capacity is None else int(capacity)
+        out, series = np.zeros(capacity, dtype=PMT_HIT_DTYPE), np.zeros(capacity, dtype=PMT_SERIES_DTYPE)
+        n, n_series = C.c_size_t(), C.c_size_t()
+        _check(_lib.load().clsimhip_pmt_hits_union_host(a_records.ctypes.data_as(C.c_void_p), len(a_records), a_series.ctypes.data_as(C.c_void_p), len(a_series),
+                                                        b_records.ctypes.data_as(C.c_void_p), len(b_records), b_series.ctypes.data_as(C.c_void_p), len(b_series),
+                                                        out.ctypes.data_as(C.c_void_p), series.ctypes.data_as(C.c_void_p), capacity, C.byref(n), C.byref(n_series)))
+        return out[:n.value], series[:n_series.value]
+
+    @staticmethod
+    def SplitHost(records, series, last_frame, head_capacity=None, tail_capacity=None):
+        """(head_records, head_series, tail_records, tail_series): the host twin of the split -- the head holds the frames <= last_frame"""
+        records, series = _pmt_hit_form(records, series)
+        head_capacity = len(records) if head_capacity is None else int(head_capacity)
+        tail_capacity = len(records) if tail_capacity is None else int(tail_capacity)
+        head, head_series = np.zeros(head_capacity, dtype=PMT_HIT_DTYPE), np.zeros(head_capacity, dtype=PMT_SERIES_DTYPE)
+        tail, tail_series = np.zeros(tail_capacity, dtype=PMT_HIT_DTYPE), np.zeros(tail_capacity, dtype=PMT_SERIES_DTYPE)
+        sizes = [C.c_size_t() for _ in range(4)]
+        _check(_lib.load().clsimhip_pmt_hits_split_host(records.ctypes.data_as(C.c_void_p), len(records), series.ctypes.data_as(C.c_void_p), len(series),
+                                                        int(last_frame), head.ctypes.data_as(C.c_void_p), head_series.ctypes.data_as(C.c_void_p), head_capacity,
+                                                        C.byref(sizes[0]), C.byref(sizes[1]), tail.ctypes.data_as(C.c_void_p),
+                                                        tail_series.ctypes.data_as(C.c_void_p), tail_capacity, C.byref(sizes[2]), C.byref(sizes[3])))
+        return head[:sizes[0].value], head_series[:sizes[1].value], tail[:sizes[2].value], tail_series[:sizes[3].value]
+
+    @staticmethod
+    def UnionWorkspaceBytes(capacity_a, capacity_b):
+        return int(_lib.load().clsimhip_pmt_hits_union_workspace_bytes(int(capacity_a), int(capacity_b)))
+
+    @staticmethod
+    def UnionDevice(d_a_records, d_a_series, d_a_counts, capacity_a, d_b_records, d_b_series, d_b_counts, capacity_b, d_out_records, d_out_series,
+                    d_out_counts, out_capacity, d_workspace, workspace_bytes, device=0, stream=0):
+        """the kernels on device-resident series forms (addresses; each input pairs with MakeSeriesDevice's or
+        MakeHitsFromFramePhotonsDevice's d_out, d_series and d_counts, or with another union's output); d_out_counts: five uint32
+        (MCPE_UNION_COUNTS), d_workspace: UnionWorkspaceBytes(capacity_a, capacity_b) bytes"""
+        _check(_lib.load().clsimhip_pmt_hits_union_device(int(device), C.c_void_p(d_a_records), C.c_void_p(d_a_series), C.c_void_p(d_a_counts), int(capacity_a),
+                                                          C.c_void_p(d_b_records), C.c_void_p(d_b_series), C.c_void_p(d_b_counts), int(capacity_b),
+                                                          C.c_void_p(d_out_records), C.c_void_p(d_out_series), C.c_void_p(d_out_counts), int(out_capacity),
+                                                          C.c_void_p(d_workspace), int(workspace_bytes), C.c_void_p(stream)))
+
+    @staticmethod
+    def SplitDevice(d_records, d_series, d_counts, capacity, last_frame, d_head_records, d_head_series, d_head_counts, head_capacity, d_tail_records,
+                    d_tail_series, d_tail_counts, tail_capacity, device=0, stream=0):
+        """the split on device-resident series (addresses); d_head_counts / d_tail_counts: five uint32 each (records, series, 0, 0, overflow)"""
+        _check(_lib.load().clsimhip_pmt_hits_split_device(int(device), C.c_void_p(d_records), C.c_void_p(d_series), C.c_void_p(d_counts), int(capacity),
+                                                          int(last_frame), C.c_void_p(d_head_records), C.c_void_p(d_head_series), C.c_void_p(d_head_counts),
+                                                          int(head_capacity), C.c_void_p(d_tail_records), C.c_void_p(d_tail_series), C.c_void_p(d_tail_counts),
+                                                          int(tail_capacity), C.c_void_p(stream)))
+
+
 class CableShadow:
     """The cylinder set of the cable shadow stage (clsimhip_cable_shadow; include/clsimhip.h: "Cable shadow"): a detected photon whose
     last `distance` metres of path meet a solid finite cylinder is shadowed.  top, bottom: [n, 3] end points; radius: [n] or one value

@@ -20,6 +20,7 @@
 #include "event_stats.h"
 #include "frame_photons.h"
 #include "frame_photon_union.h"
+#include "pmt_hit_union.h"
 #include "pmt_series.h"
 #include "photon_hits.h"
 #include "pmt_photon_hits.h"
@@ -35,6 +36,7 @@ struct clsimhip_cable_shadow { std::shared_ptr<CableShadow> impl; };
 struct clsimhip_photon_hit_maker { std::shared_ptr<PhotonHitMaker> impl; };
 struct clsimhip_mcpe_frame_store { std::unique_ptr<FrameStore> impl; };
 struct clsimhip_frame_photon_store { std::unique_ptr<FramePhotonStore> impl; };
+struct clsimhip_pmt_hit_store { std::unique_ptr<PmtHitStore> impl; };
 struct clsimhip_tabulator {
     std::unique_ptr<Tabulator> impl;
 };
@@ -1367,6 +1369,78 @@ int clsimhip_frame_photon_store_drain_host(clsimhip_frame_photon_store *s, uint3
     return guarded(nullptr, [&] { need(s, "store"); s->impl->drain_host(last_frame, records, series, capacity, n, n_series); });
 }
 int clsimhip_frame_photon_store_size(clsimhip_frame_photon_store *s, uint32_t last_frame, size_t *n, size_t *n_series)
+{
+    return guarded(nullptr, [&] { need(s, "store"); s->impl->size(last_frame, n, n_series); });
+}
+
+// ---- PMT hit frame store (pmt_hit_union.h) ----
+int clsimhip_pmt_hits_union_host(const clsimhip_pmt_hit *a_records, size_t n_a, const clsimhip_pmt_series *a_series, size_t n_series_a,
+                                 const clsimhip_pmt_hit *b_records, size_t n_b, const clsimhip_pmt_series *b_series, size_t n_series_b,
+                                 clsimhip_pmt_hit *out_records, clsimhip_pmt_series *out_series, size_t out_capacity, size_t *n, size_t *n_series)
+{
+    return guarded(nullptr, [&] {
+        pmt_hits_union_host(a_records, n_a, a_series, n_series_a, b_records, n_b, b_series, n_series_b, out_records, out_series, out_capacity, n, n_series);
+    });
+}
+int clsimhip_pmt_hits_split_host(const clsimhip_pmt_hit *records, size_t n, const clsimhip_pmt_series *series, size_t n_series, uint32_t last_frame,
+                                 clsimhip_pmt_hit *head_records, clsimhip_pmt_series *head_series, size_t head_capacity, size_t *n_head,
+                                 size_t *n_series_head, clsimhip_pmt_hit *tail_records, clsimhip_pmt_series *tail_series, size_t tail_capacity,
+                                 size_t *n_tail, size_t *n_series_tail)
+{
+    return guarded(nullptr, [&] {
+        pmt_hits_split_host(records, n, series, n_series, last_frame, head_records, head_series, head_capacity, n_head, n_series_head, tail_records, tail_series,
+                            tail_capacity, n_tail, n_series_tail);
+    });
+}
+size_t clsimhip_pmt_hits_union_workspace_bytes(size_t capacity_a, size_t capacity_b) { return pmt_hits_union_workspace_bytes(capacity_a, capacity_b); }
+int clsimhip_pmt_hits_union_device(int device, const void *d_a_records, const void *d_a_series, const void *d_a_counts, size_t capacity_a,
+                                   const void *d_b_records, const void *d_b_series, const void *d_b_counts, size_t capacity_b,
+                                   void *d_out_records, void *d_out_series, void *d_out_counts, size_t out_capacity, void *d_workspace,
+                                   size_t workspace_bytes, void *hip_stream)
+{
+    return guarded(nullptr, [&] {
+        pmt_hits_union_device(device, d_a_records, d_a_series, d_a_counts, capacity_a, d_b_records, d_b_series, d_b_counts, capacity_b, d_out_records, d_out_series,
+                              d_out_counts, out_capacity, d_workspace, workspace_bytes, static_cast<hipStream_t>(hip_stream));
+    });
+}
+int clsimhip_pmt_hits_split_device(int device, const void *d_records, const void *d_series, const void *d_counts, size_t capacity,
+                                   uint32_t last_frame, void *d_head_records, void *d_head_series, void *d_head_counts, size_t head_capacity,
+                                   void *d_tail_records, void *d_tail_series, void *d_tail_counts, size_t tail_capacity, void *hip_stream)
+{
+    return guarded(nullptr, [&] {
+        pmt_hits_split_device(device, d_records, d_series, d_counts, capacity, last_frame, d_head_records, d_head_series, d_head_counts, head_capacity, d_tail_records,
+                              d_tail_series, d_tail_counts, tail_capacity, static_cast<hipStream_t>(hip_stream));
+    });
+}
+int clsimhip_pmt_hit_store_create(int device, size_t capacity, clsimhip_pmt_hit_store **out)
+{
+    return guarded(nullptr, [&] {
+        need(out, "out");
+        *out = new clsimhip_pmt_hit_store{device < 0 ? make_host_pmt_hit_store(capacity) : make_device_pmt_hit_store(device, capacity)};
+    });
+}
+void clsimhip_pmt_hit_store_destroy(clsimhip_pmt_hit_store *s) { delete s; }
+const char *clsimhip_pmt_hit_store_last_error(const clsimhip_pmt_hit_store *s) { (void)s; return g_last_error.c_str(); }
+int clsimhip_pmt_hit_store_add_host(clsimhip_pmt_hit_store *s, const clsimhip_pmt_hit *records, size_t n, const clsimhip_pmt_series *series, size_t n_series)
+{
+    return guarded(nullptr, [&] { need(s, "store"); s->impl->add_host(records, n, series, n_series); });
+}
+int clsimhip_pmt_hit_store_add_device(clsimhip_pmt_hit_store *s, const void *d_records, const void *d_series, const void *d_series_counts, size_t capacity,
+                                      void *hip_stream)
+{
+    return guarded(nullptr, [&] { need(s, "store"); s->impl->add_device(d_records, d_series, d_series_counts, capacity, static_cast<hipStream_t>(hip_stream)); });
+}
+int clsimhip_pmt_hit_store_drain_device(clsimhip_pmt_hit_store *s, uint32_t last_frame, void *d_records, void *d_series, void *d_counts, size_t capacity,
+                                        void *hip_stream)
+{
+    return guarded(nullptr, [&] { need(s, "store"); s->impl->drain_device(last_frame, d_records, d_series, d_counts, capacity, static_cast<hipStream_t>(hip_stream)); });
+}
+int clsimhip_pmt_hit_store_drain_host(clsimhip_pmt_hit_store *s, uint32_t last_frame, clsimhip_pmt_hit *records, clsimhip_pmt_series *series, size_t capacity,
+                                      size_t *n, size_t *n_series)
+{
+    return guarded(nullptr, [&] { need(s, "store"); s->impl->drain_host(last_frame, records, series, capacity, n, n_series); });
+}
+int clsimhip_pmt_hit_store_size(clsimhip_pmt_hit_store *s, uint32_t last_frame, size_t *n, size_t *n_series)
 {
     return guarded(nullptr, [&] { need(s, "store"); s->impl->size(last_frame, n, n_series); });
 }

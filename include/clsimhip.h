@@ -1337,6 +1337,82 @@ int clsimhip_frame_photon_store_drain_host(clsimhip_frame_photon_store *s, uint3
                                            size_t capacity, size_t *n, size_t *n_series);
 int clsimhip_frame_photon_store_size(clsimhip_frame_photon_store *s, uint32_t last_frame, size_t *n, size_t *n_series);
 
+/* ---- PMT hit frame store: the PMT hit series of several bunches accumulate per frame; finished frames leave --------------------
+ * PMT series, continued: what the MCPE frame store is for MCPEs and the frame photon store for frame photons, for clsimhip_pmt_hit
+ * records with their clsimhip_pmt_series table -- the reference files every result into a frame cache that lives across bunches
+ * (private/clsim/I3CLSimClientModule.cxx:359-439) and FlushFrameCache() commits the oldest frames no bunch in flight can still
+ * touch (:686-758).  With keep_photons = 0 there are no frame photons to accumulate, and this store is what joins bunches.
+ * SERIES FORM OF PMT HITS: (records, table) as clsimhip_pmt_series_device and clsimhip_pmt_photon_hits_device write them.  The
+ *     table is strictly ascending in (frame, string_id signed, om_id, pmt); every count > 0; first[0] = 0 and first[s] =
+ *     first[s-1] + count[s-1]; the last entry ends at the number of records (an empty table needs zero records); every entry has
+ *     reserved == 0; every record carries its entry's string_id, om_id and pmt and has reserved == 0; inside a series
+ *     (tkey(time), identifier) does not descend.  Each element (entry or record) that breaks one of these rules is one MALFORMED
+ *     element.  The checks are local -- an entry looks at itself and its predecessor, a record at its entry and its predecessor --
+ *     and together they imply the partition and the global order.  The two reserved rules are what make equal keys equal bytes.
+ * KEY of a record: six 32-bit words, most significant first -- frame of its entry, module (string_id signed, om_id), pmt (the
+ *     whole word, not only values below 64), tkey high, tkey low, identifier -- compared as unsigned integers.  The time travels as
+ *     its bit pattern (tkey is an inversion on the bits; no floating-point value is formed), so a signalling NaN keeps its payload:
+ *     negative NaNs come first, then -inf ... -0, +0 ... +inf, positive NaNs last.
+ * UNION(A, B): the series form of the multiset union, ties A first, which changes no byte, the table rebuilt from the heads.  Equal
+ *     keys are equal bytes, so the union is a function of the multiset: the same bytes whatever order the bunches arrive in, and
+ *     for any split of a bunch's hits into two parts with one particle table and mask the union of their PMT series is the PMT
+ *     series of the whole, byte for byte.  n_a + n_b must fit the output capacity.
+ * SPLIT(X, last_frame): the head is the entries with frame <= last_frame and their records, a prefix; the tail is the rest with
+ *     `first` rebased to 0.  last_frame = 0xFFFFFFFF drains everything.
+ * The host twins (std::merge on the key; host only, no GPU is touched): malformed input or an output that does not fit is
+ * CLSIMHIP_ERR_ARGUMENT with text that names the first offending element. */
+int clsimhip_pmt_hits_union_host(const clsimhip_pmt_hit *a_records, size_t n_a, const clsimhip_pmt_series *a_series, size_t n_series_a,
+                                 const clsimhip_pmt_hit *b_records, size_t n_b, const clsimhip_pmt_series *b_series, size_t n_series_b,
+                                 clsimhip_pmt_hit *out_records, clsimhip_pmt_series *out_series, size_t out_capacity, size_t *n, size_t *n_series);
+int clsimhip_pmt_hits_split_host(const clsimhip_pmt_hit *records, size_t n, const clsimhip_pmt_series *series, size_t n_series, uint32_t last_frame,
+                                 clsimhip_pmt_hit *head_records, clsimhip_pmt_series *head_series, size_t head_capacity, size_t *n_head,
+                                 size_t *n_series_head, clsimhip_pmt_hit *tail_records, clsimhip_pmt_series *tail_series, size_t tail_capacity,
+                                 size_t *n_tail, size_t *n_series_tail);
+/* bytes of device memory the union's kernels need beside their inputs and output */
+size_t clsimhip_pmt_hits_union_workspace_bytes(size_t capacity_a, size_t capacity_b);
+/* The kernels, on series that live in HBM.  Inputs are read as min(counts[0], capacity) records and min(counts[1], capacity) series,
+ * so clsimhip_pmt_series_device's five-word d_counts and clsimhip_pmt_photon_hits_device's seven-word d_counts chain in unchanged.
+ * d_out_counts: five uint32 -- records, series, MALFORMED elements in A, MALFORMED elements in B, overflow (n_a + n_b when it does
+ * not fit out_capacity, else 0).  When B is malformed or the union does not fit, the output is A unchanged (nothing, should A alone
+ * not fit); when A is malformed, the output is empty.  Nothing is written beyond a capacity and every loop is bounded by one,
+ * whatever bytes the inputs hold.  The output must not overlap an input.  Records and tables are 8-byte aligned (what
+ * clsimhip_pmt_series_device produces; 24-byte elements cannot promise more), d_workspace
+ * (clsimhip_pmt_hits_union_workspace_bytes(capacity_a, capacity_b) bytes) 16-byte aligned; capacities are at most 2^31.
+ * Asynchronous on hip_stream (NULL = default stream); nothing waits for the device.  Errors are CLSIMHIP_ERR_ARGUMENT, with nothing
+ * launched. */
+int clsimhip_pmt_hits_union_device(int device, const void *d_a_records, const void *d_a_series, const void *d_a_counts, size_t capacity_a,
+                                   const void *d_b_records, const void *d_b_series, const void *d_b_counts, size_t capacity_b,
+                                   void *d_out_records, void *d_out_series, void *d_out_counts, size_t out_capacity, void *d_workspace,
+                                   size_t workspace_bytes, void *hip_stream);
+/* The split on the device; the input is taken as a series form and not checked again.  d_head_counts and d_tail_counts: five uint32
+ * each -- records, series, 0, 0, overflow.  A head that does not fit head_capacity drains nothing: the head is empty, the tail is
+ * everything, and the needed size goes into the head's overflow word.  tail_capacity >= capacity (CLSIMHIP_ERR_ARGUMENT otherwise). */
+int clsimhip_pmt_hits_split_device(int device, const void *d_records, const void *d_series, const void *d_counts, size_t capacity,
+                                   uint32_t last_frame, void *d_head_records, void *d_head_series, void *d_head_counts, size_t head_capacity,
+                                   void *d_tail_records, void *d_tail_series, void *d_tail_counts, size_t tail_capacity, void *hip_stream);
+/* The store, as clsimhip_mcpe_frame_store: device < 0 is a host store on the twins that touches no GPU; a device store owns two
+ * record and two table buffers used in turn, a workspace, five sticky counters in page-locked memory and one event that every
+ * operation waits for and records again, so operations issued on different streams are ordered as they were called.  add_host
+ * validates the bunch on the host before anything moves; add_device pairs with clsimhip_pmt_series_device and
+ * clsimhip_pmt_photon_hits_device (their d_out, d_series, d_counts) and refuses at once a bunch buffer longer than the store's
+ * capacity.  A bunch dropped on the device (malformed, or one that does not fit) is counted in the sticky counters; while one is
+ * nonzero, _size and both drains return CLSIMHIP_ERR_DEVICE with the counts in the text and nothing is delivered.  _size and
+ * drain_host wait for the store's event first and always see it; drain_device does not wait, so while the add_device that drops the
+ * bunch is still in flight it returns CLSIMHIP_OK, its kernel looks at the counters again on the device and delivers an EMPTY head,
+ * and the error is raised by the next call that waits. */
+typedef struct clsimhip_pmt_hit_store clsimhip_pmt_hit_store;
+int clsimhip_pmt_hit_store_create(int device, size_t capacity, clsimhip_pmt_hit_store **out);
+void clsimhip_pmt_hit_store_destroy(clsimhip_pmt_hit_store *s);
+const char *clsimhip_pmt_hit_store_last_error(const clsimhip_pmt_hit_store *s);
+int clsimhip_pmt_hit_store_add_host(clsimhip_pmt_hit_store *s, const clsimhip_pmt_hit *records, size_t n, const clsimhip_pmt_series *series, size_t n_series);
+int clsimhip_pmt_hit_store_add_device(clsimhip_pmt_hit_store *s, const void *d_records, const void *d_series, const void *d_series_counts, size_t capacity,
+                                      void *hip_stream);
+int clsimhip_pmt_hit_store_drain_device(clsimhip_pmt_hit_store *s, uint32_t last_frame, void *d_records, void *d_series, void *d_counts, size_t capacity,
+                                        void *hip_stream);
+int clsimhip_pmt_hit_store_drain_host(clsimhip_pmt_hit_store *s, uint32_t last_frame, clsimhip_pmt_hit *records, clsimhip_pmt_series *series, size_t capacity,
+                                      size_t *n, size_t *n_series);
+int clsimhip_pmt_hit_store_size(clsimhip_pmt_hit_store *s, uint32_t last_frame, size_t *n, size_t *n_series);
+
 /* ---- Cable shadow: drop detected photons whose last path crosses a cable ------------------------------------------------------
  * The reference's I3ShadowedPhotonRemoverModule (private/clsim/shadow/): PropagatedPhotons -> PropagatedPhotonsWithShadow, which its
  * photon-to-MCPE converter then reads.  I3ShadowedPhotonRemover::IsPhotonShadowed (I3ShadowedPhotonRemover.cxx:63-81) walks the

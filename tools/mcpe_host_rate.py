@@ -24,6 +24,12 @@ to 1000 particles in 10 frames; --one-dom puts every record on one module of one
 same input (HIP events around clsimhip_frame_photons_union_device, best of --repeats; needs a GPU) and, as the yardstick, the frame
 photons stage re-sorting the N + M source photons (clsimhip_frame_photons_device) in the same run.
 
+--pmt-hit-union N M: the PMT hit frame store's union instead (clsimhip_pmt_hits_union_host, one thread), in records per second: a
+store of the PMT series of N synthetic hits meets a bunch of the PMT series of M more, at 5160 modules of 31 PMTs dealt to 1000
+particles in 10 frames; --one-channel puts every record on one PMT of one module of one frame (one series across all output tiles).
+--device adds the union kernels' time for the same input (HIP events around clsimhip_pmt_hits_union_device, best of --repeats; needs
+a GPU) and, as the yardstick, the PMT series stage re-sorting the N + M hits (clsimhip_pmt_series_device) in the same run.
+
 --pmt: the multi-PMT hit generator's host twin instead (clsimhip_pmt_convert_host) on the same records, against the 31-PMT layout
 of tests/pmt_common.py, in photon records per second.
 
@@ -541,6 +547,81 @@ def frame_photon_union_rate(args):
     print(json.dumps(line))
 
 
+def pmt_hit_union_rate(args):
+    from tests import pmt_common as PC
+    n_a, n_b = args.pmt_hit_union
+    n = n_a + n_b
+    rng = np.random.default_rng(1)
+    s, d = np.meshgrid(np.arange(1, 87), np.arange(1, 61), indexing="ij")
+    s, d = s.reshape(-1).astype(np.int32), d.reshape(-1).astype(np.uint32)
+    types, pmts = PC.layout(PC.sphere_radius_of("mie"))
+    modules = np.zeros(len(s), dtype=CV.PMT_MODULE_DTYPE)
+    modules["stringID"], modules["omID"], modules["rotation"] = s, d, np.eye(3).reshape(9)
+    gen = PC.make_generator(PC.standard_functions(), types, pmts, modules)
+    h = np.zeros(n, dtype=CV.PMT_HIT_DTYPE)
+    at = rng.integers(0, len(s), n)
+    h["stringID"], h["omID"], h["pmt"], h["id"], h["time"] = s[at], d[at], rng.integers(0, 31, n), rng.integers(0, 1000, n), rng.uniform(0.0, 1.0e4, n)
+    p = np.zeros(1000, dtype=CV.MCPE_PARTICLE_DTYPE)
+    p["id"], p["frame"], p["timeShift"] = np.arange(1000), np.arange(1000) % 10, rng.uniform(0.0, 1.0e6, 1000)
+    if args.one_channel:
+        h["stringID"], h["omID"], h["pmt"], p["frame"] = 40, 30, 17, 4
+    a, b, whole = (gen.MakeSeriesHost(part, p)[:2] for part in (h[:n_a], h[n_a:], h))
+    best = float("inf")
+    for _ in range(args.repeats):
+        t0 = time.perf_counter()
+        records, series = CV.PMTHitFrameStore.UnionHost(*a, *b)
+        best = min(best, time.perf_counter() - t0)
+    assert records.tobytes() == whole[0].tobytes() and series.tobytes() == whole[1].tobytes()
+    line = {"input": "one_channel" if args.one_channel else "synthetic", "store_records": n_a, "bunch_records": n_b, "series": len(series), "host_seconds": best,
+            "host_records_per_s": n / best, "threads": 1}
+    if args.device:
+        import torch
+        dev = torch.device("cuda", 0)
+
+        def up(form, capacity):          # (the capacity of a table is that of its records: both buffers are padded to it)
+            out = []
+            for x in form:
+                t = torch.zeros(max(capacity, 1) * 24, dtype=torch.uint8, device=dev)
+                if len(x):
+                    t[:len(x) * 24] = torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).copy()).to(dev)
+                out.append(t)
+            return out + [torch.tensor([len(form[0]), len(form[1]), 0, 0, 0], dtype=torch.int32, device=dev)]
+        d_a, d_b = up(a, n_a), up(b, n_b)
+        d_out, d_table = torch.zeros((max(n, 1), 24), dtype=torch.uint8, device=dev), torch.zeros((max(n, 1), 24), dtype=torch.uint8, device=dev)
+        d_counts = torch.zeros(5, dtype=torch.int32, device=dev)
+        ws = CV.PMTHitFrameStore.UnionWorkspaceBytes(n_a, n_b)
+        d_ws = torch.zeros(ws, dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream().cuda_stream
+        times = []
+        for _ in range(args.repeats + 1):
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            CV.PMTHitFrameStore.UnionDevice(d_a[0].data_ptr(), d_a[1].data_ptr(), d_a[2].data_ptr(), n_a, d_b[0].data_ptr(), d_b[1].data_ptr(), d_b[2].data_ptr(), n_b,
+                                            d_out.data_ptr(), d_table.data_ptr(), d_counts.data_ptr(), n, d_ws.data_ptr(), ws, stream=stream)
+            stop.record()
+            torch.cuda.synchronize()
+            times.append(start.elapsed_time(stop) * 1e-3)
+        assert [int(c) for c in d_counts.cpu()] == [n, len(series), 0, 0, 0]
+        assert d_out.cpu().numpy().reshape(-1)[:n * 24].tobytes() == records.tobytes() and d_table.cpu().numpy().reshape(-1)[:len(series) * 24].tobytes() == series.tobytes()
+        line.update(device_seconds=min(times[1:]), device_records_per_s=n / min(times[1:]))
+        # the yardstick: the PMT series stage re-sorting the N + M hits
+        d_in = torch.from_numpy(h.view(np.uint8).reshape(-1, 24).copy()).to(dev)
+        d_cnt = torch.tensor([n], dtype=torch.int32, device=dev)
+        ws = CV.PMTHitGenerator.SeriesWorkspaceBytes(n, len(p), 0)
+        d_ws = torch.zeros(ws, dtype=torch.uint8, device=dev)
+        times = []
+        for _ in range(args.repeats + 1):
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            gen.MakeSeriesDevice(d_in.data_ptr(), d_cnt.data_ptr(), n, d_out.data_ptr(), d_table.data_ptr(), d_counts.data_ptr(), d_ws.data_ptr(), ws, p, None, stream=stream)
+            stop.record()
+            torch.cuda.synchronize()
+            times.append(start.elapsed_time(stop) * 1e-3)
+        assert int(d_counts[0]) == n and d_out.cpu().numpy().reshape(-1)[:n * 24].tobytes() == records.tobytes()
+        line.update(resort_device_seconds=min(times[1:]), union_over_resort=line["device_seconds"] / min(times[1:]))
+    print(json.dumps(line))
+
+
 def merge_rate(args):
     from tests import mcpe_merge_common as MM
     from tests import mcpe_series_common as S
@@ -595,6 +676,8 @@ def main():
     ap.add_argument("--union", type=int, nargs=2, default=None, metavar=("N", "M"))
     ap.add_argument("--frame-photon-union", type=int, nargs=2, default=None, metavar=("N", "M"))
     ap.add_argument("--one-dom", action="store_true")
+    ap.add_argument("--pmt-hit-union", type=int, nargs=2, default=None, metavar=("N", "M"))
+    ap.add_argument("--one-channel", action="store_true")
     ap.add_argument("--pmt-series", type=int, default=0, metavar="N")
     ap.add_argument("--frame-photons", type=int, default=0, metavar="N")
     ap.add_argument("--cable-shadow", type=int, default=0, metavar="N")
@@ -607,6 +690,8 @@ def main():
         return union_rate(args)
     if args.frame_photon_union:
         return frame_photon_union_rate(args)
+    if args.pmt_hit_union:
+        return pmt_hit_union_rate(args)
     if args.pmt_photon_hits:
         return pmt_photon_hits_rate(args)
     if args.photon_hits:
