@@ -167,6 +167,9 @@ SYMBOLS = [
     "clsimhip_photon_hit_maker_create", "clsimhip_photon_hit_maker_destroy", "clsimhip_photon_hit_maker_last_error",
     "clsimhip_photon_hit_maker_efficiency", "clsimhip_photon_hits_host", "clsimhip_photon_hits_workspace_bytes", "clsimhip_photon_hits_device",
     "clsimhip_pmt_photon_hits_host", "clsimhip_pmt_photon_hits_workspace_bytes", "clsimhip_pmt_photon_hits_device",
+    "clsimhip_slice_muons",
+    "clsimhip_mcpe_series_relabel_host", "clsimhip_frame_photons_relabel_host", "clsimhip_series_relabel_workspace_bytes",
+    "clsimhip_mcpe_series_relabel_device", "clsimhip_frame_photons_relabel_device", "clsimhip_mcpe_parents_relabel_host",
 ]
 
 # clsimhip_get_last_launch: CLSIMHIP_FAMILY_* and CLSIMHIP_LENGTHS_* by name
@@ -429,15 +432,22 @@ def load():
         "clsimhip_pmt_photon_hits_host": (i32, [vp, vp, sz, vp, sz, vp, vp, C.POINTER(sz), C.POINTER(sz), vp]),
         "clsimhip_pmt_photon_hits_workspace_bytes": (sz, [sz]),
         "clsimhip_pmt_photon_hits_device": (i32, [vp, i32, vp, vp, vp, sz, vp, vp, vp, vp, sz, vp]),
+        "clsimhip_slice_muons": (i32, [vp, sz, vp, sz, u32, vp, sz, C.POINTER(sz), vp, sz, C.POINTER(sz), vp]),
+        "clsimhip_mcpe_series_relabel_host": (i32, [vp, sz, vp, sz, vp, sz, vp, vp, C.POINTER(sz)]),
+        "clsimhip_frame_photons_relabel_host": (i32, [vp, sz, vp, sz, vp, sz, vp, vp, C.POINTER(sz)]),
+        "clsimhip_series_relabel_workspace_bytes": (sz, [sz, sz, sz]),
+        "clsimhip_mcpe_series_relabel_device": (i32, [i32, vp, vp, vp, sz, vp, sz, vp, vp, vp, vp, sz, vp]),
+        "clsimhip_frame_photons_relabel_device": (i32, [i32, vp, vp, vp, sz, vp, sz, vp, vp, vp, vp, sz, vp]),
+        "clsimhip_mcpe_parents_relabel_host": (i32, [vp, vp, sz, vp, sz, vp, vp, C.POINTER(sz)]),
         "clsimhip_tabulator_write_fits_file": (i32, [vp, C.c_char_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double), sz]),
     }
     for name in SYMBOLS:
         # (A/B measurements load an older build through CLSIMHIP_LIB: it may lack the entries of the run-time compiled kernel, of the event
-        # statistics stage, of the photon hits stage and of the two frame stores, which bench.py does not call)
+        # statistics stage, of the photon hits stage, of the frame stores, of the muon slicer and of the relabel stage, which bench.py does not call)
         newer = (name in ("clsimhip_baked_info", "clsimhip_baked_compile", "clsimhip_baked_set_compiler_library") or "event_statistics" in name
                  or "photon_hit" in name or "mcpe_series_union" in name or "mcpe_series_split" in name or "mcpe_frame_store" in name
                  or "frame_photons_union" in name or "frame_photons_split" in name or "frame_photon_store" in name
-                 or "pmt_hits_union" in name or "pmt_hits_split" in name or "pmt_hit_store" in name)
+                 or "pmt_hits_union" in name or "pmt_hits_split" in name or "pmt_hit_store" in name or "relabel" in name or name == "clsimhip_slice_muons")
         if newer and LIB_PATH != DEFAULT_LIB_PATH and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)          # AttributeError if the library lacks a declared symbol

@@ -600,6 +600,47 @@ class MCPEFrameStore:
         return (take(d_merged, MCPE_MERGED_DTYPE, n_merged), take(d_merged_series, MCPE_SERIES_DTYPE, n_series), take(d_parents, MCPE_PARENT_DTYPE, n_parents),
                 take(d_ranges, MCPE_PARENT_RANGE_DTYPE, n_series))
 
+    def drain_relabelled(self, last_frame, relabeler, window=None, generator=None):
+        """The frames <= last_frame with every slice's records under its muon's identifier: drain -> relabel (-> merge) -- on a device
+        store one stream carries all of it and only the download waits.  relabeler: a SeriesRelabeler.  window=None: (records,
+        series); else (merged, merged_series, parents, parent_ranges) as DrainMerged returns them, with `generator` for a device store.
+        A TIE_OVERFLOW of the relabel stage raises: nothing would have been delivered."""
+        if self.device is None:
+            records, series, counters = relabeler.mcpe_series_host(*self.Drain(last_frame))
+            if counters["tie_overflow"]:
+                raise I3CLSimStepToPhotonConverter_exception("series relabel: TIE_OVERFLOW = %d, nothing is delivered" % counters["tie_overflow"])
+            return (records, series) if window is None else MCPEGenerator.MergeHost(records, series, window)
+        if window is not None and generator is None:
+            raise ValueError("drain_relabelled with a window on a device store needs the MCPEGenerator whose series these are (MergeDevice is its method)")
+        import torch
+        dev = torch.device("cuda", int(self.device))
+        capacity = max(self.Size(last_frame)[0], 1)
+        sizes = (MCPE_DTYPE.itemsize, MCPE_SERIES_DTYPE.itemsize, MCPE_DTYPE.itemsize, MCPE_SERIES_DTYPE.itemsize, MCPE_MERGED_DTYPE.itemsize,
+                 MCPE_SERIES_DTYPE.itemsize, MCPE_PARENT_DTYPE.itemsize, MCPE_PARENT_RANGE_DTYPE.itemsize)
+        d_records, d_series, d_new, d_new_series, d_merged, d_merged_series, d_parents, d_ranges = (
+            torch.zeros(capacity * s, dtype=torch.uint8, device=dev) for s in sizes)
+        d_counts, d_new_counts, d_merged_counts = (torch.zeros(k, dtype=torch.int32, device=dev) for k in (5, 5, 2))
+        ws_bytes = max(relabeler.workspace_bytes(capacity, MCPE_DTYPE.itemsize), MCPEGenerator.MergeWorkspaceBytes(capacity))
+        d_ws = torch.zeros(ws_bytes, dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        self.DrainDevice(last_frame, d_records.data_ptr(), d_series.data_ptr(), d_counts.data_ptr(), capacity, stream=stream)
+        relabeler.mcpe_series_device(d_records.data_ptr(), d_series.data_ptr(), d_counts.data_ptr(), capacity, d_new.data_ptr(), d_new_series.data_ptr(),
+                                     d_new_counts.data_ptr(), d_ws.data_ptr(), ws_bytes, device=int(self.device), stream=stream)
+        if window is not None:
+            generator.MergeDevice(d_new.data_ptr(), d_new_series.data_ptr(), d_new_counts.data_ptr(), capacity, window, d_merged.data_ptr(),
+                                  d_merged_series.data_ptr(), d_parents.data_ptr(), d_ranges.data_ptr(), d_merged_counts.data_ptr(), d_ws.data_ptr(), ws_bytes,
+                                  device=int(self.device), stream=stream)
+        counts = d_new_counts.cpu().numpy().view(np.uint32)
+        if counts[4]:
+            raise I3CLSimStepToPhotonConverter_exception("series relabel: TIE_OVERFLOW = %d, nothing is delivered" % int(counts[4]))
+        n, n_series = int(counts[0]), int(counts[1])
+        take = lambda t, dtype, k: t.cpu().numpy()[:k * dtype.itemsize].copy().view(dtype).reshape(-1)
+        if window is None:
+            return take(d_new, MCPE_DTYPE, n), take(d_new_series, MCPE_SERIES_DTYPE, n_series)
+        n_merged, n_parents = (int(c) for c in d_merged_counts.cpu().numpy())
+        return (take(d_merged, MCPE_MERGED_DTYPE, n_merged), take(d_merged_series, MCPE_SERIES_DTYPE, n_series), take(d_parents, MCPE_PARENT_DTYPE, n_parents),
+                take(d_ranges, MCPE_PARENT_RANGE_DTYPE, n_series))
+
 
 # Multi-PMT hit generator (include/clsimhip.h): clsimhip_pmt_type, clsimhip_pmt, clsimhip_pmt_module and clsimhip_pmt_hit
 PMT_TYPE_DTYPE = np.dtype([("sphereRadius", "<f8"), ("firstPMT", "<i4"), ("numPMTs", "<i4"), ("glassGelSurvival", "<i4"), ("reserved", "<i4")])
@@ -1996,3 +2037,91 @@ def FlasherTimeProfile(pulseWidthNs):
     d, c = np.zeros(240, dtype=np.float32), np.zeros(240, dtype=np.float32)
     _check(_lib.load().clsimhip_flasher_time_profile(float(pulseWidthNs), d.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p)))
     return d, c
+
+
+# ---- muon slicer and series relabel (include/clsimhip.h: I3MuonSlicer and I3MuonSliceRemoverAndPulseRelabeler) ----
+TREE_PARTICLE_DTYPE = np.dtype([("particle", PARTICLE_DTYPE), ("speed", "<f8"), ("parent", "<i4"), ("flags", "<u4")])
+MMC_TRACK_DTYPE = np.dtype([("identifier", "<u4"), ("reserved", "<u4"), ("Ei", "<f8"), ("Ef", "<f8"), ("ti", "<f8"), ("tf", "<f8")])
+RELABEL_DTYPE = np.dtype([("from", "<u4"), ("to", "<u4")])
+assert TREE_PARTICLE_DTYPE.itemsize == 104 and MMC_TRACK_DTYPE.itemsize == 40 and RELABEL_DTYPE.itemsize == 8
+TREE_DARK = 1
+SLICER_COUNTERS = ("off_track", "energy_reset", "stops_before_start", "zero_duration", "long_slice")
+RELABEL_COUNTERS = ("relabelled", "tie_overflow")
+RELABEL_COUNTS = ("records", "series", "relabelled", "reserved", "tie_overflow")
+
+
+def slice_muons(tree, tracks, first_slice_identifier):
+    """(tree, relabel, counters): I3MuonSlicer on a flattened tree.  tree: TREE_PARTICLE_DTYPE in depth-first pre-order; tracks:
+    MMC_TRACK_DTYPE; the k-th slice of the output takes identifier first_slice_identifier + k.  relabel: RELABEL_DTYPE, (slice ->
+    muon), ascending in `from`; counters = {name: count} (SLICER_COUNTERS).  EnqueueLightSources takes the output's `particle` field
+    of the nodes without TREE_DARK."""
+    tree = np.ascontiguousarray(tree, dtype=TREE_PARTICLE_DTYPE)
+    tracks = np.ascontiguousarray(tracks, dtype=MMC_TRACK_DTYPE)
+    lib = _lib.load()
+    n_out, n_relabel, counters = C.c_size_t(), C.c_size_t(), np.zeros(5, dtype=np.uint64)
+    out, relabel = np.zeros(0, dtype=TREE_PARTICLE_DTYPE), np.zeros(0, dtype=RELABEL_DTYPE)
+    for _ in range(2):                  # sizes first, as with clsimhip_ppc_enqueue
+        _check(lib.clsimhip_slice_muons(tree.ctypes.data_as(C.c_void_p), len(tree), tracks.ctypes.data_as(C.c_void_p), len(tracks), int(first_slice_identifier),
+                                        out.ctypes.data_as(C.c_void_p), len(out), C.byref(n_out), relabel.ctypes.data_as(C.c_void_p), len(relabel),
+                                        C.byref(n_relabel), counters.ctypes.data_as(C.c_void_p)))
+        if n_out.value <= len(out) and n_relabel.value <= len(relabel):
+            break
+        out, relabel = np.zeros(n_out.value, dtype=TREE_PARTICLE_DTYPE), np.zeros(n_relabel.value, dtype=RELABEL_DTYPE)
+    return out[:n_out.value], relabel[:n_relabel.value], dict(zip(SLICER_COUNTERS, (int(c) for c in counters)))
+
+
+class SeriesRelabeler:
+    """RELABEL(X, map) of include/clsimhip.h for the two series forms and the merging stage's parent table.  map: RELABEL_DTYPE (or
+    pairs), strictly ascending in `from`, no `to` among the `from`s -- slice_muons' relabel table."""
+
+    def __init__(self, map):
+        self.map = np.ascontiguousarray(map, dtype=RELABEL_DTYPE).reshape(-1)
+        self._lib = _lib.load()
+
+    def _host(self, fn, records, series, dtype):
+        records = np.ascontiguousarray(records, dtype=dtype)
+        series = np.ascontiguousarray(series, dtype=MCPE_SERIES_DTYPE)
+        out, counters, kept = np.zeros(len(records), dtype=dtype), np.zeros(2, dtype=np.uint64), C.c_size_t()
+        _check(fn(records.ctypes.data_as(C.c_void_p), len(records), series.ctypes.data_as(C.c_void_p), len(series), self.map.ctypes.data_as(C.c_void_p),
+                  len(self.map), out.ctypes.data_as(C.c_void_p), counters.ctypes.data_as(C.c_void_p), C.byref(kept)))
+        counters = dict(zip(RELABEL_COUNTERS, (int(c) for c in counters)))
+        return (out, series.copy(), counters) if not counters["tie_overflow"] else (out[:0], series[:0].copy(), counters)
+
+    def mcpe_series_host(self, records, series):
+        """(records, series, counters): the host twin on MCPE_DTYPE records; nothing is delivered after a TIE_OVERFLOW"""
+        return self._host(self._lib.clsimhip_mcpe_series_relabel_host, records, series, MCPE_DTYPE)
+
+    def frame_photons_host(self, records, series):
+        """(records, series, counters): the host twin on FRAME_PHOTON_DTYPE records"""
+        return self._host(self._lib.clsimhip_frame_photons_relabel_host, records, series, FRAME_PHOTON_DTYPE)
+
+    def workspace_bytes(self, capacity, record_bytes):
+        return int(self._lib.clsimhip_series_relabel_workspace_bytes(int(capacity), len(self.map), int(record_bytes)))
+
+    def _device(self, fn, d_records, d_series, d_counts, capacity, d_out_records, d_out_series, d_out_counts, d_workspace, workspace_bytes, device, stream):
+        _check(fn(int(device), C.c_void_p(d_records), C.c_void_p(d_series), C.c_void_p(d_counts), int(capacity), self.map.ctypes.data_as(C.c_void_p), len(self.map),
+                  C.c_void_p(d_out_records), C.c_void_p(d_out_series), C.c_void_p(d_out_counts), C.c_void_p(d_workspace), int(workspace_bytes), C.c_void_p(stream)))
+
+    def mcpe_series_device(self, d_records, d_series, d_counts, capacity, d_out_records, d_out_series, d_out_counts, d_workspace, workspace_bytes,
+                           device=0, stream=0):
+        """the kernels on a device-resident series form (addresses; pairs with MakeSeriesDevice, a union or a store's DrainDevice);
+        d_out_counts: five uint32 (RELABEL_COUNTS); d_workspace: workspace_bytes(capacity, 16) bytes; asynchronous on `stream`"""
+        self._device(self._lib.clsimhip_mcpe_series_relabel_device, d_records, d_series, d_counts, capacity, d_out_records, d_out_series, d_out_counts,
+                     d_workspace, workspace_bytes, device, stream)
+
+    def frame_photons_device(self, d_records, d_series, d_counts, capacity, d_out_records, d_out_series, d_out_counts, d_workspace, workspace_bytes,
+                             device=0, stream=0):
+        """the same on frame photons (48-byte records; workspace_bytes(capacity, 48))"""
+        self._device(self._lib.clsimhip_frame_photons_relabel_device, d_records, d_series, d_counts, capacity, d_out_records, d_out_series, d_out_counts,
+                     d_workspace, workspace_bytes, device, stream)
+
+    def parents_host(self, parents, ranges):
+        """(parents, ranges): the merging stage's parent table under the map -- relabelled, sorted by (id, index) per series, duplicates
+        dropped.  On the device the table comes from merging BEHIND the relabel stage instead."""
+        parents = np.ascontiguousarray(parents, dtype=MCPE_PARENT_DTYPE)
+        ranges = np.ascontiguousarray(ranges, dtype=MCPE_PARENT_RANGE_DTYPE)
+        out, out_ranges, n = np.zeros(len(parents), dtype=MCPE_PARENT_DTYPE), np.zeros(len(ranges), dtype=MCPE_PARENT_RANGE_DTYPE), C.c_size_t()
+        _check(self._lib.clsimhip_mcpe_parents_relabel_host(parents.ctypes.data_as(C.c_void_p), ranges.ctypes.data_as(C.c_void_p), len(ranges),
+                                                            self.map.ctypes.data_as(C.c_void_p), len(self.map), out.ctypes.data_as(C.c_void_p),
+                                                            out_ranges.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return out[:n.value], out_ranges

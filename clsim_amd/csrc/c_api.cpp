@@ -24,6 +24,8 @@
 #include "pmt_series.h"
 #include "photon_hits.h"
 #include "pmt_photon_hits.h"
+#include "muon_slicer.h"
+#include "series_relabel.h"
 
 using namespace clsimhip;
 
@@ -1176,6 +1178,57 @@ int clsimhip_mcpe_frame_store_drain_host(clsimhip_mcpe_frame_store *s, uint32_t 
 int clsimhip_mcpe_frame_store_size(clsimhip_mcpe_frame_store *s, uint32_t last_frame, size_t *n, size_t *n_series)
 {
     return guarded(nullptr, [&] { need(s, "store"); s->impl->size(last_frame, n, n_series); });
+}
+
+// ---- Muon slicer (muon_slicer.h) ----
+int clsimhip_slice_muons(const clsimhip_tree_particle *tree, size_t n, const clsimhip_mmc_track *tracks, size_t n_tracks,
+                         uint32_t first_slice_identifier, clsimhip_tree_particle *out, size_t capacity, size_t *n_out,
+                         clsimhip_relabel *relabel, size_t relabel_capacity, size_t *n_relabel, uint64_t counters[5])
+{
+    return guarded(nullptr, [&] {
+        slice_muons(tree, n, tracks, n_tracks, first_slice_identifier, out, capacity, n_out, relabel, relabel_capacity, n_relabel, counters);
+    });
+}
+
+// ---- Series relabel (series_relabel.h) ----
+int clsimhip_mcpe_series_relabel_host(const clsimhip_mcpe *records, size_t n, const clsimhip_mcpe_series *series, size_t n_series,
+                                      const clsimhip_relabel *map, size_t n_map, clsimhip_mcpe *out_records, uint64_t counters[2], size_t *n_kept)
+{
+    return guarded(nullptr, [&] { mcpe_series_relabel_host(records, n, series, n_series, map, n_map, out_records, counters, n_kept); });
+}
+int clsimhip_frame_photons_relabel_host(const clsimhip_frame_photon *records, size_t n, const clsimhip_mcpe_series *series, size_t n_series,
+                                        const clsimhip_relabel *map, size_t n_map, clsimhip_frame_photon *out_records, uint64_t counters[2],
+                                        size_t *n_kept)
+{
+    return guarded(nullptr, [&] { frame_photons_relabel_host(records, n, series, n_series, map, n_map, out_records, counters, n_kept); });
+}
+size_t clsimhip_series_relabel_workspace_bytes(size_t capacity, size_t n_map, size_t record_bytes)
+{
+    return series_relabel_workspace_bytes(capacity, n_map, record_bytes);
+}
+int clsimhip_mcpe_series_relabel_device(int device, const void *d_records, const void *d_series, const void *d_counts, size_t capacity,
+                                        const clsimhip_relabel *map, size_t n_map, void *d_out_records, void *d_out_series,
+                                        void *d_out_counts, void *d_workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return guarded(nullptr, [&] {
+        mcpe_series_relabel_device(device, d_records, d_series, d_counts, capacity, map, n_map, d_out_records, d_out_series, d_out_counts, d_workspace,
+                                   workspace_bytes, static_cast<hipStream_t>(hip_stream));
+    });
+}
+int clsimhip_frame_photons_relabel_device(int device, const void *d_records, const void *d_series, const void *d_counts, size_t capacity,
+                                          const clsimhip_relabel *map, size_t n_map, void *d_out_records, void *d_out_series,
+                                          void *d_out_counts, void *d_workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return guarded(nullptr, [&] {
+        frame_photons_relabel_device(device, d_records, d_series, d_counts, capacity, map, n_map, d_out_records, d_out_series, d_out_counts, d_workspace,
+                                     workspace_bytes, static_cast<hipStream_t>(hip_stream));
+    });
+}
+int clsimhip_mcpe_parents_relabel_host(const clsimhip_mcpe_parent *parents, const clsimhip_mcpe_parent_range *ranges, size_t n_series,
+                                       const clsimhip_relabel *map, size_t n_map, clsimhip_mcpe_parent *out,
+                                       clsimhip_mcpe_parent_range *out_ranges, size_t *n_out)
+{
+    return guarded(nullptr, [&] { mcpe_parents_relabel_host(parents, ranges, n_series, map, n_map, out, out_ranges, n_out); });
 }
 
 // ---- Multi-PMT hit generator (pmt_hits.h) ----

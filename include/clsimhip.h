@@ -1730,6 +1730,104 @@ int clsimhip_pmt_photon_hits_device(clsimhip_pmt_generator *g, int device, const
                                     size_t capacity, void *d_out, void *d_out_series, void *d_counts, void *d_workspace, size_t workspace_bytes,
                                     void *hip_stream);
 
+/* ---- Muon slicer: a muon with a length becomes slices between its stochastic losses ------------------------------------------
+ * The reference's standard chain cuts every muon that has a length into slices between its daughters (I3MuonSlicer,
+ * private/clsim/util/I3MuonSlicer.cxx:182-493 and the primaries loop :531-555); each slice carries the energy the muon still has
+ * there, and slices and cascades are propagated as light sources of their own.  Here: sequential binary64 host code on a flattened
+ * tree, every formula in the reference's operation order (dEdt_calc, dEdt_max with its one log, their min, the running energy and
+ * time, the reset to 0 at :319-322), in this library's units (m, ns, GeV; c = 0.299792458 m/ns).
+ * INPUT: the tree in depth-first pre-order -- a node's children follow it, in the reference's sibling order; parent < own index.
+ * OUTPUT: the reference's append order, pre-order as well.  A sliced muon comes first, with CLSIMHIP_TREE_DARK set; then, per
+ *     daughter, the slice in front of it (if its length >= 0.1 mm), the daughter, and the daughter's own sliced subtree; the slice
+ *     behind the last daughter comes last.  A slice copies the muon's type, shape, flags as they were on input, direction and speed,
+ *     and takes identifier = first_slice_identifier + k, k its position among the slices in output order; `relabel` receives
+ *     (that identifier -> the muon's identifier), strictly ascending in `from` by construction.
+ * The paths without slices are the reference's: a muon that is not in `tracks`, or whose Ei / Ef are invalid, takes the particle's
+ *     own values (:257-268); the early returns at :421-434 and :441-444; tf < ti and tf == ti only darken the muon; a muon without a
+ *     length, and any other particle, is copied and recursed into.  A daughter more than 1 mm off the track is appended and skipped
+ *     (its subtree with it, :326-333); a daughter with a NaN time is dropped (:335).
+ * The reference's log_fatal conditions are CLSIMHIP_ERR_ARGUMENT, with text that names the first offending node, and nothing is
+ *     written: a muon or a type-0 daughter below a muon with a length; NaN speed, energy or time of such a muon; daughters not
+ *     ascending in time (the reference's own check never clears its first-iteration flag and so only ever refuses NaN times; here it
+ *     is what its text says: a NaN time of the first daughter, or a time below the predecessor's); Ei <= 0 with daughters; an
+ *     identifier twice in `tracks`.  Also refused: parent >= index, a slice identifier that equals an input identifier, slice
+ *     identifiers that would wrap.
+ * counters[5] (may be NULL): what the reference logs as error or warning -- OFF_TRACK, ENERGY_RESET, STOPS_BEFORE_START,
+ *     ZERO_DURATION, LONG_SLICE (> 1 km).
+ * *n_out and *n_relabel are what is needed; at most the capacities are written, as clsimhip_ppc_enqueue does it.  A caller passes
+ * clsimhip_ppc_enqueue the output nodes without CLSIMHIP_TREE_DARK.  The block under TRY_TO_CORRECT_MMC is compiled out upstream
+ * and is not here.  Host only, no GPU is touched. */
+#define CLSIMHIP_TREE_DARK 1u                 /* I3Particle::Dark */
+#define CLSIMHIP_SLICER_OFF_TRACK 0           /* index into the five counters */
+#define CLSIMHIP_SLICER_ENERGY_RESET 1
+#define CLSIMHIP_SLICER_STOPS_BEFORE_START 2
+#define CLSIMHIP_SLICER_ZERO_DURATION 3
+#define CLSIMHIP_SLICER_LONG_SLICE 4
+typedef struct {
+    clsimhip_particle particle;               /* as clsimhip_ppc_enqueue takes it */
+    double speed;                             /* [m/ns] */
+    int32_t parent;                           /* index of the parent in the same array, -1: a primary; parent < own index */
+    uint32_t flags;                           /* CLSIMHIP_TREE_* */
+} clsimhip_tree_particle;                     /* 104 bytes */
+typedef struct { uint32_t identifier, reserved; double Ei, Ef, ti, tf; } clsimhip_mmc_track;   /* 40 bytes */
+typedef struct { uint32_t from, to; } clsimhip_relabel;                                        /* 8 bytes */
+typedef char clsimhip_tree_particle_is_104_bytes[sizeof(clsimhip_tree_particle) == 104 ? 1 : -1];
+typedef char clsimhip_mmc_track_is_40_bytes[sizeof(clsimhip_mmc_track) == 40 ? 1 : -1];
+typedef char clsimhip_relabel_is_8_bytes[sizeof(clsimhip_relabel) == 8 ? 1 : -1];
+int clsimhip_slice_muons(const clsimhip_tree_particle *tree, size_t n, const clsimhip_mmc_track *tracks, size_t n_tracks,
+                         uint32_t first_slice_identifier, clsimhip_tree_particle *out, size_t capacity, size_t *n_out,
+                         clsimhip_relabel *relabel, size_t relabel_capacity, size_t *n_relabel, uint64_t counters[5]);
+
+/* ---- Series relabel: records take their muon's identifier, and the series form's order is restored -------------------------
+ * Behind its hit makers the reference replaces every slice's identifier, in every MCPE and every photon, by that of the muon the
+ * slice was cut from (I3MuonSliceRemoverAndPulseRelabeler, private/clsim/util/I3MuonSliceRemoverAndPulseRelabeler.cxx:230-400).
+ * The series forms here end their key in the identifier, so the order has to be made again:
+ * RELABEL(X, map) for a series form X of MCPEs or of frame photons: every record whose identifier is a `from` of the map takes that
+ *     entry's `to`; all other bytes stay; the series table is unchanged; the records of every series are put back into the form's
+ *     order.  Only runs of records equal in (series entry, tkey) can be out of order.  A run is DISTURBED when its new identifiers
+ *     descend somewhere.  Undisturbed runs are copied, whatever their length.  A disturbed run is sorted on the rest of the key:
+ *     `identifier` for MCPEs; `identifier, h, w0 ... w7` for frame photons, h as the frame photon contract defines it.  A disturbed
+ *     run of more than 2 048 records is counted member by member as TIE_OVERFLOW, and the call then delivers nothing (records =
+ *     series = 0): loud, as for the frame photon stage.
+ * The map is strictly ascending in `from`, and no `to` may equal any `from` (the reference's own sanity check, :320-332); a map that
+ * breaks either rule is CLSIMHIP_ERR_ARGUMENT.  An empty map gives a copy.  Equal keys are equal bytes for both record types, so the
+ * result is a function of the input: the same bytes from the host twins and the kernels.
+ * The host twins (a walk over the runs, std::stable_sort; host only, no GPU is touched): a malformed input is CLSIMHIP_ERR_ARGUMENT.
+ * out_records holds n entries; counters[2] (may be NULL): RELABELLED, TIE_OVERFLOW; *n_kept: n, or 0 after a TIE_OVERFLOW. */
+#define CLSIMHIP_RELABEL_RELABELLED 0         /* index into the two counters */
+#define CLSIMHIP_RELABEL_TIE_OVERFLOW 1
+int clsimhip_mcpe_series_relabel_host(const clsimhip_mcpe *records, size_t n, const clsimhip_mcpe_series *series, size_t n_series,
+                                      const clsimhip_relabel *map, size_t n_map, clsimhip_mcpe *out_records, uint64_t counters[2], size_t *n_kept);
+int clsimhip_frame_photons_relabel_host(const clsimhip_frame_photon *records, size_t n, const clsimhip_mcpe_series *series, size_t n_series,
+                                        const clsimhip_relabel *map, size_t n_map, clsimhip_frame_photon *out_records, uint64_t counters[2],
+                                        size_t *n_kept);
+/* bytes of device memory the kernels need beside their input and output (the map's copy included); record_bytes: 16 (MCPEs) or 48
+ * (frame photons), anything else: 0 */
+size_t clsimhip_series_relabel_workspace_bytes(size_t capacity, size_t n_map, size_t record_bytes);
+/* The kernels, on series that live in HBM.  The input is read as clsimhip_mcpe_merge_device reads it: min(counts[0], capacity)
+ * records, min(counts[1], capacity) series; it is taken as a series form and not checked again.  d_out_records and d_out_series:
+ * `capacity` entries each; d_out_series receives a copy of the table, so the output triple is complete; d_out_counts: five uint32 --
+ * records, series, RELABELLED, 0, TIE_OVERFLOW; the first two follow the series stage's layout, so the output chains unchanged into
+ * the merge, a union, a split and a store's add_device.  The map is host memory; it is checked and copied before the call returns, as
+ * the series stage treats its particle table.  Whatever bytes the input holds, nothing is written beyond a capacity and every loop
+ * is bounded by one.  The output must not overlap the input (CLSIMHIP_ERR_ARGUMENT).  Records, tables and d_workspace
+ * (clsimhip_series_relabel_workspace_bytes bytes) are 16-byte aligned, the counts 4-byte; capacity is at most 2^31.  Asynchronous on
+ * hip_stream (NULL = default stream); nothing waits for the device. */
+int clsimhip_mcpe_series_relabel_device(int device, const void *d_records, const void *d_series, const void *d_counts, size_t capacity,
+                                        const clsimhip_relabel *map, size_t n_map, void *d_out_records, void *d_out_series,
+                                        void *d_out_counts, void *d_workspace, size_t workspace_bytes, void *hip_stream);
+int clsimhip_frame_photons_relabel_device(int device, const void *d_records, const void *d_series, const void *d_counts, size_t capacity,
+                                          const clsimhip_relabel *map, size_t n_map, void *d_out_records, void *d_out_series,
+                                          void *d_out_counts, void *d_workspace, size_t workspace_bytes, void *hip_stream);
+/* The merging stage's parent table under the map, host only: per range the identifiers are replaced, the entries sorted by
+ * (identifier, index), duplicates dropped and the ranges rebuilt (the ranges must lie end to end; out holds as many entries as the
+ * input, out_ranges n_series).  The reference's version of this step tests the wrong way round (:369-370) and dereferences end() for
+ * every particle that is not a slice; that defect is not restated.  On the device there is no such stage: merging ignores particles,
+ * so the parent table comes from running clsimhip_mcpe_merge_device BEHIND the relabel stage. */
+int clsimhip_mcpe_parents_relabel_host(const clsimhip_mcpe_parent *parents, const clsimhip_mcpe_parent_range *ranges, size_t n_series,
+                                       const clsimhip_relabel *map, size_t n_map, clsimhip_mcpe_parent *out,
+                                       clsimhip_mcpe_parent_range *out_ranges, size_t *n_out);
+
 #ifdef __cplusplus
 }
 #endif
