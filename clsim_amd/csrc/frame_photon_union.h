@@ -1,15 +1,16 @@
 // Frame photon store: the union of two series forms of frame photons, the split of one at a frame bound, and the store that folds
-// bunches into accumulated state and gives up finished frames (include/clsimhip.h: "Frame photon store").  The definition lives here
-// ONCE, as functions both the host twins (frame_photon_union.cpp) and the HIP kernels (frame_photon_union_kernel.hip) compile.  It
-// stands where the reference's client module files every result's photons into a frame cache that lives across bunches and commits
-// the oldest frames no bunch in flight can still touch
+// bunches into accumulated state and gives up finished frames (include/clsimhip.h: "Frame photon store").  The stage itself is stated
+// once for every record type (series_union.h, series_union_host.h, series_union_device.hip.h); what is the frame photon's own lives
+// here ONCE, as functions both the host twins (frame_photon_union.cpp) and the HIP kernels (frame_photon_union_kernel.hip) compile,
+// with the traits type FramePhotonUnion that hands them to the shared statement.  The stage stands where the reference's client
+// module files every result's photons into a frame cache that lives across bunches and commits the oldest frames no bunch in flight
+// can still touch
 //   I3CLSimClientModule::AddPhotonsToFrames   private/clsim/I3CLSimClientModule.cxx:359-439  ((*frame->photons)[ModuleKey] :407-415)
 //   I3CLSimClientModule::FlushFrameCache      :686-758  (framesForBunches_, lastPendingFrame: a prefix of the cache)
-// The table rules, the DOM code, the word comparison, the bisections and the sticky counters are the MCPE frame store's and are taken
-// from mcpe_union.h as they stand.  What is this stage's own is the key: 14 words, the last nine of them the record's content, so
-// that records equal in the key are equal bytes and the union is a function of the multiset of records.  The comparison is the full
-// key everywhere: the frame photons stage's bound on runs of content ties (frame_photons.h: kFramePhotonsTieBound) has no
-// counterpart here.
+// The table is the MCPE frame store's and its rules are taken from mcpe_union.h as they stand.  What is this stage's own is the key:
+// 14 words, the last nine of them the record's content, so that records equal in the key are equal bytes and the union is a function
+// of the multiset of records.  The comparison is the full key everywhere: the frame photons stage's bound on runs of content ties
+// (frame_photons.h: kFramePhotonsTieBound) has no counterpart here.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -58,8 +59,6 @@ UNION_HD FramePhotonKey frame_photon_union_make_key(uint32_t frame, const uint32
     return k;
 }
 
-UNION_HD bool frame_photon_union_key_less(const FramePhotonKey &a, const FramePhotonKey &b) { return union_words_less(a.w, b.w, kFramePhotonKeyWords); }
-
 UNION_HD const uint32_t *frame_photon_union_words(const clsimhip_frame_photon *records, size_t i)
 {
     return reinterpret_cast<const uint32_t *>(records + i);
@@ -84,6 +83,32 @@ UNION_HD bool frame_photon_union_record_ok(const clsimhip_frame_photon *records,
     return true;
 }
 
+// what the shared statement of the stage (series_union.h) takes from this header
+struct FramePhotonUnion {
+    using Record = clsimhip_frame_photon;
+    using Entry = clsimhip_mcpe_series;
+    using Key = FramePhotonKey;
+    static constexpr uint32_t kRecordWords = kFramePhotonRecordWords, kEntryWords = 4u, kKeyWords = kFramePhotonKeyWords, kChannelWords = 2u /* frame, DOM code */,
+                              kAlign = 16u;
+    static constexpr const char *kStore = "frame photon store", *kName = "frame photon";
+    static constexpr const char *kEntryRule = McpeUnion::kEntryRule;
+    static constexpr const char *kRecordRule =
+        "every record must lie in an entry, carry its string_id and om_id, and not descend in (time key, identifier, h, w0 ... w7) behind its predecessor";
+    static UNION_HD Key key_of(uint32_t frame, const Record *records, size_t i) { return frame_photon_union_make_key(frame, frame_photon_union_words(records, i)); }
+    static UNION_HD bool entry_ok(const Entry *series, uint32_t n_series, uint32_t n, uint32_t s) { return union_entry_ok(series, n_series, n, s); }
+    static UNION_HD bool record_ok(const Record *records, const Entry *series, uint32_t n_series, uint32_t i, uint32_t *frame)
+    {
+        return frame_photon_union_record_ok(records, series, n_series, i, frame);
+    }
+    static void open_entry(Entry &s, uint32_t frame, const Record &r)
+    {
+        s.frame = frame;
+        s.string_id = r.string_id; s.om_id = r.om_id;
+        s.count = 0u;
+    }
+};
+static_assert(union_traits_ok<FramePhotonUnion>(), "");
+
 // ---- the host twins (frame_photon_union.cpp: host only, no HIP call); they throw Error (CLSIMHIP_ERR_ARGUMENT) ----
 void frame_photons_union_host(const clsimhip_frame_photon *a_records, size_t n_a, const clsimhip_mcpe_series *a_series, size_t n_series_a,
                               const clsimhip_frame_photon *b_records, size_t n_b, const clsimhip_mcpe_series *b_series, size_t n_series_b,
@@ -95,41 +120,8 @@ void frame_photons_split_host(const clsimhip_frame_photon *records, size_t n, co
 void frame_photons_form_check(const char *what, const clsimhip_frame_photon *records, size_t n, const clsimhip_mcpe_series *series, size_t n_series);
 
 // ---- the device stage (frame_photon_union_kernel.hip) ----
-// The header is the MCPE union's (mcpe_union.h: UnionHeader beside mcpe_series.h's SH_KEPT and SH_SERIES), so that
+// The header is the MCPE union's (series_union.h: UnionHeader beside mcpe_series.h's SH_KEPT and SH_SERIES), so that
 // launch_series_tile_scan runs unchanged on it.
-struct FramePhotonUnionDeviceArgs {
-    const clsimhip_frame_photon *a_records;
-    const clsimhip_mcpe_series *a_series;
-    const uint32_t *a_counts;               // records = min([0], capacity_a), series = min([1], capacity_a)
-    const clsimhip_frame_photon *b_records;
-    const clsimhip_mcpe_series *b_series;
-    const uint32_t *b_counts;
-    uint32_t capacity_a, capacity_b, out_capacity;
-    uint32_t *header;                       // kSeriesHeaderWords
-    uint32_t *tile_counts;                  // heads per output tile, scanned in place
-    uint32_t *partition;                    // per output tile boundary: records of A in front of it
-    uint32_t *a_frames, *b_frames;          // per input record: its entry's frame
-    uint32_t *out_frames;                   // per output record
-    clsimhip_frame_photon *out_records;
-    clsimhip_mcpe_series *out_series;
-    uint32_t *out_counts;                   // five
-};
-
-struct FramePhotonSplitDeviceArgs {
-    const clsimhip_frame_photon *records;
-    const clsimhip_mcpe_series *series;
-    const uint32_t *counts;
-    uint32_t capacity, last_frame;
-    const uint32_t *blocked;                // (may be null) five words: any nonzero -> nothing is drained
-    clsimhip_frame_photon *head_records;    // (null with head_series: the head is dropped, the store's own use behind a download)
-    clsimhip_mcpe_series *head_series;
-    uint32_t *head_counts;                  // five: records, series, 0, 0, overflow
-    uint32_t head_capacity;
-    clsimhip_frame_photon *tail_records;
-    clsimhip_mcpe_series *tail_series;
-    uint32_t *tail_counts;                  // five: records, series, 0, 0, 0
-};
-
 size_t frame_photons_union_workspace_bytes(size_t capacity_a, size_t capacity_b);
 void frame_photons_union_device(int device, const void *d_a_records, const void *d_a_series, const void *d_a_counts, size_t capacity_a, const void *d_b_records,
                                 const void *d_b_series, const void *d_b_counts, size_t capacity_b, void *d_out_records, void *d_out_series, void *d_out_counts,
@@ -138,17 +130,8 @@ void frame_photons_split_device(int device, const void *d_records, const void *d
                                 void *d_head_records, void *d_head_series, void *d_head_counts, size_t head_capacity, void *d_tail_records, void *d_tail_series,
                                 void *d_tail_counts, size_t tail_capacity, hipStream_t stream);
 
-// ---- the store: FrameStore's behaviour (mcpe_union.h) on 48-byte records; the sticky counters are FrameStoreSticky ----
-class FramePhotonStore {
-public:
-    virtual ~FramePhotonStore() = default;
-    virtual bool on_device() const = 0;
-    virtual void add_host(const clsimhip_frame_photon *records, size_t n, const clsimhip_mcpe_series *series, size_t n_series) = 0;
-    virtual void add_device(const void *d_records, const void *d_series, const void *d_series_counts, size_t capacity, hipStream_t stream) = 0;
-    virtual void drain_device(uint32_t last_frame, void *d_records, void *d_series, void *d_counts, size_t capacity, hipStream_t stream) = 0;
-    virtual void drain_host(uint32_t last_frame, clsimhip_frame_photon *records, clsimhip_mcpe_series *series, size_t capacity, size_t *n, size_t *n_series) = 0;
-    virtual void size(uint32_t last_frame, size_t *n, size_t *n_series) = 0;
-};
+// ---- the store: the sticky counters are FrameStoreSticky ----
+using FramePhotonStore = FrameStoreOf<FramePhotonUnion>;
 std::unique_ptr<FramePhotonStore> make_host_frame_photon_store(size_t capacity);                    // frame_photon_union.cpp
 std::unique_ptr<FramePhotonStore> make_device_frame_photon_store(int device, size_t capacity);      // frame_photon_union_kernel.hip
 

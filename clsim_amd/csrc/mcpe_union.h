@@ -1,8 +1,10 @@
 // MCPE frame store: the union of two series-form inputs, the split of one at a frame bound, and the store that folds bunches into
-// accumulated state and gives up finished frames (include/clsimhip.h: "MCPE frame store").  The definition lives here ONCE, as
-// functions both the host twins (mcpe_union.cpp) and the HIP kernels (mcpe_union_kernel.hip) compile.  It stands where the
-// reference's client module files every result's hits into a frame cache that lives across bunches and commits the oldest frames no
-// bunch in flight can still touch
+// accumulated state and gives up finished frames (include/clsimhip.h: "MCPE frame store").  The stage itself is stated once for
+// every record type (series_union.h, series_union_host.h, series_union_device.hip.h); what is the MCPE's own lives here ONCE, as
+// functions both the host twins (mcpe_union.cpp) and the HIP kernels (mcpe_union_kernel.hip) compile: the key, the local checks of
+// its series form and the traits type McpeUnion that hands them to the shared statement.  The stage stands where the reference's
+// client module files every result's hits into a frame cache that lives across bunches and commits the oldest frames no bunch in
+// flight can still touch
 //   I3CLSimClientModule::AddPhotonsToFrames   private/clsim/I3CLSimClientModule.cxx:359-439  (frame->hits)
 //   I3CLSimClientModule::FlushFrameCache      :686-758  (framesForBunches_, lastPendingFrame: a prefix of the cache)
 // A series form is sorted by one integer key and equal keys are equal bytes, so the union is a function of the multiset of records:
@@ -15,27 +17,14 @@
 #include <memory>
 
 #include "mcpe_series.h"
+#include "series_union.h"
 
 namespace clsimhip {
 
-#define UNION_HD __host__ __device__ __forceinline__
-
 // The key of a record: (frame of its entry, DOM code, tkey high, tkey low, identifier), most significant word first, compared word
-// by word as unsigned integers.  The comparison takes the number of words: a 24- or 48-byte record's key is a longer array.
+// by word as unsigned integers (union_words_less).
 constexpr uint32_t kUnionKeyWords = 5u;
 struct UnionKey { uint32_t w[kUnionKeyWords]; };
-
-// ascending in (string ID signed, OM ID); `word` = string ID | OM ID << 16, as in the records and the table entries
-UNION_HD uint32_t union_dom_code(uint32_t word) { return (((word & 0xffffu) ^ 0x8000u) << 16) | (word >> 16); }
-UNION_HD uint32_t union_dom_word(uint32_t code) { return ((code >> 16) ^ 0x8000u) | (code << 16); }
-
-UNION_HD bool union_words_less(const uint32_t *a, const uint32_t *b, uint32_t words)
-{
-    for (uint32_t k = 0; k < words; ++k)
-        if (a[k] != b[k]) return a[k] < b[k];
-    return false;
-}
-UNION_HD bool union_key_less(const UnionKey &a, const UnionKey &b) { return union_words_less(a.w, b.w, kUnionKeyWords); }
 
 // a record's first 8 bytes: identifier | string ID << 32 | OM ID << 48; a table entry's: frame | string ID << 32 | OM ID << 48
 UNION_HD UnionKey union_make_key(uint32_t frame, uint64_t ids, uint64_t time_bits)
@@ -74,18 +63,6 @@ UNION_HD bool union_entry_ok(const clsimhip_mcpe_series *series, uint32_t n_seri
     return true;
 }
 
-// the entry record i belongs to: the last one with first <= i, by bisection over `first` (as the photon hits stage finds it); -1
-// when there is none.  At most 32 trips whatever the table holds.
-UNION_HD int64_t union_entry_of(const clsimhip_mcpe_series *series, uint32_t n_series, uint32_t i)
-{
-    uint32_t lo = 0u, hi = n_series;                                    // first entry with first > i
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo) / 2u;
-        if (series[mid].first <= i) lo = mid + 1u; else hi = mid;
-    }
-    return (int64_t)lo - 1;
-}
-
 // record i of n; *frame receives its entry's frame (0 without an entry)
 UNION_HD bool union_record_ok(const clsimhip_mcpe *records, const clsimhip_mcpe_series *series, uint32_t n_series, uint32_t i, uint32_t *frame)
 {
@@ -105,16 +82,34 @@ UNION_HD bool union_record_ok(const clsimhip_mcpe *records, const clsimhip_mcpe_
     return true;
 }
 
-// Split: the number of entries with frame <= last_frame, a prefix of a table ascending in the frame
-UNION_HD uint32_t union_split_entries(const clsimhip_mcpe_series *series, uint32_t n_series, uint32_t last_frame)
-{
-    uint32_t lo = 0u, hi = n_series;
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo) / 2u;
-        if (series[mid].frame <= last_frame) lo = mid + 1u; else hi = mid;
+// what the shared statement of the stage (series_union.h) takes from this header
+struct McpeUnion {
+    using Record = clsimhip_mcpe;
+    using Entry = clsimhip_mcpe_series;
+    using Key = UnionKey;
+    static constexpr uint32_t kRecordWords = 4u, kEntryWords = 4u, kKeyWords = kUnionKeyWords, kChannelWords = 2u /* frame, DOM code */, kAlign = 16u;
+    static constexpr const char *kStore = "MCPE frame store", *kName = "MCPE";
+    static constexpr const char *kEntryRule = "the table must ascend strictly in (frame, string_id, om_id), every count > 0, first[0] = 0, first[s] = first[s-1] + count[s-1]";
+    static constexpr const char *kRecordRule = "every record must lie in an entry, carry its string_id and om_id, and not descend in (time key, identifier) behind its predecessor";
+    static UNION_HD Key key_of(uint32_t frame, const Record *records, size_t i)
+    {
+        const uint64_t *rec = reinterpret_cast<const uint64_t *>(records + i);
+        return union_make_key(frame, rec[0], rec[1]);
     }
-    return lo;
-}
+    static UNION_HD bool entry_ok(const Entry *series, uint32_t n_series, uint32_t n, uint32_t s) { return union_entry_ok(series, n_series, n, s); }
+    static UNION_HD bool record_ok(const Record *records, const Entry *series, uint32_t n_series, uint32_t i, uint32_t *frame)
+    {
+        return union_record_ok(records, series, n_series, i, frame);
+    }
+    // the table entry a record opens (first: the caller's)
+    static void open_entry(Entry &s, uint32_t frame, const Record &r)
+    {
+        s.frame = frame;
+        s.string_id = r.string_id; s.om_id = r.om_id;
+        s.count = 0u;
+    }
+};
+static_assert(union_traits_ok<McpeUnion>(), "");
 
 // ---- the host twins (mcpe_union.cpp: host only, no HIP call); they throw Error (CLSIMHIP_ERR_ARGUMENT) ----
 void mcpe_series_union_host(const clsimhip_mcpe *a_records, size_t n_a, const clsimhip_mcpe_series *a_series, size_t n_series_a, const clsimhip_mcpe *b_records,
@@ -127,45 +122,6 @@ void mcpe_series_split_host(const clsimhip_mcpe *records, size_t n, const clsimh
 void mcpe_series_form_check(const char *what, const clsimhip_mcpe *records, size_t n, const clsimhip_mcpe_series *series, size_t n_series);
 
 // ---- the device stage (mcpe_union_kernel.hip) ----
-// words of the series stage's header (mcpe_series.h: SeriesHeader) the union keeps its own sizes in; the tile scan it shares with
-// the series stage reads SH_KEPT (the records of the output) and writes SH_SERIES
-enum UnionHeader : uint32_t { UH_MALFORMED_A = 2, UH_MALFORMED_B = 3, UH_OVERFLOW = 4 /* with SH_KEPT, SH_SERIES: the five output counts */,
-                              UH_N_A = 40 /* the effective sizes */, UH_N_B = 41, UH_IN_A = 42 /* what the inputs hold */, UH_IN_B = 43,
-                              UH_SERIES_A = 44, UH_SERIES_B = 45 };
-
-struct UnionDeviceArgs {
-    const clsimhip_mcpe *a_records;
-    const clsimhip_mcpe_series *a_series;
-    const uint32_t *a_counts;               // records = min([0], capacity_a), series = min([1], capacity_a)
-    const clsimhip_mcpe *b_records;
-    const clsimhip_mcpe_series *b_series;
-    const uint32_t *b_counts;
-    uint32_t capacity_a, capacity_b, out_capacity;
-    uint32_t *header;                       // kSeriesHeaderWords
-    uint32_t *tile_counts;                  // heads per output tile, scanned in place
-    uint32_t *partition;                    // per output tile boundary: records of A in front of it
-    uint32_t *a_frames, *b_frames;          // per input record: its entry's frame
-    uint32_t *out_frames;                   // per output record
-    clsimhip_mcpe *out_records;
-    clsimhip_mcpe_series *out_series;
-    uint32_t *out_counts;                   // five
-};
-
-struct SplitDeviceArgs {
-    const clsimhip_mcpe *records;
-    const clsimhip_mcpe_series *series;
-    const uint32_t *counts;
-    uint32_t capacity, last_frame;
-    const uint32_t *blocked;                // (may be null) five words: any nonzero -> nothing is drained
-    clsimhip_mcpe *head_records;            // (null with head_series: the head is dropped, the store's own use behind a download)
-    clsimhip_mcpe_series *head_series;
-    uint32_t *head_counts;                  // five: records, series, 0, 0, overflow
-    uint32_t head_capacity;
-    clsimhip_mcpe *tail_records;
-    clsimhip_mcpe_series *tail_series;
-    uint32_t *tail_counts;                  // five: records, series, 0, 0, 0
-};
-
 size_t mcpe_union_workspace_bytes(size_t capacity_a, size_t capacity_b);
 void mcpe_union_device(int device, const void *d_a_records, const void *d_a_series, const void *d_a_counts, size_t capacity_a, const void *d_b_records,
                        const void *d_b_series, const void *d_b_counts, size_t capacity_b, void *d_out_records, void *d_out_series, void *d_out_counts,
@@ -175,20 +131,7 @@ void mcpe_split_device(int device, const void *d_records, const void *d_series, 
                        void *d_tail_counts, size_t tail_capacity, hipStream_t stream);
 
 // ---- the store ----
-constexpr size_t kFrameStoreMaxCapacity = size_t{1} << 31;
-// sticky counters of a device store: data that was dropped on the device, where no call could refuse it
-enum FrameStoreSticky : uint32_t { FS_MALFORMED_BUNCHES = 0, FS_MALFORMED_ELEMENTS = 1, FS_OVERFLOWED_BUNCHES = 2, FS_OVERFLOWED_RECORDS = 3, FS_MALFORMED_STORE = 4 };
-
-class FrameStore {
-public:
-    virtual ~FrameStore() = default;
-    virtual bool on_device() const = 0;
-    virtual void add_host(const clsimhip_mcpe *records, size_t n, const clsimhip_mcpe_series *series, size_t n_series) = 0;
-    virtual void add_device(const void *d_records, const void *d_series, const void *d_series_counts, size_t capacity, hipStream_t stream) = 0;
-    virtual void drain_device(uint32_t last_frame, void *d_records, void *d_series, void *d_counts, size_t capacity, hipStream_t stream) = 0;
-    virtual void drain_host(uint32_t last_frame, clsimhip_mcpe *records, clsimhip_mcpe_series *series, size_t capacity, size_t *n, size_t *n_series) = 0;
-    virtual void size(uint32_t last_frame, size_t *n, size_t *n_series) = 0;
-};
+using FrameStore = FrameStoreOf<McpeUnion>;
 std::unique_ptr<FrameStore> make_host_frame_store(size_t capacity);                     // mcpe_union.cpp
 std::unique_ptr<FrameStore> make_device_frame_store(int device, size_t capacity);       // mcpe_union_kernel.hip
 

@@ -1,13 +1,13 @@
 // PMT hit frame store: the union of two series forms of PMT hits, the split of one at a frame bound, and the store that folds bunches
-// into accumulated state and gives up finished frames (include/clsimhip.h: "PMT hit frame store").  The definition lives here ONCE,
-// as functions both the host twins (pmt_hit_union.cpp) and the HIP kernels (pmt_hit_union_kernel.hip) compile.  It stands where the
-// reference's client module files every result into a frame cache that lives across bunches and commits the oldest frames no bunch
-// in flight can still touch
+// into accumulated state and gives up finished frames (include/clsimhip.h: "PMT hit frame store").  The stage itself is stated once
+// for every record type (series_union.h, series_union_host.h, series_union_device.hip.h); what is the PMT hit's own lives here ONCE,
+// as functions both the host twins (pmt_hit_union.cpp) and the HIP kernels (pmt_hit_union_kernel.hip) compile, with the traits type
+// PmtHitUnion that hands them to the shared statement.  The stage stands where the reference's client module files every result into
+// a frame cache that lives across bunches and commits the oldest frames no bunch in flight can still touch
 //   I3CLSimClientModule::AddPhotonsToFrames   private/clsim/I3CLSimClientModule.cxx:359-439
 //   I3CLSimClientModule::FlushFrameCache      :686-758  (framesForBunches_, lastPendingFrame: a prefix of the cache)
-// The DOM code, the word comparison, the header words and the sticky counters are the MCPE frame store's and the integer time key is
-// the frame photon store's; both headers are taken as they stand.  What needs the PMT table type (24-byte entries with a pmt word and
-// a reserved word) is restated here: the entry check, the bisections over the table, the record check.
+// The integer time key is the frame photon store's, taken as it stands.  What needs the PMT table type (24-byte entries with a pmt
+// word and a reserved word) is stated here: the entry check and the record check.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -61,8 +61,6 @@ UNION_HD void pmt_hit_union_record_of(const uint32_t key[kPmtHitKeyWords], uint3
     rec[5] = (uint32_t)(bits >> 32);
 }
 
-UNION_HD bool pmt_hit_union_key_less(const PmtHitKey &a, const PmtHitKey &b) { return union_words_less(a.w, b.w, kPmtHitKeyWords); }
-
 // (frame, DOM code, pmt) of a table entry
 UNION_HD void pmt_hit_union_entry_channel(const uint32_t e[kPmtHitEntryWords], uint32_t channel[kPmtHitChannelWords])
 {
@@ -93,23 +91,11 @@ UNION_HD bool pmt_hit_union_entry_ok(const clsimhip_pmt_series *series, uint32_t
     return true;
 }
 
-// the entry record i belongs to: the last one with first <= i, by bisection over `first`; -1 when there is none.  At most 32 trips
-// whatever the table holds.
-UNION_HD int64_t pmt_hit_union_entry_of(const clsimhip_pmt_series *series, uint32_t n_series, uint32_t i)
-{
-    uint32_t lo = 0u, hi = n_series;                                    // first entry with first > i
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo) / 2u;
-        if (pmt_hit_union_entry_words(series, mid)[3] <= i) lo = mid + 1u; else hi = mid;
-    }
-    return (int64_t)lo - 1;
-}
-
 // record i of n; *frame receives its entry's frame (0 without an entry)
 UNION_HD bool pmt_hit_union_record_ok(const clsimhip_pmt_hit *records, const clsimhip_pmt_series *series, uint32_t n_series, uint32_t i, uint32_t *frame)
 {
     *frame = 0u;
-    const int64_t s = pmt_hit_union_entry_of(series, n_series, i);
+    const int64_t s = union_entry_of(series, n_series, i);
     if (s < 0) return false;                                            // (an empty table needs zero records)
     const uint32_t *e = pmt_hit_union_entry_words(series, (size_t)s);
     const uint32_t first = e[3], count = e[4];
@@ -125,16 +111,34 @@ UNION_HD bool pmt_hit_union_record_ok(const clsimhip_pmt_hit *records, const cls
     return true;
 }
 
-// Split: the number of entries with frame <= last_frame, a prefix of a table ascending in the frame
-UNION_HD uint32_t pmt_hit_union_split_entries(const clsimhip_pmt_series *series, uint32_t n_series, uint32_t last_frame)
-{
-    uint32_t lo = 0u, hi = n_series;
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo) / 2u;
-        if (pmt_hit_union_entry_words(series, mid)[0] <= last_frame) lo = mid + 1u; else hi = mid;
+// what the shared statement of the stage (series_union.h) takes from this header
+struct PmtHitUnion {
+    using Record = clsimhip_pmt_hit;
+    using Entry = clsimhip_pmt_series;
+    using Key = PmtHitKey;
+    static constexpr uint32_t kRecordWords = kPmtHitRecordWords, kEntryWords = kPmtHitEntryWords, kKeyWords = kPmtHitKeyWords, kChannelWords = kPmtHitChannelWords,
+                              kAlign = 8u;
+    static constexpr const char *kStore = "PMT hit frame store", *kName = "PMT hit";
+    static constexpr const char *kEntryRule =
+        "the table must ascend strictly in (frame, string_id, om_id, pmt), every count > 0, every reserved = 0, first[0] = 0, first[s] = first[s-1] + count[s-1]";
+    static constexpr const char *kRecordRule =
+        "every record must lie in an entry, carry its string_id, om_id and pmt, have reserved = 0, and not descend in (time key, identifier) behind its predecessor";
+    static UNION_HD Key key_of(uint32_t frame, const Record *records, size_t i) { return pmt_hit_union_make_key(frame, pmt_hit_union_words(records, i)); }
+    static UNION_HD bool entry_ok(const Entry *series, uint32_t n_series, uint32_t n, uint32_t s) { return pmt_hit_union_entry_ok(series, n_series, n, s); }
+    static UNION_HD bool record_ok(const Record *records, const Entry *series, uint32_t n_series, uint32_t i, uint32_t *frame)
+    {
+        return pmt_hit_union_record_ok(records, series, n_series, i, frame);
     }
-    return lo;
-}
+    static void open_entry(Entry &s, uint32_t frame, const Record &r)
+    {
+        s.frame = frame;
+        s.string_id = r.string_id; s.om_id = r.om_id;
+        s.pmt = r.pmt;
+        s.count = 0u;
+        s.reserved = 0u;
+    }
+};
+static_assert(union_traits_ok<PmtHitUnion>(), "");
 
 // ---- the host twins (pmt_hit_union.cpp: host only, no HIP call); they throw Error (CLSIMHIP_ERR_ARGUMENT) ----
 void pmt_hits_union_host(const clsimhip_pmt_hit *a_records, size_t n_a, const clsimhip_pmt_series *a_series, size_t n_series_a, const clsimhip_pmt_hit *b_records,
@@ -147,41 +151,8 @@ void pmt_hits_split_host(const clsimhip_pmt_hit *records, size_t n, const clsimh
 void pmt_hits_form_check(const char *what, const clsimhip_pmt_hit *records, size_t n, const clsimhip_pmt_series *series, size_t n_series);
 
 // ---- the device stage (pmt_hit_union_kernel.hip) ----
-// The header is the MCPE union's (mcpe_union.h: UnionHeader beside mcpe_series.h's SH_KEPT and SH_SERIES), so that
+// The header is the MCPE union's (series_union.h: UnionHeader beside mcpe_series.h's SH_KEPT and SH_SERIES), so that
 // launch_series_tile_scan runs unchanged on it.
-struct PmtHitUnionDeviceArgs {
-    const clsimhip_pmt_hit *a_records;
-    const clsimhip_pmt_series *a_series;
-    const uint32_t *a_counts;               // records = min([0], capacity_a), series = min([1], capacity_a)
-    const clsimhip_pmt_hit *b_records;
-    const clsimhip_pmt_series *b_series;
-    const uint32_t *b_counts;
-    uint32_t capacity_a, capacity_b, out_capacity;
-    uint32_t *header;                       // kSeriesHeaderWords
-    uint32_t *tile_counts;                  // heads per output tile, scanned in place
-    uint32_t *partition;                    // per output tile boundary: records of A in front of it
-    uint32_t *a_frames, *b_frames;          // per input record: its entry's frame
-    uint32_t *out_frames;                   // per output record
-    clsimhip_pmt_hit *out_records;
-    clsimhip_pmt_series *out_series;
-    uint32_t *out_counts;                   // five
-};
-
-struct PmtHitSplitDeviceArgs {
-    const clsimhip_pmt_hit *records;
-    const clsimhip_pmt_series *series;
-    const uint32_t *counts;
-    uint32_t capacity, last_frame;
-    const uint32_t *blocked;                // (may be null) five words: any nonzero -> nothing is drained
-    clsimhip_pmt_hit *head_records;         // (null with head_series: the head is dropped, the store's own use behind a download)
-    clsimhip_pmt_series *head_series;
-    uint32_t *head_counts;                  // five: records, series, 0, 0, overflow
-    uint32_t head_capacity;
-    clsimhip_pmt_hit *tail_records;
-    clsimhip_pmt_series *tail_series;
-    uint32_t *tail_counts;                  // five: records, series, 0, 0, 0
-};
-
 size_t pmt_hits_union_workspace_bytes(size_t capacity_a, size_t capacity_b);
 void pmt_hits_union_device(int device, const void *d_a_records, const void *d_a_series, const void *d_a_counts, size_t capacity_a, const void *d_b_records,
                            const void *d_b_series, const void *d_b_counts, size_t capacity_b, void *d_out_records, void *d_out_series, void *d_out_counts,
@@ -190,17 +161,8 @@ void pmt_hits_split_device(int device, const void *d_records, const void *d_seri
                            void *d_head_records, void *d_head_series, void *d_head_counts, size_t head_capacity, void *d_tail_records, void *d_tail_series,
                            void *d_tail_counts, size_t tail_capacity, hipStream_t stream);
 
-// ---- the store: FrameStore's behaviour (mcpe_union.h) on PMT hits; the sticky counters are FrameStoreSticky ----
-class PmtHitStore {
-public:
-    virtual ~PmtHitStore() = default;
-    virtual bool on_device() const = 0;
-    virtual void add_host(const clsimhip_pmt_hit *records, size_t n, const clsimhip_pmt_series *series, size_t n_series) = 0;
-    virtual void add_device(const void *d_records, const void *d_series, const void *d_series_counts, size_t capacity, hipStream_t stream) = 0;
-    virtual void drain_device(uint32_t last_frame, void *d_records, void *d_series, void *d_counts, size_t capacity, hipStream_t stream) = 0;
-    virtual void drain_host(uint32_t last_frame, clsimhip_pmt_hit *records, clsimhip_pmt_series *series, size_t capacity, size_t *n, size_t *n_series) = 0;
-    virtual void size(uint32_t last_frame, size_t *n, size_t *n_series) = 0;
-};
+// ---- the store: the sticky counters are FrameStoreSticky ----
+using PmtHitStore = FrameStoreOf<PmtHitUnion>;
 std::unique_ptr<PmtHitStore> make_host_pmt_hit_store(size_t capacity);                  // pmt_hit_union.cpp
 std::unique_ptr<PmtHitStore> make_device_pmt_hit_store(int device, size_t capacity);    // pmt_hit_union_kernel.hip
 
