@@ -520,7 +520,12 @@ DM float generate_wavelength(KP P, int gen, uint64_t &x, uint32_t a)
     if ((b == 0.0f) && (slope == 0.0f)) return x0;
     else if (b == 0.0f) return x0 + dm::sqrt_(2.0f * dy / slope);
     else if (slope == 0.0f) return x0 + dy / b;
-    else return x0 + (dm::sqrt_(dy * (2.0f * slope) / (b * b) + 1.0f) - 1.0f) * b / slope;
+    // A DEPARTURE FROM THE REFERENCE: where the density falls to (nearly) zero the discriminant at the bin's end is zero
+    // up to rounding and comes out negative for some draws; the reference's square root is then NaN and the photon never ends.
+    // Held at zero from below (a NaN too): x0 - b / slope, the bin's end.  Bit-identical wherever it was positive.
+    const float disc = dy * (2.0f * slope) / (b * b) + 1.0f;
+    // (compiles to one v_max_f32 on the discriminant, as __builtin_fmaxf(disc, 0.0f) does: the same machine code)
+    return x0 + (dm::sqrt_((disc > 0.0f) ? disc : 0.0f) - 1.0f) * b / slope;
 }
 
 // FunctionFromTable.cxx:167-300

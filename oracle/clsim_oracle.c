@@ -420,7 +420,9 @@ static inline float generateWavelength_k(const oracle_tables *T, int kgen, rng_t
     if ((b == 0.0f) && (slope == 0.0f)) return x0;
     else if (b == 0.0f) return x0 + om_sqrt(2.0f * dy / slope);
     else if (slope == 0.0f) return x0 + dy / b;
-    else return x0 + (om_sqrt(dy * (2.0f * slope) / (b * b) + 1.0f) - 1.0f) * b / slope;
+    /* A DEPARTURE FROM THE REFERENCE: the discriminant is held at zero from below (a NaN too).  At the end of a bin
+     * whose density falls to (nearly) zero it is zero up to rounding and can come out negative: the reference's sqrt is NaN there. */
+    return x0 + (om_sqrt(fmaxf_(dy * (2.0f * slope) / (b * b) + 1.0f, 0.0f)) - 1.0f) * b / slope;
 }
 /* MediumPropertiesSource.cxx:392-432 */
 static inline float generateWavelength(const oracle_tables *T, uint32_t number, rng_t *rng)

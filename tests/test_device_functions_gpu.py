@@ -9,6 +9,7 @@ import pytest
 
 from oracle import capi
 from tests import common
+from tests import sampler_common as SC
 from tests.propagation_reference import ppc_anisotropy, tilt_independent          # the independent formulas live there
 
 pytestmark = pytest.mark.gpu
@@ -140,6 +141,9 @@ def test_random_distributions_device_equals_oracle(setups, name):
     c, _ = conv.SampleOnDevice("scattering_cosine", x, a, 200)
     mean_cos = 0.9 if name != "photonics_mie" else float(c.mean())
     assert -1.0 <= c.min() and c.max() <= 1.0 and abs(c.mean() - mean_cos) < 0.01         # <cos theta> = 0.9 (cfg.txt), whatever the mixture
+    # ... which is why the mean cannot see a wrong mixture: the distribution itself, against the analytic CDF (tests/sampler_reference.py)
+    kind = {0: "hg", 1: "liu", 2: "mixed"}[int(T.t.scat_kind)]
+    SC.kolmogorov((kind, float(T.t.hg_g), float(T.t.mix_frac) if kind == "mixed" else None), c, name)
     w, _ = conv.SampleOnDevice("wavelength", x, a, 200)
     assert 2.6e-7 <= w.min() and w.max() <= 6.8e-7
     if name == "flasher_led405":

@@ -3,7 +3,11 @@
 I3CLSimRandomValueInterpolatedDistribution(x, y) (InterpolatedDistribution.cxx:40-55, :148-154, :292-297) and the flasher LEDs'
 measured spectra (python/GetIceCubeFlasherSpectrum.py; the data files of resources/flasher_data/).  Host side: C ABI against
 the oracle's builders and against plain numpy; the sampling itself is pinned on the reference's generated code by
-tests/test_verbatim_cl.py (flasher_led405) and checked here as a distribution."""
+tests/test_verbatim_cl.py (flasher_led405) and checked here as a distribution.  Draw by draw -- every generator, forced draws on every
+cumulative-table entry, word 0 and the largest word, against the exact CDF of the float64 table -- it is held by
+tests/test_sampler_reference.py (the oracle) and tests/test_sampler_reference_gpu.py (the tester kernel), with the statement in
+tests/sampler_reference.py; the draw on which the reference's own expression gives a NaN wavelength (the end of a bin whose density
+falls to zero: LED370nm, r = 1) is there too."""
 import numpy as np
 import pytest
 
