@@ -164,6 +164,12 @@ SYMBOLS = [
     "clsimhip_event_statistics_add", "clsimhip_event_statistics_weight", "clsimhip_event_statistics_host",
     "clsimhip_event_statistics_workspace_bytes", "clsimhip_event_statistics_device", "clsimhip_set_event_statistics",
     "clsimhip_get_result_event_statistics",
+    "clsimhip_event_statistics_canonical_host", "clsimhip_event_statistics_combine_host", "clsimhip_event_statistics_split_host",
+    "clsimhip_event_statistics_store_workspace_bytes", "clsimhip_event_statistics_canonical_device",
+    "clsimhip_event_statistics_combine_device", "clsimhip_event_statistics_split_device",
+    "clsimhip_event_statistics_store_create", "clsimhip_event_statistics_store_destroy", "clsimhip_event_statistics_store_last_error",
+    "clsimhip_event_statistics_store_add_host", "clsimhip_event_statistics_store_add_device", "clsimhip_event_statistics_store_drain_device",
+    "clsimhip_event_statistics_store_drain_host", "clsimhip_event_statistics_store_size",
     "clsimhip_photon_hit_maker_create", "clsimhip_photon_hit_maker_destroy", "clsimhip_photon_hit_maker_last_error",
     "clsimhip_photon_hit_maker_efficiency", "clsimhip_photon_hits_host", "clsimhip_photon_hits_workspace_bytes", "clsimhip_photon_hits_device",
     "clsimhip_pmt_photon_hits_host", "clsimhip_pmt_photon_hits_workspace_bytes", "clsimhip_pmt_photon_hits_device",
@@ -422,6 +428,21 @@ def load():
         "clsimhip_event_statistics_device": (i32, [i32, vp, sz, vp, vp, sz, vp, sz, vp, sz, vp, vp, vp, sz, vp]),
         "clsimhip_set_event_statistics": (i32, [vp, i32]),
         "clsimhip_get_result_event_statistics": (i32, [vp, vp, C.POINTER(vp), C.POINTER(sz), vp]),
+        "clsimhip_event_statistics_canonical_host": (i32, [vp, sz, vp, sz, vp, sz, C.POINTER(sz), vp]),
+        "clsimhip_event_statistics_combine_host": (i32, [vp, sz, vp, sz, vp, sz, C.POINTER(sz)]),
+        "clsimhip_event_statistics_split_host": (i32, [vp, sz, u32, vp, sz, C.POINTER(sz), vp, sz, C.POINTER(sz)]),
+        "clsimhip_event_statistics_store_workspace_bytes": (sz, [sz, sz]),
+        "clsimhip_event_statistics_canonical_device": (i32, [i32, vp, vp, sz, vp, sz, vp, vp, sz, vp, sz, vp]),
+        "clsimhip_event_statistics_combine_device": (i32, [i32, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, sz, vp]),
+        "clsimhip_event_statistics_split_device": (i32, [i32, vp, vp, sz, u32, vp, vp, sz, vp, vp, sz, vp]),
+        "clsimhip_event_statistics_store_create": (i32, [i32, sz, C.POINTER(vp)]),
+        "clsimhip_event_statistics_store_destroy": (None, [vp]),
+        "clsimhip_event_statistics_store_last_error": (C.c_char_p, [vp]),
+        "clsimhip_event_statistics_store_add_host": (i32, [vp, vp, sz, vp, sz]),
+        "clsimhip_event_statistics_store_add_device": (i32, [vp, vp, vp, sz, vp, sz, vp]),
+        "clsimhip_event_statistics_store_drain_device": (i32, [vp, u32, vp, sz, vp, vp, sz, vp]),
+        "clsimhip_event_statistics_store_drain_host": (i32, [vp, u32, vp, sz, vp, sz, C.POINTER(sz)]),
+        "clsimhip_event_statistics_store_size": (i32, [vp, u32, C.POINTER(sz)]),
         "clsimhip_photon_hit_maker_create": (i32, [C.POINTER(Function), sz, C.POINTER(Polynomial), vp, sz, C.POINTER(PhotonHitConfig), C.POINTER(vp)]),
         "clsimhip_photon_hit_maker_destroy": (None, [vp]),
         "clsimhip_photon_hit_maker_last_error": (C.c_char_p, [vp]),

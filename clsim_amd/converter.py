@@ -2125,3 +2125,138 @@ class SeriesRelabeler:
                                                             self.map.ctypes.data_as(C.c_void_p), len(self.map), out.ctypes.data_as(C.c_void_p),
                                                             out_ranges.ctypes.data_as(C.c_void_p), C.byref(n)))
         return out[:n.value], out_ranges
+
+
+EVENT_STATISTICS_STORE_COUNTERS = ("relabelled", "empty_dropped")
+# the five output counts of the event statistics store's device stages (include/clsimhip.h: "Event statistics frame store")
+EVENT_STATISTICS_CANONICAL_COUNTS = ("records", "series", "relabelled", "empty_dropped", "overflow")
+EVENT_STATISTICS_COMBINE_COUNTS = ("records", "series", "malformed_a", "malformed_b", "overflow")
+
+
+def _statistics(records):
+    return np.ascontiguousarray(records, dtype=EVENT_STATISTICS_DTYPE).reshape(-1)
+
+
+def _relabel_map(map):
+    return np.zeros(0, dtype=RELABEL_DTYPE) if map is None else np.ascontiguousarray(map, dtype=RELABEL_DTYPE).reshape(-1)
+
+
+def _address(array):
+    return C.c_void_p(array.ctypes.data if len(array) else None)
+
+
+class EventStatisticsStore:
+    """The event statistics records of several bunches accumulate per frame and particle as exact sums; finished frames leave
+    (clsimhip_event_statistics_store; include/clsimhip.h: "Event statistics frame store"): what MCPEFrameStore is for MCPEs, for
+    EVENT_STATISTICS_DTYPE records, with a relabel map (RELABEL_DTYPE, slice_muons' table) that folds slices into their muon when a
+    bunch is added or when a frame is drained.  device=None: a host store, which needs no GPU; device=k: the state lives in HBM of
+    GPU k.  Call Add (or AddDevice) per result and Drain with the last frame no bunch in flight can still touch."""
+
+    def __init__(self, capacity, device=None):
+        self._lib = _lib.load()
+        self._h = C.c_void_p()
+        self.capacity, self.device = int(capacity), device
+        _check(self._lib.clsimhip_event_statistics_store_create(-1 if device is None else int(device), self.capacity, C.byref(self._h)))
+
+    def __del__(self):
+        try:
+            if self._h:
+                self._lib.clsimhip_event_statistics_store_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def Add(self, records, map=None):
+        """one bunch in host memory: any list of records (a result's event statistics as they come, zeros included)"""
+        records, map = _statistics(records), _relabel_map(map)
+        _check(self._lib.clsimhip_event_statistics_store_add_host(self._h, _address(records), len(records), _address(map), len(map)))
+
+    def AddDevice(self, d_records, d_count, capacity, map=None, stream=0):
+        """one bunch in HBM (addresses: EventStatistics.MakeDevice's d_out, and word 3 of its d_counters as the count); asynchronous
+        on `stream`"""
+        map = _relabel_map(map)
+        _check(self._lib.clsimhip_event_statistics_store_add_device(self._h, C.c_void_p(d_records), C.c_void_p(d_count), int(capacity), _address(map), len(map),
+                                                                    C.c_void_p(stream)))
+
+    def Size(self, last_frame=ALL_FRAMES):
+        """records of the frames <= last_frame, before a drain's map folds them: what a Drain's output must hold; waits"""
+        n = C.c_size_t()
+        _check(self._lib.clsimhip_event_statistics_store_size(self._h, int(last_frame), C.byref(n)))
+        return n.value
+
+    def Drain(self, last_frame=ALL_FRAMES, map=None):
+        """the records of the frames <= last_frame under the map, which leave the store; waits"""
+        n, map = self.Size(last_frame), _relabel_map(map)
+        records, got = np.zeros(n, dtype=EVENT_STATISTICS_DTYPE), C.c_size_t()
+        _check(self._lib.clsimhip_event_statistics_store_drain_host(self._h, int(last_frame), _address(map), len(map), _address(records), n, C.byref(got)))
+        return records[:got.value]
+
+    def DrainDevice(self, last_frame, d_out, d_counts, capacity, map=None, stream=0):
+        """the frames <= last_frame move to the caller's device buffer under the map (addresses; d_counts: five uint32,
+        EVENT_STATISTICS_CANONICAL_COUNTS); asynchronous on `stream`"""
+        map = _relabel_map(map)
+        _check(self._lib.clsimhip_event_statistics_store_drain_device(self._h, int(last_frame), _address(map), len(map), C.c_void_p(d_out), C.c_void_p(d_counts),
+                                                                      int(capacity), C.c_void_p(stream)))
+
+    @staticmethod
+    def CanonicalHost(records, map=None, capacity=None):
+        """(records, counters): the host twin of CANON; counters = {name: count} (EVENT_STATISTICS_STORE_COUNTERS); capacity: of the
+        output, len(records) by default"""
+        records, map = _statistics(records), _relabel_map(map)
+        capacity = len(records) if capacity is None else int(capacity)
+        out, n, counters = np.zeros(capacity, dtype=EVENT_STATISTICS_DTYPE), C.c_size_t(), np.zeros(2, dtype=np.uint64)
+        _check(_lib.load().clsimhip_event_statistics_canonical_host(_address(records), len(records), _address(map), len(map), _address(out), capacity, C.byref(n),
+                                                                    counters.ctypes.data_as(C.c_void_p)))
+        return out[:n.value], dict(zip(EVENT_STATISTICS_STORE_COUNTERS, (int(c) for c in counters)))
+
+    @staticmethod
+    def CombineHost(a, b, capacity=None):
+        """the host twin of COMBINE of two statistics forms; capacity: of the output, len(a) + len(b) by default"""
+        a, b = _statistics(a), _statistics(b)
+        capacity = len(a) + len(b) if capacity is None else int(capacity)
+        out, n = np.zeros(capacity, dtype=EVENT_STATISTICS_DTYPE), C.c_size_t()
+        _check(_lib.load().clsimhip_event_statistics_combine_host(_address(a), len(a), _address(b), len(b), _address(out), capacity, C.byref(n)))
+        return out[:n.value]
+
+    @staticmethod
+    def SplitHost(records, last_frame, head_capacity=None, tail_capacity=None):
+        """(head, tail): the host twin of SPLIT -- the head holds the frames <= last_frame"""
+        records = _statistics(records)
+        head_capacity = len(records) if head_capacity is None else int(head_capacity)
+        tail_capacity = len(records) if tail_capacity is None else int(tail_capacity)
+        head, tail = np.zeros(head_capacity, dtype=EVENT_STATISTICS_DTYPE), np.zeros(tail_capacity, dtype=EVENT_STATISTICS_DTYPE)
+        n_head, n_tail = C.c_size_t(), C.c_size_t()
+        _check(_lib.load().clsimhip_event_statistics_split_host(_address(records), len(records), int(last_frame), _address(head), head_capacity, C.byref(n_head),
+                                                                _address(tail), tail_capacity, C.byref(n_tail)))
+        return head[:n_head.value], tail[:n_tail.value]
+
+    @staticmethod
+    def WorkspaceBytes(capacity_a, capacity_b):
+        """bytes of d_workspace: CombineDevice of (capacity_a, capacity_b); CanonicalDevice of `capacity` records under a map of n_map
+        entries takes (capacity, n_map)"""
+        return int(_lib.load().clsimhip_event_statistics_store_workspace_bytes(int(capacity_a), int(capacity_b)))
+
+    @staticmethod
+    def CanonicalDevice(d_records, d_count, capacity, d_out, d_out_counts, out_capacity, d_workspace, workspace_bytes, map=None, device=0, stream=0):
+        """the kernels on device-resident records (addresses; d_count: one uint32); d_out_counts: five uint32
+        (EVENT_STATISTICS_CANONICAL_COUNTS); d_workspace: WorkspaceBytes(capacity, len(map)) bytes"""
+        map = _relabel_map(map)
+        _check(_lib.load().clsimhip_event_statistics_canonical_device(int(device), C.c_void_p(d_records), C.c_void_p(d_count), int(capacity), _address(map), len(map),
+                                                                      C.c_void_p(d_out), C.c_void_p(d_out_counts), int(out_capacity), C.c_void_p(d_workspace),
+                                                                      int(workspace_bytes), C.c_void_p(stream)))
+
+    @staticmethod
+    def CombineDevice(d_a, d_a_count, capacity_a, d_b, d_b_count, capacity_b, d_out, d_out_counts, out_capacity, d_workspace, workspace_bytes, device=0, stream=0):
+        """the kernels on two device-resident statistics forms (addresses); d_out_counts: five uint32 (EVENT_STATISTICS_COMBINE_COUNTS);
+        d_workspace: WorkspaceBytes(capacity_a, capacity_b) bytes"""
+        _check(_lib.load().clsimhip_event_statistics_combine_device(int(device), C.c_void_p(d_a), C.c_void_p(d_a_count), int(capacity_a), C.c_void_p(d_b),
+                                                                    C.c_void_p(d_b_count), int(capacity_b), C.c_void_p(d_out), C.c_void_p(d_out_counts),
+                                                                    int(out_capacity), C.c_void_p(d_workspace), int(workspace_bytes), C.c_void_p(stream)))
+
+    @staticmethod
+    def SplitDevice(d_records, d_count, capacity, last_frame, d_head, d_head_counts, head_capacity, d_tail, d_tail_counts, tail_capacity, device=0, stream=0):
+        """the split on a device-resident statistics form (addresses); d_head_counts / d_tail_counts: five uint32 each (records, 0, 0, 0,
+        overflow)"""
+        _check(_lib.load().clsimhip_event_statistics_split_device(int(device), C.c_void_p(d_records), C.c_void_p(d_count), int(capacity), int(last_frame),
+                                                                  C.c_void_p(d_head), C.c_void_p(d_head_counts), int(head_capacity), C.c_void_p(d_tail),
+                                                                  C.c_void_p(d_tail_counts), int(tail_capacity), C.c_void_p(stream)))

@@ -18,6 +18,7 @@
 #include "pmt_hits.h"
 #include "cable_shadow.h"
 #include "event_stats.h"
+#include "event_stats_store.h"
 #include "frame_photons.h"
 #include "frame_photon_union.h"
 #include "pmt_hit_union.h"
@@ -39,6 +40,7 @@ struct clsimhip_photon_hit_maker { std::shared_ptr<PhotonHitMaker> impl; };
 struct clsimhip_mcpe_frame_store { std::unique_ptr<FrameStore> impl; };
 struct clsimhip_frame_photon_store { std::unique_ptr<FramePhotonStore> impl; };
 struct clsimhip_pmt_hit_store { std::unique_ptr<PmtHitStore> impl; };
+struct clsimhip_event_statistics_store { std::unique_ptr<EventStatsStore> impl; };
 struct clsimhip_tabulator {
     std::unique_ptr<Tabulator> impl;
 };
@@ -1568,6 +1570,85 @@ int clsimhip_get_result_event_statistics(clsimhip_converter *c, const clsimhip_p
                                          uint64_t counters[3])
 {
     return guarded(c, [&] { need(c, "converter"); c->impl.result_event_statistics(photons, records, n, counters); });
+}
+
+// ---- Event statistics frame store (event_stats_store.h) ----
+int clsimhip_event_statistics_canonical_host(const clsimhip_event_statistics *records, size_t n, const clsimhip_relabel *map, size_t n_map,
+                                             clsimhip_event_statistics *out, size_t capacity, size_t *n_out, uint64_t counters[2])
+{
+    return guarded(nullptr, [&] { event_stats_canonical_host(records, n, map, n_map, out, capacity, n_out, counters); });
+}
+int clsimhip_event_statistics_combine_host(const clsimhip_event_statistics *a, size_t n_a, const clsimhip_event_statistics *b, size_t n_b,
+                                           clsimhip_event_statistics *out, size_t capacity, size_t *n_out)
+{
+    return guarded(nullptr, [&] { event_stats_combine_host(a, n_a, b, n_b, out, capacity, n_out); });
+}
+int clsimhip_event_statistics_split_host(const clsimhip_event_statistics *records, size_t n, uint32_t last_frame,
+                                         clsimhip_event_statistics *head, size_t head_capacity, size_t *n_head,
+                                         clsimhip_event_statistics *tail, size_t tail_capacity, size_t *n_tail)
+{
+    return guarded(nullptr, [&] { event_stats_split_host(records, n, last_frame, head, head_capacity, n_head, tail, tail_capacity, n_tail); });
+}
+size_t clsimhip_event_statistics_store_workspace_bytes(size_t capacity_a, size_t capacity_b) { return event_stats_store_workspace_bytes(capacity_a, capacity_b); }
+int clsimhip_event_statistics_canonical_device(int device, const void *d_records, const void *d_count, size_t capacity,
+                                               const clsimhip_relabel *map, size_t n_map, void *d_out, void *d_out_counts, size_t out_capacity,
+                                               void *d_workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return guarded(nullptr, [&] {
+        event_stats_canonical_device(device, d_records, d_count, capacity, map, n_map, d_out, d_out_counts, out_capacity, d_workspace, workspace_bytes,
+                                     static_cast<hipStream_t>(hip_stream));
+    });
+}
+int clsimhip_event_statistics_combine_device(int device, const void *d_a, const void *d_a_count, size_t capacity_a, const void *d_b,
+                                             const void *d_b_count, size_t capacity_b, void *d_out, void *d_out_counts, size_t out_capacity,
+                                             void *d_workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return guarded(nullptr, [&] {
+        event_stats_combine_device(device, d_a, d_a_count, capacity_a, d_b, d_b_count, capacity_b, d_out, d_out_counts, out_capacity, d_workspace, workspace_bytes,
+                                   static_cast<hipStream_t>(hip_stream));
+    });
+}
+int clsimhip_event_statistics_split_device(int device, const void *d_records, const void *d_count, size_t capacity, uint32_t last_frame,
+                                           void *d_head, void *d_head_counts, size_t head_capacity, void *d_tail, void *d_tail_counts,
+                                           size_t tail_capacity, void *hip_stream)
+{
+    return guarded(nullptr, [&] {
+        event_stats_split_device(device, d_records, d_count, capacity, last_frame, d_head, d_head_counts, head_capacity, d_tail, d_tail_counts, tail_capacity,
+                                 static_cast<hipStream_t>(hip_stream));
+    });
+}
+int clsimhip_event_statistics_store_create(int device, size_t capacity, clsimhip_event_statistics_store **out)
+{
+    return guarded(nullptr, [&] {
+        need(out, "out");
+        *out = new clsimhip_event_statistics_store{device < 0 ? make_host_event_stats_store(capacity) : make_device_event_stats_store(device, capacity)};
+    });
+}
+void clsimhip_event_statistics_store_destroy(clsimhip_event_statistics_store *s) { delete s; }
+const char *clsimhip_event_statistics_store_last_error(const clsimhip_event_statistics_store *s) { (void)s; return g_last_error.c_str(); }
+int clsimhip_event_statistics_store_add_host(clsimhip_event_statistics_store *s, const clsimhip_event_statistics *records, size_t n,
+                                             const clsimhip_relabel *map, size_t n_map)
+{
+    return guarded(nullptr, [&] { need(s, "store"); s->impl->add_host(records, n, map, n_map); });
+}
+int clsimhip_event_statistics_store_add_device(clsimhip_event_statistics_store *s, const void *d_records, const void *d_count, size_t capacity,
+                                               const clsimhip_relabel *map, size_t n_map, void *hip_stream)
+{
+    return guarded(nullptr, [&] { need(s, "store"); s->impl->add_device(d_records, d_count, capacity, map, n_map, static_cast<hipStream_t>(hip_stream)); });
+}
+int clsimhip_event_statistics_store_drain_device(clsimhip_event_statistics_store *s, uint32_t last_frame, const clsimhip_relabel *map,
+                                                 size_t n_map, void *d_out, void *d_counts, size_t capacity, void *hip_stream)
+{
+    return guarded(nullptr, [&] { need(s, "store"); s->impl->drain_device(last_frame, map, n_map, d_out, d_counts, capacity, static_cast<hipStream_t>(hip_stream)); });
+}
+int clsimhip_event_statistics_store_drain_host(clsimhip_event_statistics_store *s, uint32_t last_frame, const clsimhip_relabel *map,
+                                               size_t n_map, clsimhip_event_statistics *out, size_t capacity, size_t *n)
+{
+    return guarded(nullptr, [&] { need(s, "store"); s->impl->drain_host(last_frame, map, n_map, out, capacity, n); });
+}
+int clsimhip_event_statistics_store_size(clsimhip_event_statistics_store *s, uint32_t last_frame, size_t *n)
+{
+    return guarded(nullptr, [&] { need(s, "store"); s->impl->size(last_frame, n); });
 }
 
 // ---- Photon hits (photon_hits.h) ----

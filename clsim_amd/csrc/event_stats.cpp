@@ -1,5 +1,5 @@
 // Event statistics (event_stats.h): what a bunch's particle table and mask become before any record is looked at, the host twin, the
-// two helpers of the C ABI, and the host side of the device stage.  The kernels are in event_stats_kernel.hip.
+// weight helper of the C ABI, and the host side of the device stage.  The kernels are in event_stats_kernel.hip.
 #include "event_stats.h"
 
 #include <algorithm>
@@ -143,27 +143,6 @@ void event_stats_host(const clsimhip_step *steps, size_t n_steps, const clsimhip
         event_stats_close(slots.data() + static_cast<size_t>(r) * kEventStatsSlots, identifier, frame, out[r]);
     }
     if (counters) std::memcpy(counters, counts, sizeof counts);
-}
-
-void event_stats_add(clsimhip_event_statistics &acc, const clsimhip_event_statistics &rec)
-{
-    const auto add_words = [](uint64_t *a, const uint64_t *b) {
-        uint64_t carry = 0u;
-        for (int k = 0; k < 6; ++k) {
-            const uint64_t s = a[k] + b[k];
-            const uint64_t c = s < a[k] ? 1u : 0u;
-            a[k] = s + carry;
-            carry = c | (a[k] < s ? 1u : 0u);
-        }
-    };
-    add_words(acc.generated_sum, rec.generated_sum);
-    add_words(acc.at_doms_sum, rec.at_doms_sum);
-    acc.generated_count += rec.generated_count;
-    acc.at_doms_count += rec.at_doms_count;
-    for (int k = 0; k < 3; ++k) {
-        acc.generated_special[k] += rec.generated_special[k];
-        acc.at_doms_special[k] += rec.at_doms_special[k];
-    }
 }
 
 double event_stats_weight(const uint64_t words[6], const uint32_t special[3])

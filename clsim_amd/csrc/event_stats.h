@@ -98,6 +98,33 @@ SERIES_HD void event_stats_close(const uint64_t *slots, uint32_t identifier, uin
     }
 }
 
+// ADD, acc += rec (include/clsimhip.h: clsimhip_event_statistics_add): the words of both sums with carry, modulo 2^384, both counts modulo
+// 2^64, the six special counters modulo 2^32; acc's identifier and frame stay.  Associative and commutative: what the event statistics
+// store (event_stats_store.h) rests on.
+SERIES_HD void event_stats_add_words(uint64_t *a, const uint64_t *b)
+{
+    uint64_t carry = 0u;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const uint64_t s = a[k] + b[k];
+        const uint64_t c = s < a[k] ? 1u : 0u;
+        a[k] = s + carry;
+        carry = c | (a[k] < s ? 1u : 0u);
+    }
+}
+SERIES_HD void event_stats_add(clsimhip_event_statistics &acc, const clsimhip_event_statistics &rec)
+{
+    event_stats_add_words(acc.generated_sum, rec.generated_sum);
+    event_stats_add_words(acc.at_doms_sum, rec.at_doms_sum);
+    acc.generated_count += rec.generated_count;
+    acc.at_doms_count += rec.at_doms_count;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        acc.generated_special[k] += rec.generated_special[k];
+        acc.at_doms_special[k] += rec.at_doms_special[k];
+    }
+}
+
 // the mask: keys frame rank << 32 | record word (string ID | OM ID << 16), ascending and distinct
 SERIES_HD bool event_stats_is_masked(const uint64_t *keys, uint32_t n, uint64_t key)
 {
@@ -153,8 +180,7 @@ void event_stats_device(int device, const void *d_steps, size_t n_steps, const v
 void event_stats_device_prepared(int device, const void *d_steps, size_t n_steps, const void *d_photons, const void *d_count, size_t capacity, const SeriesBunch &bunch,
                                  const uint8_t *h_blob, void *d_out, void *d_counters, void *d_workspace, size_t workspace_bytes, hipStream_t stream,
                                  hipEvent_t uploaded = nullptr);
-// the two helpers of the C ABI
-void event_stats_add(clsimhip_event_statistics &acc, const clsimhip_event_statistics &rec);
+// the helper of the C ABI that is host only (event_stats_add is above)
 double event_stats_weight(const uint64_t words[6], const uint32_t special[3]);
 
 } // namespace clsimhip

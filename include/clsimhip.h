@@ -1828,6 +1828,86 @@ int clsimhip_mcpe_parents_relabel_host(const clsimhip_mcpe_parent *parents, cons
                                        const clsimhip_relabel *map, size_t n_map, clsimhip_mcpe_parent *out,
                                        clsimhip_mcpe_parent_range *out_ranges, size_t *n_out);
 
+/* ---- Event statistics frame store: per frame and per particle, the exact sums of bunch after bunch ----------------------------
+ * The client module of the reference files four things into a frame: MCPEs, frame photons, PMT hits and I3CLSimEventStatistics
+ * (private/clsim/I3CLSimClientModule.cxx:728-740).  The first three have their frame stores above; this is the fourth.  A frame's light
+ * spans several bunches, and with muon slicing the particle table holds one entry per slice, while the user wants one record per
+ * muon and frame.  The sums are exact integers modulo 2^384 and the counts are modular too, so addition is associative and
+ * commutative, and the content of a store is a function of the multiset of records it was given: the same bytes whatever order the
+ * bunches arrive in, from the host twins and from the kernels.
+ * KEY of a record: (frame, identifier), compared as two unsigned 32-bit integers, frame first.
+ * EMPTY record: the 136 bytes behind identifier and frame are all zero.
+ * STATISTICS FORM: n records of clsimhip_event_statistics, strictly ascending in the key, none empty.  A record that is empty, or whose
+ *     key is not above its predecessor's, is one MALFORMED element.
+ * ADD: clsimhip_event_statistics_add -- sum words with carry modulo 2^384, counts modulo 2^64, special counters modulo 2^32.
+ * CANON(L, map) for any list L of records, in any key order, duplicates and empties allowed: drop the empty records (EMPTY_DROPPED);
+ *     replace every identifier that is a `from` of the map by its `to` (RELABELLED; the frame stays); sort by key; replace every run
+ *     of equal keys by its ADD-sum, carrying the key.  The result is a statistics form.  The map follows the series relabel stage's
+ *     rules (strictly ascending in `from`, no `to` equal to any `from`, CLSIMHIP_ERR_ARGUMENT otherwise; an empty map is allowed).  A run
+ *     may be as long as the input: addition needs no order inside a run, so there is no tie limit.
+ * COMBINE(A, B) of two statistics forms: merged by key, equal keys become one record by ADD; n_out <= n_a + n_b.
+ * SPLIT(X, last_frame): the head is the prefix with frame <= last_frame, the tail the rest; 0xFFFFFFFF drains everything.
+ * From these: COMBINE(A, B) = COMBINE(B, A); COMBINE(CANON(L1), CANON(L2)) = CANON(L1 ++ L2); CANON(CANON(L, no map), map) =
+ * CANON(L, map) -- folding the slices when a bunch is added and folding them when a frame is drained give the same bytes.
+ * The host twins (host only, no GPU is touched): malformed input or an output that does not fit is CLSIMHIP_ERR_ARGUMENT, with text
+ * that names the first offending element, and nothing is written.  counters[2] (may be NULL): RELABELLED, EMPTY_DROPPED. */
+#define CLSIMHIP_EVENT_STATISTICS_STORE_RELABELLED 0      /* index into the two counters */
+#define CLSIMHIP_EVENT_STATISTICS_STORE_EMPTY_DROPPED 1
+int clsimhip_event_statistics_canonical_host(const clsimhip_event_statistics *records, size_t n, const clsimhip_relabel *map, size_t n_map,
+                                             clsimhip_event_statistics *out, size_t capacity, size_t *n_out, uint64_t counters[2]);
+int clsimhip_event_statistics_combine_host(const clsimhip_event_statistics *a, size_t n_a, const clsimhip_event_statistics *b, size_t n_b,
+                                           clsimhip_event_statistics *out, size_t capacity, size_t *n_out);
+int clsimhip_event_statistics_split_host(const clsimhip_event_statistics *records, size_t n, uint32_t last_frame,
+                                         clsimhip_event_statistics *head, size_t head_capacity, size_t *n_head,
+                                         clsimhip_event_statistics *tail, size_t tail_capacity, size_t *n_tail);
+/* bytes of device memory the kernels need beside their inputs and outputs: COMBINE of (capacity_a, capacity_b); CANON of `capacity`
+ * records under a map of n_map entries takes (capacity, n_map), the map's copy included */
+size_t clsimhip_event_statistics_store_workspace_bytes(size_t capacity_a, size_t capacity_b);
+/* The kernels, on records that live in HBM, under the contract of clsimhip_mcpe_series_union_device: an input is read as
+ * min(*d_count, capacity) records, its count ONE uint32 in device memory -- word 3 of clsimhip_event_statistics_device's d_counters
+ * (the records written) chains in unchanged, and so does word 0 of another stage's output counts; records and d_workspace are
+ * 16-byte aligned, counts 4-byte; capacities are at most 2^31; the output must not overlap an input (CLSIMHIP_ERR_ARGUMENT);
+ * asynchronous on hip_stream (NULL = default stream), nothing waits for the device; whatever bytes the inputs hold, nothing is
+ * written beyond a capacity and every loop is bounded by one.  The map is host memory: it is checked and copied before the call
+ * returns.  Output counts are five uint32 in the union's layout:
+ *     CANON     records, 0, RELABELLED, EMPTY_DROPPED, overflow -- a result that does not fit delivers nothing (records = 0) and
+ *               reports the size it needs;
+ *     COMBINE   records, 0, MALFORMED elements in A, MALFORMED elements in B, overflow (the needed size when the result does not fit,
+ *               else 0).  B malformed, or a result that does not fit: the output is A unchanged.  A malformed: the output is empty.
+ *     SPLIT     head: records, 0, 0, 0, overflow -- a head that does not fit drains nothing and reports the size it needs; tail:
+ *               records, 0, 0, 0, 0.  tail_capacity must not be below capacity.  The input is taken as a statistics form. */
+int clsimhip_event_statistics_canonical_device(int device, const void *d_records, const void *d_count, size_t capacity,
+                                               const clsimhip_relabel *map, size_t n_map, void *d_out, void *d_out_counts, size_t out_capacity,
+                                               void *d_workspace, size_t workspace_bytes, void *hip_stream);
+int clsimhip_event_statistics_combine_device(int device, const void *d_a, const void *d_a_count, size_t capacity_a, const void *d_b,
+                                             const void *d_b_count, size_t capacity_b, void *d_out, void *d_out_counts, size_t out_capacity,
+                                             void *d_workspace, size_t workspace_bytes, void *hip_stream);
+int clsimhip_event_statistics_split_device(int device, const void *d_records, const void *d_count, size_t capacity, uint32_t last_frame,
+                                           void *d_head, void *d_head_counts, size_t head_capacity, void *d_tail, void *d_tail_counts,
+                                           size_t tail_capacity, void *hip_stream);
+/* THE STORE: add is COMBINE(store, CANON(bunch, map)) -- the bunch is any list of records, a result's records as they come, zeros
+ * included; drain delivers CANON(head of SPLIT(store, last_frame), map), and the tail becomes the store.  device < 0: a host store,
+ * which needs no GPU and takes no device call (CLSIMHIP_ERR_STATE).  Everything else is as the MCPE frame store documents it: two
+ * buffers used in turn; one event orders operations issued on different streams; five sticky counters (malformed bunches, their
+ * elements, bunches that did not fit, their records, malformed elements of the store itself), with _size and both drains returning
+ * CLSIMHIP_ERR_DEVICE while any is nonzero; add_host validates before anything moves and leaves the store unchanged on refusal (a host
+ * store also when the result would exceed its capacity); add_device drops a bunch whose result does not fit, whole, and counts it.
+ * _size and the capacity a drain asks of its output are those of the head BEFORE the drain's map folds it; the drain's d_counts are
+ * CANON's (records, 0, RELABELLED, EMPTY_DROPPED, overflow), with the split's overflow passed on. */
+typedef struct clsimhip_event_statistics_store clsimhip_event_statistics_store;
+int clsimhip_event_statistics_store_create(int device, size_t capacity, clsimhip_event_statistics_store **out);
+void clsimhip_event_statistics_store_destroy(clsimhip_event_statistics_store *s);
+const char *clsimhip_event_statistics_store_last_error(const clsimhip_event_statistics_store *s);
+int clsimhip_event_statistics_store_add_host(clsimhip_event_statistics_store *s, const clsimhip_event_statistics *records, size_t n,
+                                             const clsimhip_relabel *map, size_t n_map);
+int clsimhip_event_statistics_store_add_device(clsimhip_event_statistics_store *s, const void *d_records, const void *d_count, size_t capacity,
+                                               const clsimhip_relabel *map, size_t n_map, void *hip_stream);
+int clsimhip_event_statistics_store_drain_device(clsimhip_event_statistics_store *s, uint32_t last_frame, const clsimhip_relabel *map,
+                                                 size_t n_map, void *d_out, void *d_counts, size_t capacity, void *hip_stream);
+int clsimhip_event_statistics_store_drain_host(clsimhip_event_statistics_store *s, uint32_t last_frame, const clsimhip_relabel *map,
+                                               size_t n_map, clsimhip_event_statistics *out, size_t capacity, size_t *n);
+int clsimhip_event_statistics_store_size(clsimhip_event_statistics_store *s, uint32_t last_frame, size_t *n);
+
 #ifdef __cplusplus
 }
 #endif
